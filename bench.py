@@ -3,6 +3,7 @@
 
     python bench.py --gpus 1 --steps K --warmup W           # single GPU
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...   # row-block split
+    python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR   # + the headline call's output as DIR/*.npy
 
 A "step" is one kinematicWaveRouting call (one pass of the hot path over the whole raster): every land
 cell goes through one implicit Newton-Raphson solve = one cell-step.  Inputs (discharge, lateral
@@ -26,6 +27,8 @@ sys.path.insert(0, os.path.join(ROOT, "lisflood-code_amd"))
 
 B_ALG = 48.0          # algorithmic bytes per cell-step
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8 TB/s
+DUMP_MAX_VALUES = 6_000_000   # --dump-outputs: float64 values per array (48 MB); larger outputs are sampled
+DUMP_SEED = 20251015          # --dump-outputs: seed of the sampled positions
 
 
 def parse():
@@ -43,6 +46,10 @@ def parse():
                     help="run the row-block/RCCL path even with a single rank (smoke test of that path)")
     ap.add_argument("--calibrate", action="store_true",
                     help="run the known-traffic stream copies first (PMC calibration under rocprofv3)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the discharge the headline call left after its last timed step to DIR/discharge.npy "
+                         "(float64, pixel order; above %d cells the values at a fixed seeded sample of %d pixels, "
+                         "ascending)" % (DUMP_MAX_VALUES, DUMP_MAX_VALUES))
     return ap.parse_args()
 
 
@@ -83,11 +90,12 @@ def build_case(family, H, W):
     return kw, p, g
 
 
-def run_routing(kw, p, steps, warmup, nq=3, profile_steps=2, ordered=True):
+def run_routing(kw, p, steps, warmup, nq=3, profile_steps=2, ordered=True, keep_output=False):
     """-> dict(ms_per_step, event_ms_per_step, prof) with inputs resident in HBM.
 
     ordered=True : discharge / lateral inflow resident in the engine's sweep-order layout (lf_router_route_ordered)
     ordered=False: resident in the reference's pixel order, gathered/scattered inside the sweep (lf_router_route_device)
+    keep_output  : discharge = host copy (pixel order) of the discharge after the last timed call, else None
     """
     from lisflood_amd import _lib
     from lisflood_amd import synthetic as syn
@@ -115,6 +123,12 @@ def run_routing(kw, p, steps, warmup, nq=3, profile_steps=2, ordered=True):
     _lib.synchronize()
     t1 = time.perf_counter()
     stats = kw.last_launches()
+    discharge = None
+    if keep_output:         # before the profiled calls below route the same vector on
+        pix = kw.from_engine_order(Q) if ordered else Q
+        discharge = pix.download()
+        if ordered:
+            pix.free()
     # per-kernel durations with hipEvents on the launch stream (separate short pass: the event pairs
     # add host work per launch, so they are kept out of the timed region)
     kw.profile(True)
@@ -131,7 +145,20 @@ def run_routing(kw, p, steps, warmup, nq=3, profile_steps=2, ordered=True):
     for d in qs + [Q]:
         d.free()
     return dict(ms_per_step=(t1 - t0) * 1e3 / steps, event_ms_per_step=ev_ms / steps, prof=prof, stats=stats,
-                finite=ok, profile_steps=profile_steps, cells=N, checksum=crc)
+                finite=ok, profile_steps=profile_steps, cells=N, checksum=crc, discharge=discharge)
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: each `name -> vector` of `arrays` as directory/<name>.npy in float64, whole up to DUMP_MAX_VALUES
+    elements, else its elements at DUMP_MAX_VALUES positions drawn without replacement with DUMP_SEED (ascending): the
+    same positions on every run of the same raster, so that two builds can be compared output for output"""
+    os.makedirs(directory, exist_ok=True)
+    for name, x in arrays.items():
+        x = np.asarray(x, np.float64).ravel()
+        if x.size > DUMP_MAX_VALUES:
+            x = x[np.sort(np.random.default_rng(DUMP_SEED).choice(x.size, DUMP_MAX_VALUES, replace=False))]
+        np.save(os.path.join(directory, name + ".npy"), x)
+        log("[bench] %s: %d values -> %s" % (name, x.size, os.path.join(directory, name + ".npy")))
 
 
 def pmc_traffic(kernel_key, cells_per_launch):
@@ -723,6 +750,9 @@ def etrs89_bench(passes=3):
 def main():
     a = parse()
     world = int(os.environ.get("WORLD_SIZE", "1"))
+    if a.dump_outputs and (a.gpus > 1 or world > 1 or a.force_dist or a.only):
+        sys.exit("bench.py: --dump-outputs writes the output of the single-GPU headline call: not with more than one rank, "
+                 "--force-dist or --only")
     if a.gpus > 1 or world > 1 or a.force_dist:
         import bench_dist
         return bench_dist.main(a)
@@ -761,7 +791,9 @@ def main():
         _lib.synchronize()
         src.free(); dst.free()
     kw, p, g = build_case(a.family, H, W)
-    res = run_routing(kw, p, a.steps, a.warmup)
+    res = run_routing(kw, p, a.steps, a.warmup, keep_output=bool(a.dump_outputs))
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, {"discharge": res.pop("discharge")})
     N = kw.num_pixels
     value = N / res["ms_per_step"] / 1e3          # Mcell-steps/s
     out = {

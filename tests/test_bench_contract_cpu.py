@@ -153,3 +153,22 @@ def test_committed_compact_line_round6():
     assert "land_surface" in st and "canopy" not in st and st["land_surface"][0] < 14.8     # canopy 2.9 + soil 11.9 in round 5
     # (round 5: 23.6-24.6 ms; round 6: 22.4-23.7 depending on the box the line was taken on -- the boxes differ by ~5 %)
     assert legs["hot_path_deep_5000"]["ms"] < 24.6 and legs["hot_path_deep_5000"]["ms_unreported_maps_left_out"] < 20.6
+
+
+def test_dump_outputs_samples_large_outputs_at_fixed_positions(tmp_path):
+    """--dump-outputs: an output longer than DUMP_MAX_VALUES is written as its values at a fixed seeded set of positions
+    (ascending, no repeats), the same on every call; a short one whole; float64, under 64 MB in all."""
+    import sys
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    n = bench.DUMP_MAX_VALUES + 1000
+    x = np.arange(n, dtype=np.float64)
+    bench.dump_outputs(str(tmp_path / "a"), {"big": x, "small": x[:1000]})
+    bench.dump_outputs(str(tmp_path / "b"), {"big": x})
+    big = np.load(str(tmp_path / "a" / "big.npy"))
+    assert big.dtype == np.float64 and big.size == bench.DUMP_MAX_VALUES
+    assert (np.diff(big) > 0).all() and big[0] >= 0 and big[-1] < n        # positions of x, ascending, distinct
+    assert np.array_equal(big, np.load(str(tmp_path / "b" / "big.npy")))
+    assert np.array_equal(np.load(str(tmp_path / "a" / "small.npy")), x[:1000])
+    assert os.path.getsize(str(tmp_path / "a" / "big.npy")) < 64e6

@@ -2086,15 +2086,22 @@ def test_soil_pf_golden(amd):
 
 @pytest.mark.parametrize("family", ["saddle", "shallow"])
 def test_two_rank_rccl_halo_exchange(amd, family):
-    """The multi-GPU transport itself: 2 processes, one GPU each, boundary discharge over RCCL Send/Recv
-    (lf_dist_router_route) against the single-domain oracle.  Needs two visible devices; the single-GPU boxes run the
-    same kernels and plan through the device-copy loopback (test_row_block_partition_loopback)."""
+    """The multi-GPU transport itself: 2 processes, boundary discharge over RCCL Send/Recv (lf_dist_router_route) against
+    the single-domain oracle.  With two visible devices, one GPU each over the real RCCL.  With one, RCCL refuses two ranks
+    on the same device (test_real_rccl_gpu.py), so both ranks share it and the same Send/Recv calls go through the
+    stand-in tests/fake_rccl (test_dist_multirank_gpu.py), which also checks that the two ranks issue them in matching
+    order."""
     import subprocess
     import sys
     from lisflood_amd import _lib
-    if _lib.device_count() < 2:
-        pytest.skip("one GPU visible: RCCL Send/Recv needs a second device")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    if _lib.device_count() < 2:
+        if os.path.join(root, "tests") not in sys.path:
+            sys.path.insert(0, os.path.join(root, "tests"))
+        import test_dist_multirank_gpu as M
+        outs = M.run_ranks(M.fake_rccl_dir(), 2, "tests/dist_worker_rccl.py", {"LF_TEST_FAMILY": family})
+        assert "DIST_RCCL_OK" in outs[0][0] and "ranks=2" in outs[0][0]
+        return
     procs = []
     for rank in range(2):
         env = dict(os.environ, RANK=str(rank), WORLD_SIZE="2", LOCAL_RANK=str(rank), MASTER_ADDR="127.0.0.1",

@@ -12,6 +12,8 @@ sys.path.insert(0, os.path.join(ROOT, "lisflood-code_amd"))
 
 def main():
     world, out = int(sys.argv[1]), os.path.abspath(sys.argv[2])
+    if world > 6:
+        sys.exit("%d ranks on one GPU: at most six processes may have the device open at once" % world)
     args = ["--gpus", str(world), "--no-extra"] + sys.argv[3:]
     fake = os.path.join(ROOT, "tests", "fake_rccl")
     procs = []
