@@ -1402,77 +1402,6 @@ int lf_dist_routing_substep(lf_dist_router *r, lf_comm *comm, const lf_substep_a
 // ------------------------------------------------------------------------------------------------
 namespace {
 
-struct dist_fused_args {
-    const int *__restrict__ ups_base; // [N] first upstream position if the upstream cells are consecutive (then: same phase)
-    const int *__restrict__ ups_idx;  // fused lists: same-phase position, or -(slab slot) - 1
-    const int *__restrict__ out_slot; // [N] slab slot of the cell's router outputs, -1 none
-    int unit0, nunits;                // launch units (levels) of the phase
-};
-
-// k_fused_substeps (lf_fused.h) on one phase of a rank's block: launch t works on (unit t - s, sub-step s).  A cell
-// reads the router outputs of its same-phase upstream cells from the parity buffers (previous unit, written at t - 1)
-// and those of earlier phases / other ranks from the slabs; cells feeding a later phase or another rank store theirs in
-// the slabs.  The per-cell arithmetic is fused_cell's: bit-identical to the single-domain wavefront.
-template <bool SPLIT>
-__global__ void __launch_bounds__(kBlock) k_fused_substeps_dist(fused_args F, dist_fused_args D)
-{
-    int s, blk;
-    if (F.packed) {
-        int cnt = 0, start = 0;
-        for (int q = 0; q < F.nsteps; ++q) {
-            const bool ge = (int)blockIdx.x >= F.blk_start[q];
-            cnt += ge ? 1 : 0;
-            start = ge ? F.blk_start[q] : start;
-        }
-        s = cnt - 1;
-        blk = (int)blockIdx.x - start;
-    } else {
-        s = blockIdx.y;
-        blk = blockIdx.x;
-    }
-    int k;
-    if (F.use_lvl) { // beside k_fused_cones: the single (wide) level sub-step s works on at this wave time, -1 none
-        k = F.lvl[s];
-        if (k < 0) return;
-    } else {
-        k = F.t - s;
-        if (k < 0 || k >= D.nunits) return;
-        k += D.unit0;
-    }
-    const long long first = F.level_start[k];
-    const long long i = (long long)blk * kBlock + threadIdx.x;
-    if (i >= F.level_start[k + 1] - first) return;
-    const long long p = first + i;
-    const int u0 = F.ups_ptr[p], u1 = F.ups_ptr[p + 1];
-    // ups_base also marks runs of GHOST slots (positions >= N of the per-call state vector) as consecutive: here those
-    // come from the slabs, so only a run inside the local cells -- then: same phase, previous unit -- takes the short way
-    const int base_raw = D.ups_base[p];
-    const int base = (base_raw >= 0 && (long long)base_raw + (u1 - u0) <= F.n) ? base_raw : -1;
-    const int kmax = F.kmax;
-    const long long slot = D.out_slot[p];
-    const int *idx = D.ups_idx;
-    const double *slab1 = F.root1, *slab2 = F.root2;
-    const long long ss = F.root_ss, off = (long long)s * F.root_st;
-    fused_cell<SPLIT, false>(F, p, s, [=](const double *q, int section) {
-        if (base >= 0) return upstream_sum8(q, base, base + (u1 - u0), kmax);
-        const double *slab = section ? slab2 : slab1;
-        double v[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            double x = 0.0;
-            if (j < kmax && u0 + j < u1) {
-                const int e = idx[u0 + j];
-                x = e >= 0 ? q[e] : slab[(long long)(-(e + 1)) * ss + off];
-            }
-            v[j] = x;
-        }
-        double ups = 0.0;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) ups += v[j];
-        return ups;
-    }, slot);
-}
-
 int dist_fused_prepare(lf_dist_router *r, const lf_substep_args *a, int nsteps)
 {
     if (!r || !a || nsteps < 1) return lf_set_error(LF_E_INVALID, "bad argument");
@@ -1492,13 +1421,8 @@ int dist_fused_prepare(lf_dist_router *r, const lf_substep_args *a, int nsteps)
     }
     if (a->split && !r->slab2.p) LF_TRY(r->slab2.alloc(need));
     // which derived statics the wavefront may recompute instead of streaming (fused_args::recompute)
-    const char *e = std::getenv("LF_NO_RECOMPUTE");
-    if (r->N > 0 && !(e && e[0] == '1')) {
-        if (!r->derived_ok.p) LF_TRY(r->derived_ok.alloc(1));
-        hipStream_t s = r->ctx->stream;
-        LF_HIP(hipMemsetD32Async((hipDeviceptr_t)r->derived_ok.p, 3, 1, s));
-        hipLaunchKernelGGL(k_check_derived, dim3(blocks_for(r->N)), dim3(kBlock), 0, s, (long long)r->N, *a, r->a1.p, r->a2.p,
-                           r->dx_per_pixel ? r->dx.p : nullptr, r->dx_scalar, r->dt, r->derived_ok.p);
+    if (r->N > 0 && fused_recompute()) {
+        LF_TRY(fused_check_derived(*r, *a, r->ctx->stream));
         LF_HIP(hipGetLastError());
     } else {
         r->derived_ok.release();
@@ -1515,178 +1439,33 @@ int dist_fused_phase(lf_dist_router *r, const lf_substep_args *a, int nsteps, in
     if (nsteps != r->slab_steps && nsteps > r->slab_steps) return lf_set_error(LF_E_INVALID, "lf_dist_fused_prepare first");
     const int unit0 = r->phase_level[phase], nunits = r->phase_level[phase + 1] - unit0;
     if (nunits <= 0 || r->N == 0) return LF_OK;
-    fused_args F;
-    std::memset(&F, 0, sizeof(F));
-    F.S = *a;
-    F.ups_ptr = r->ups_ptr.p;
-    F.a1 = r->a1.p;
-    F.a2 = r->a2.p;
-    F.dx = r->dx_per_pixel ? r->dx.p : nullptr;
-    F.level_start = r->level_start.p;
-    F.qr1 = r->fused_qr1.p;
-    F.qr2 = r->fused_qr2.p;
+    fused_args F = fused_args_of(*r, *a, nsteps, msteps > 0 ? msteps : nsteps, sideflow_stride, side_mstride);
     F.root1 = r->slab1.p;
     F.root2 = r->slab2.p;
     F.nroots = r->n_slots;
     F.root_ss = r->slab_steps; // [slot][sub-step]
     F.root_st = 1;
-    F.n = r->N;
-    F.side_stride = sideflow_stride;
-    F.msteps = msteps > 0 ? msteps : nsteps; // several model steps per call: lf_dist_routing_model_steps_fused
-    F.side_mstride = side_mstride;
-    F.dx_scalar = r->dx_scalar;
-    F.beta = r->beta;
-    F.inv_beta = r->inv_beta;
-    F.b_minus_1 = r->b_minus_1;
-    F.kmax = r->kmax;
-    F.nlevels = (int)r->h_level_start.size() - 1;
-    F.nsteps = nsteps;
-    F.solve35 = r->fused ? 1 : 0;
     F.recompute = r->derived_ok.p;
-    F.dt = r->dt;
-    dist_fused_args D;
-    D.ups_base = r->ups_base.p;
-    D.ups_idx = r->ups_idx_f.p;
-    D.out_slot = r->out_slot.p;
-    D.unit0 = unit0;
-    D.nunits = nunits;
+    F.d_ups_base = r->ups_base.p;
+    F.d_ups_idx = r->ups_idx_f.p;
+    F.d_out_slot = r->out_slot.p;
     hipStream_t s = r->ctx->stream;
-    F.d_ups_base = D.ups_base;
-    F.d_ups_idx = D.ups_idx;
-    F.d_out_slot = D.out_slot;
-    // ---- a phase of few, wide levels: level after level, every level through all its sub-steps (k_fused_level_steps<DIST>,
-    // lf_fused.h; the single domain's rule and switches: LF_FUSED_TIME_MAJOR, LF_FUSED_TIME_MAJOR_LEVELS) -------------------
-    {
-        static const int tm_levels = [] {
-            const char *e = std::getenv("LF_FUSED_TIME_MAJOR_LEVELS");
-            return e ? std::atoi(e) : 192;
-        }();
-        const char *e = std::getenv("LF_FUSED_TIME_MAJOR");
-        const int64_t cells = r->h_level_start[unit0 + nunits] - r->h_level_start[unit0];
-        const bool want = e ? e[0] != '0' : (nunits <= tm_levels && cells >= 20000 * (int64_t)nunits);
-        if (want && nsteps > 1) {
-            const bool ok = lf_history_ensure(r->fused_hist1, r->fused_hist2, r->fused_hist_refused,
-                                              (size_t)nsteps * (size_t)r->N, a->split);
-            if (ok) {
-                F.hist1 = r->fused_hist1.p;
-                F.hist2 = r->fused_hist2.p;
-                const bool all35 = r->fused && a->Beta == 0.6;
-                for (int k = 0; k < nunits; ++k) {
-                    const int64_t w = r->h_level_start[unit0 + k + 1] - r->h_level_start[unit0 + k];
-                    if (w <= 0) continue;
-                    const dim3 grid(blocks_for(w)), block(kBlock);
-                    if (a->split && all35)
-                        hipLaunchKernelGGL((k_fused_level_steps<true, true, true>), grid, block, 0, s, F, unit0 + k);
-                    else if (a->split)
-                        hipLaunchKernelGGL((k_fused_level_steps<true, false, true>), grid, block, 0, s, F, unit0 + k);
-                    else if (all35)
-                        hipLaunchKernelGGL((k_fused_level_steps<false, true, true>), grid, block, 0, s, F, unit0 + k);
-                    else
-                        hipLaunchKernelGGL((k_fused_level_steps<false, false, true>), grid, block, 0, s, F, unit0 + k);
-                    r->last_launches++;
-                }
-                LF_HIP(hipGetLastError());
-                return LF_OK;
-            }
-            // no room for the history inside its budget (remembered in fused_hist_refused): the skewed wavefront below
-        }
-    }
-    if (!r->fb_phase_block.empty() && nsteps <= kMaxPackedSteps) { // blocks of levels, cone by cone (k_fused_cones<DIST>)
-        const int b0 = r->fb_phase_block[phase], NB = r->fb_phase_block[phase + 1] - b0;
-        F.fb_level = r->fb_level_dev.p;
-        F.fb_row = r->fb_row_dev.p;
-        F.fb_cone = r->fb_cone.p;
-        F.fb_off = r->fb_off_dev.p;
-        F.fb_block0 = b0;
-        F.fb_nblocks = NB;
-        auto cones = [&](int b) { return (int64_t)(r->fb_row[b + 1] - r->fb_row[b] - 1); };
-        auto multi = [&](int b) { return r->fb_level[b + 1] - r->fb_level[b] > 1; };
-        const bool all35 = r->fused && a->Beta == 0.6;
-        for (int t = 0; t < NB + nsteps - 1; ++t) {
-            F.t = t;
-            int64_t acc = 0;
-            for (int q = 0; q < nsteps; ++q) {
-                F.blk_start[q] = (int)acc;
-                const int b = t - q;
-                if (b >= 0 && b < NB && multi(b0 + b)) acc += cones(b0 + b);
-            }
-            F.blk_start[nsteps] = (int)acc;
-            if (acc >= ((int64_t)1 << 31)) return lf_set_error(LF_E_INVALID, "fused sub-steps: grid too large");
-            if (acc > 0) {
-                F.packed = 1;
-                F.use_lvl = 0;
-                const dim3 grid((unsigned)acc);
-                if (a->split && all35)
-                    hipLaunchKernelGGL((k_fused_cones<true, true, false, true>), grid, dim3(kBlock), 0, s, F);
-                else if (a->split)
-                    hipLaunchKernelGGL((k_fused_cones<true, false, false, true>), grid, dim3(kBlock), 0, s, F);
-                else if (all35)
-                    hipLaunchKernelGGL((k_fused_cones<false, true, false, true>), grid, dim3(kBlock), 0, s, F);
-                else
-                    hipLaunchKernelGGL((k_fused_cones<false, false, false, true>), grid, dim3(kBlock), 0, s, F);
-                r->last_launches++;
-            }
-            int64_t acc1 = 0, widest = 0;
-            for (int q = 0; q < nsteps; ++q) {
-                F.blk_start[q] = (int)acc1;
-                F.lvl[q] = -1;
-                const int b = t - q;
-                if (b >= 0 && b < NB && !multi(b0 + b)) {
-                    const int k = r->fb_level[b0 + b];
-                    const int64_t w = r->h_level_start[k + 1] - r->h_level_start[k];
-                    F.lvl[q] = k;
-                    acc1 += blocks_for(w);
-                    widest = std::max(widest, w);
-                }
-            }
-            F.blk_start[nsteps] = (int)acc1;
-            if (acc1 > 0) {
-                F.use_lvl = 1;
-                F.packed = 0;
-                dim3 grid(blocks_for(widest), nsteps);
-                if (2 * acc1 <= (int64_t)blocks_for(widest) * nsteps && acc1 < ((int64_t)1 << 31)) {
-                    F.packed = 1;
-                    grid = dim3((unsigned)acc1, 1);
-                }
-                if (a->split)
-                    hipLaunchKernelGGL((k_fused_substeps_dist<true>), grid, dim3(kBlock), 0, s, F, D);
-                else
-                    hipLaunchKernelGGL((k_fused_substeps_dist<false>), grid, dim3(kBlock), 0, s, F, D);
-                r->last_launches++;
-            }
-        }
-        LF_HIP(hipGetLastError());
-        return LF_OK;
-    }
-    auto width = [&](int k) { return r->h_level_start[unit0 + k + 1] - r->h_level_start[unit0 + k]; };
-    for (int t = 0; t < nunits + nsteps - 1; ++t) {
-        const int k_lo = std::max(0, t - nsteps + 1), k_hi = std::min(nunits - 1, t);
-        int64_t widest = 0;
-        for (int k = k_lo; k <= k_hi; ++k) widest = std::max(widest, width(k));
-        F.t = t;
-        dim3 grid(blocks_for(widest), nsteps);
-        F.packed = 0;
-        if (nsteps <= kMaxPackedSteps) {
-            int64_t acc = 0;
-            for (int q = 0; q < nsteps; ++q) {
-                F.blk_start[q] = (int)acc;
-                const int k = t - q;
-                if (k >= 0 && k < nunits) acc += blocks_for(width(k));
-            }
-            F.blk_start[nsteps] = (int)acc;
-            if (2 * acc <= (int64_t)blocks_for(widest) * nsteps && acc < ((int64_t)1 << 31)) {
-                F.packed = 1;
-                grid = dim3((unsigned)std::max<int64_t>(acc, 1), 1);
-            }
-        }
+    // the units of the phase and their level blocks through the DIST kernels (fused_wavefront, lf_fused.h); no sites
+    auto cones = [&](int64_t ncones) {
+        fused_pick(a->split, r->fused && a->Beta == 0.6, [&](auto sp, auto a35) {
+            hipLaunchKernelGGL((k_fused_cones<sp, a35, false, true>), dim3((unsigned)ncones), dim3(kBlock), 0, s, F);
+        });
+    };
+    auto levels = [&](dim3 grid) {
         if (a->split)
-            hipLaunchKernelGGL((k_fused_substeps_dist<true>), grid, dim3(kBlock), 0, s, F, D);
+            hipLaunchKernelGGL((k_fused_substeps<true, false, true>), grid, dim3(kBlock), 0, s, F);
         else
-            hipLaunchKernelGGL((k_fused_substeps_dist<false>), grid, dim3(kBlock), 0, s, F, D);
-        r->last_launches++;
-    }
-    LF_HIP(hipGetLastError());
-    return LF_OK;
+            hipLaunchKernelGGL((k_fused_substeps<false, false, true>), grid, dim3(kBlock), 0, s, F);
+    };
+    const int b0 = r->fb_phase_block.empty() ? 0 : r->fb_phase_block[phase];
+    const int NB = r->fb_phase_block.empty() ? -1 : r->fb_phase_block[phase + 1] - b0;
+    return fused_wavefront<true>(*r, F, unit0, nunits, b0, NB, true, s, r->last_launches, cones, levels,
+                                 [](bool, int, int) {});
 }
 
 } // namespace

@@ -1,7 +1,9 @@
-// lf_fused.h -- device code of the fused multi-sub-step routing wavefront (routing.py:512-603, 693-703 around
-// kinematic_wave_parallel_tools.py:34-92), shared by the single-GPU router (lf_router.hip) and the row-block partition
-// (lf_dist.hip).  See the comment block above lf_routing_substeps_fused in lf_router.hip for the scheme.
+// lf_fused.h -- device code and launch schedule of the fused multi-sub-step routing wavefront (routing.py:512-603,
+// 693-703 around kinematic_wave_parallel_tools.py:34-92), shared by the single-GPU router (lf_router.hip) and the row-block
+// partition (lf_dist.hip).  See the comment block above lf_routing_substeps_fused in lf_router.hip for the scheme.
 #pragma once
+#include <cstring>
+
 #include "lf_blocks.h"
 #include "lf_structures.h"
 #include "lf_sweep.h"
@@ -62,6 +64,10 @@ struct fused_args {
     // k_fused_substeps beside k_fused_cones: the level of sub-step s at this wave time (-1: none) instead of t - s
     int use_lvl;
     int lvl[kMaxPackedSteps];
+    // first level of this wavefront (row-block partition: the first unit of the phase; k_fused_substeps<DIST> works on
+    // levels level0 + [0, nlevels), lvl[] counts from it), else 0.  (Fits the struct's tail padding: the kernel argument
+    // behind the struct, k_fused_level_steps' level, keeps its offset.)
+    int level0;
 };
 
 // sub-step s inside its model step (fused_args::msteps); s is uniform, so these are scalar operations
@@ -385,7 +391,11 @@ __device__ __forceinline__ void fused_cell(const fused_args &F, long long p, int
     }
 }
 
-template <bool SPLIT, bool STRUCT>
+// DIST (row-block partition, one phase: levels [level0, level0 + nlevels)): a cell reads the router outputs of its
+// same-phase upstream cells from the parity buffers (previous level, written at t - 1) and those of earlier phases / other
+// ranks from the slabs; cells feeding a later phase or another rank store theirs in the slabs.  The per-cell arithmetic is
+// fused_cell's: bit-identical to the single-domain wavefront.
+template <bool SPLIT, bool STRUCT, bool DIST = false>
 __global__ void __launch_bounds__(kBlock) k_fused_substeps(fused_args F)
 {
     int s, blk;
@@ -403,15 +413,46 @@ __global__ void __launch_bounds__(kBlock) k_fused_substeps(fused_args F)
         s = blockIdx.y;
         blk = blockIdx.x;
     }
-    const int k = F.use_lvl ? F.lvl[s] : F.t - s; // level handled by this sub-step at wave time t
+    int k = F.use_lvl ? F.lvl[s] : F.t - s; // level handled by this sub-step at wave time t
     if (k < 0 || k >= F.nlevels) return;
+    if (DIST) k += F.level0;
     const long long first = F.level_start[k];
     const long long i = (long long)blk * kBlock + threadIdx.x;
     if (i >= F.level_start[k + 1] - first) return;
     const long long p = first + i;
     const int u0 = F.ups_ptr[p], u1 = F.ups_ptr[p + 1];
+    if (!DIST) {
+        const int kmax = F.kmax;
+        fused_cell<SPLIT, STRUCT>(F, p, s, [u0, u1, kmax](const double *q, int) { return upstream_sum8_pairs(q, u0, u1, kmax); });
+        return;
+    }
+    // ups_base also marks runs of GHOST slots (positions >= N of the per-call state vector) as consecutive: here those
+    // come from the slabs, so only a run inside the local cells -- then: same phase, previous level -- takes the short way
+    const int base_raw = F.d_ups_base[p];
+    const int base = (base_raw >= 0 && (long long)base_raw + (u1 - u0) <= F.n) ? base_raw : -1;
     const int kmax = F.kmax;
-    fused_cell<SPLIT, STRUCT>(F, p, s, [u0, u1, kmax](const double *q, int) { return upstream_sum8_pairs(q, u0, u1, kmax); });
+    const long long slot = F.d_out_slot[p];
+    const int *idx = F.d_ups_idx;
+    const double *slab1 = F.root1, *slab2 = F.root2;
+    const long long ss = F.root_ss, off = (long long)s * F.root_st;
+    fused_cell<SPLIT, STRUCT>(F, p, s, [=](const double *q, int section) {
+        if (base >= 0) return upstream_sum8(q, base, base + (u1 - u0), kmax);
+        const double *slab = section ? slab2 : slab1;
+        double v[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            double x = 0.0;
+            if (j < kmax && u0 + j < u1) {
+                const int e = idx[u0 + j];
+                x = e >= 0 ? q[e] : slab[(long long)(-(e + 1)) * ss + off];
+            }
+            v[j] = x;
+        }
+        double ups = 0.0;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) ups += v[j];
+        return ups;
+    }, slot);
 }
 
 // ---- several levels per launch: the wavefront over LEVEL BLOCKS, one workgroup per upstream cone --------------------
@@ -853,7 +894,7 @@ __device__ __forceinline__ void cone_compute(const fused_args &F, const cone_cel
 #endif
 // DIST (row-block partition, a phase's levels): upstream cells are a consecutive local run (hist), or come from the list --
 // same-phase positions (hist) and slab slots (earlier phases, other ranks: the slabs hold every sub-step) --, and a cell
-// whose router outputs cross a phase or rank boundary also writes them to its slab slot, as k_fused_substeps_dist does.
+// whose router outputs cross a phase or rank boundary also writes them to its slab slot, as k_fused_substeps<DIST> does.
 template <bool SPLIT, bool ALL35, bool DIST = false>
 __global__ void __launch_bounds__(kBlock) LF_TM_ATTR k_fused_level_steps(fused_args F, int k)
 {
@@ -867,7 +908,7 @@ __global__ void __launch_bounds__(kBlock) LF_TM_ATTR k_fused_level_steps(fused_a
     int base = u0;
     long long slot = -1;
     if (DIST) {
-        const int base_raw = F.d_ups_base[p]; // (a run of ghost slots is not a local run: see k_fused_substeps_dist)
+        const int base_raw = F.d_ups_base[p]; // (a run of ghost slots is not a local run: see k_fused_substeps<DIST>)
         base = (base_raw >= 0 && (long long)base_raw + (u1 - u0) <= n) ? base_raw : -1;
         slot = F.d_out_slot[p];
     }
@@ -1177,7 +1218,7 @@ __global__ void __launch_bounds__(CW) __attribute__((amdgpu_waves_per_eu(LF_CONE
         if (!cone_skip<SPLIT>(cur)) {
             double ups1, ups2 = 0.0;
             // row-block partition: the upstream cells are the consecutive local run [base, base + count) -- a run of ghost
-            // slots is not one, see k_fused_substeps_dist -- or come from the list: same-phase cells (level before: LDS,
+            // slots is not one, see k_fused_substeps<DIST> -- or come from the list: same-phase cells (level before: LDS,
             // or the parity buffers for the block's first level) and slab slots (earlier phases, other ranks)
             const int cu0 = DIST ? cur.base : cur.u0, cu1 = DIST ? cur.base + (cur.u1 - cur.u0) : cur.u1;
             if (DIST && (cur.base < 0 || (long long)cu1 > F.n)) {
@@ -1674,6 +1715,202 @@ __global__ void __launch_bounds__(64 * (1 + KC)) k_fused_cones_split(fused_args 
         body(std::true_type());
     else
         body(std::false_type());
+}
+
+// ================================================================================================
+// Host side: the launch schedule of the wavefront, shared by the single domain (lf_router.hip: all levels) and the row-block
+// partition (lf_dist.hip: the levels and level blocks of one phase).  R is lf_router or lf_dist_router, whose members used
+// here have the same names and meanings.
+// ================================================================================================
+
+// The instantiation of a kernel for two run-time flags: fn(std::bool_constant<a>, std::bool_constant<b>)
+template <class Fn>
+void fused_pick(bool a, bool b, Fn &&fn)
+{
+    if (a && b)
+        fn(std::true_type(), std::true_type());
+    else if (a)
+        fn(std::true_type(), std::false_type());
+    else if (b)
+        fn(std::false_type(), std::true_type());
+    else
+        fn(std::false_type(), std::false_type());
+}
+
+// fused_args of nsteps sub-steps (msteps per model step) from the router's statics; the wave fields are the schedule's,
+// the rest (structures, slabs, recompute flag, ...) stays zero for the caller
+template <class R>
+fused_args fused_args_of(const R &r, const lf_substep_args &a, int nsteps, int msteps, int64_t side_stride, int64_t side_mstride)
+{
+    fused_args F;
+    std::memset(&F, 0, sizeof(F));
+    F.S = a;
+    F.ups_ptr = r.ups_ptr.p;
+    F.a1 = r.a1.p;
+    F.a2 = r.a2.p;
+    F.dx = r.dx_per_pixel ? r.dx.p : nullptr;
+    F.level_start = r.level_start.p;
+    F.qr1 = r.fused_qr1.p;
+    F.qr2 = r.fused_qr2.p;
+    F.n = r.N;
+    F.side_stride = side_stride;
+    F.msteps = msteps;
+    F.side_mstride = side_mstride;
+    F.dx_scalar = r.dx_scalar;
+    F.beta = r.beta;
+    F.inv_beta = r.inv_beta;
+    F.b_minus_1 = r.b_minus_1;
+    F.kmax = r.kmax;
+    F.nsteps = nsteps;
+    F.solve35 = r.fused ? 1 : 0;
+    F.dt = r.dt;
+    return F;
+}
+
+// fused_args::recompute: LF_NO_RECOMPUTE=1 streams the derived statics as given (A/B switch)
+inline bool fused_recompute()
+{
+    const char *e = std::getenv("LF_NO_RECOMPUTE");
+    return !(e && e[0] == '1');
+}
+
+// ... otherwise k_check_derived over the router's cells sets the flags in r.derived_ok
+template <class R>
+int fused_check_derived(R &r, const lf_substep_args &a, hipStream_t s)
+{
+    if (!r.derived_ok.p) LF_TRY(r.derived_ok.alloc(1));
+    LF_HIP(hipMemsetD32Async((hipDeviceptr_t)r.derived_ok.p, 3, 1, s));
+    hipLaunchKernelGGL(k_check_derived, dim3(blocks_for(r.N)), dim3(kBlock), 0, s, (long long)r.N, a, r.a1.p, r.a2.p,
+                       r.dx_per_pixel ? r.dx.p : nullptr, r.dx_scalar, r.dt, r.derived_ok.p);
+    return LF_OK;
+}
+
+// The wavefront over levels [level0, level0 + nlevels) -- and, if nblocks >= 0, their level blocks [b0, b0 + nblocks) --
+// for F.nsteps sub-steps; fills F's wave fields and adds its launches to `launches`.  Of the three schedules the first that
+// applies runs:
+//   time-major   (time_major: the caller's precondition) one k_fused_level_steps launch per level;
+//   level blocks (nblocks >= 0, F.nsteps <= kMaxPackedSteps) per wave time t: cones(ncones) launches the multi-level
+//                blocks through a cone kernel on a packed grid of ncones workgroups, levels(grid) the single levels
+//                through k_fused_substeps (F.use_lvl);
+//   levels       per wave time t: levels(grid), level t - s for sub-step s.
+// sites(blocks, lo, hi) runs first at every wave time t, with the window [lo, hi] of the level blocks (blocks = true) or
+// levels in flight, counted from b0 / level0.
+template <bool DIST, class R, class Cones, class Levels, class Sites>
+int fused_wavefront(R &r, fused_args &F, int level0, int nlevels, int b0, int nblocks, bool time_major, hipStream_t s,
+                    int64_t &launches, Cones &&cones, Levels &&levels, Sites &&sites)
+{
+    const int nsteps = F.nsteps;
+    const bool split = F.S.split != 0, all35 = r.fused && F.S.Beta == 0.6; // otherwise: run-time flags and OCML pow
+    auto width = [&](int k) { return r.h_level_start[k + 1] - r.h_level_start[k]; };
+    F.level0 = level0;
+    F.nlevels = nlevels;
+    // ---- few, wide levels: level after level, every level through all its sub-steps (k_fused_level_steps) ----------------
+    // LF_FUSED_TIME_MAJOR=0 / 1: never / whenever it applies (A/B switch); LF_FUSED_TIME_MAJOR_LEVELS: the level count up to
+    // which it is the default -- each launch carries a dependent chain of nsteps solves (~10 us), so NL launches of that
+    // kind must stay small beside what the saved traffic (~3.8 kB per cell and model step) is worth
+    static const int tm_levels = [] {
+        const char *e = std::getenv("LF_FUSED_TIME_MAJOR_LEVELS");
+        return e ? std::atoi(e) : 192;
+    }();
+    const char *e = std::getenv("LF_FUSED_TIME_MAJOR");
+    const int64_t cells = r.h_level_start[level0 + nlevels] - r.h_level_start[level0];
+    const bool want = e ? e[0] != '0' : (nlevels <= tm_levels && cells >= 20000 * (int64_t)nlevels);
+    // (no room for the history inside its budget, remembered in fused_hist_refused: the skewed wavefront below)
+    if (time_major && want && nsteps > 1 &&
+        lf_history_ensure(r.fused_hist1, r.fused_hist2, r.fused_hist_refused, (size_t)nsteps * (size_t)r.N, split)) {
+        F.hist1 = r.fused_hist1.p;
+        F.hist2 = r.fused_hist2.p;
+        for (int k = level0; k < level0 + nlevels; ++k) {
+            const int64_t w = width(k);
+            if (w <= 0) continue;
+            fused_pick(split, all35, [&](auto sp, auto a35) {
+                hipLaunchKernelGGL((k_fused_level_steps<sp, a35, DIST>), dim3(blocks_for(w)), dim3(kBlock), 0, s, F, k);
+            });
+            ++launches;
+        }
+        LF_HIP(hipGetLastError());
+        return LF_OK;
+    }
+    // grid of a level-kernel launch whose blocks, packed by sub-step, are F.blk_start[0 .. nsteps]: the packed 1-D grid
+    // only where it saves at least half of the blocks of the 2-D one sized by the widest level -- finding its sub-step
+    // costs a block ~1.7 us (24 scalar kernarg loads), which shows on latency-bound launches (deep 5000^2: 65.2 vs 56.7 ms
+    // per model step, same-call A/B) but is nothing against 360 000 empty blocks (2000^2 hot path: 14.5 vs 16.1 ms)
+    auto level_grid = [&](bool pack, int64_t packed_blocks, int64_t widest) {
+        F.packed = pack && 2 * packed_blocks <= (int64_t)blocks_for(widest) * nsteps && packed_blocks < ((int64_t)1 << 31);
+        return F.packed ? dim3((unsigned)std::max<int64_t>(packed_blocks, 1), 1) : dim3(blocks_for(widest), nsteps);
+    };
+    if (nblocks >= 0 && nsteps <= kMaxPackedSteps) { // several levels per launch (k_fused_cones)
+        F.fb_level = r.fb_level_dev.p;
+        F.fb_row = r.fb_row_dev.p;
+        F.fb_cone = r.fb_cone.p;
+        F.fb_off = r.fb_off_dev.p;
+        F.fb_block0 = b0;
+        F.fb_nblocks = nblocks;
+        auto ncones = [&](int b) { return (int64_t)(r.fb_row[b0 + b + 1] - r.fb_row[b0 + b] - 1); };
+        auto multi = [&](int b) { return r.fb_level[b0 + b + 1] - r.fb_level[b0 + b] > 1; };
+        for (int t = 0; t < nblocks + nsteps - 1; ++t) {
+            // (block t - q, sub-step q), q = 0 .. nsteps-1, are independent of each other: the blocks of several levels go
+            // to the cone kernel, the single (wide) levels to the level kernel, which streams them at full occupancy
+            F.t = t;
+            sites(true, std::max(0, t - nsteps + 1), std::min(nblocks - 1, t));
+            int64_t acc = 0;
+            for (int q = 0; q < nsteps; ++q) {
+                F.blk_start[q] = (int)acc;
+                const int b = t - q;
+                if (b >= 0 && b < nblocks && multi(b)) acc += ncones(b);
+            }
+            F.blk_start[nsteps] = (int)acc;
+            if (acc >= ((int64_t)1 << 31)) return lf_set_error(LF_E_INVALID, "fused sub-steps: grid too large");
+            if (acc > 0) {
+                F.packed = 1;
+                F.use_lvl = 0;
+                cones(acc);
+                ++launches;
+            }
+            int64_t acc1 = 0, widest = 0;
+            for (int q = 0; q < nsteps; ++q) {
+                F.blk_start[q] = (int)acc1;
+                F.lvl[q] = -1;
+                const int b = t - q;
+                if (b >= 0 && b < nblocks && !multi(b)) {
+                    const int k = r.fb_level[b0 + b];
+                    F.lvl[q] = k - level0;
+                    acc1 += blocks_for(width(k));
+                    widest = std::max(widest, width(k));
+                }
+            }
+            F.blk_start[nsteps] = (int)acc1;
+            if (acc1 > 0) {
+                F.use_lvl = 1;
+                levels(level_grid(true, acc1, widest));
+                ++launches;
+            }
+        }
+        LF_HIP(hipGetLastError());
+        return LF_OK;
+    }
+    for (int t = 0; t < nlevels + nsteps - 1; ++t) {
+        // widest level inside the window [t - nsteps + 1, t]
+        const int k_lo = std::max(0, t - nsteps + 1), k_hi = std::min(nlevels - 1, t);
+        int64_t widest = 0;
+        for (int k = k_lo; k <= k_hi; ++k) widest = std::max(widest, width(level0 + k));
+        F.t = t;
+        sites(false, k_lo, k_hi);
+        const bool pack = nsteps <= kMaxPackedSteps;
+        int64_t acc = 0;
+        if (pack) {
+            for (int q = 0; q < nsteps; ++q) {
+                F.blk_start[q] = (int)acc;
+                const int k = t - q;
+                if (k >= 0 && k < nlevels) acc += blocks_for(width(level0 + k));
+            }
+            F.blk_start[nsteps] = (int)acc;
+        }
+        levels(level_grid(pack, acc, widest));
+        ++launches;
+    }
+    LF_HIP(hipGetLastError());
+    return LF_OK;
 }
 
 } // namespace

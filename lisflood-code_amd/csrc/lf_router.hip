@@ -1439,48 +1439,11 @@ int fused_impl(lf_router *r, const lf_substep_args *a, int nsteps, int64_t sidef
     if (n == 0) return LF_OK;
     if (!r->fused_qr1.p) LF_TRY(r->fused_qr1.alloc(2 * n));
     if (a->split && !r->fused_qr2.p) LF_TRY(r->fused_qr2.alloc(2 * n));
-    fused_args F;
-    F.S = *a;
-    F.ups_ptr = r->ups_ptr.p;
-    F.a1 = r->a1.p;
-    F.a2 = r->a2.p;
-    F.dx = r->dx_per_pixel ? r->dx.p : nullptr;
-    F.level_start = r->level_start.p;
-    F.qr1 = r->fused_qr1.p;
-    F.qr2 = r->fused_qr2.p;
-    F.hist1 = F.hist2 = nullptr;
-    F.root1 = F.root2 = nullptr;
-    F.nroots = 0;
-    F.root_ss = 1;
-    F.root_st = 0;
-    F.n = n;
-    F.side_stride = sideflow_stride;
-    F.msteps = msteps;
-    F.side_mstride = side_mstride;
-    F.dx_scalar = r->dx_scalar;
-    F.beta = r->beta;
-    F.inv_beta = r->inv_beta;
-    F.b_minus_1 = r->b_minus_1;
-    F.kmax = r->kmax;
-    F.nlevels = (int)r->NL;
-    F.nsteps = nsteps;
-    F.solve35 = r->fused ? 1 : 0;
+    fused_args F = fused_args_of(*r, *a, nsteps, msteps, sideflow_stride, side_mstride);
     F.linked = r->linked.p;
     F.level_nlinked = r->level_nlinked.p;
-    F.inert = nullptr;
-    F.site_level = nullptr;
-    F.fb_level = F.fb_row = F.fb_cone = nullptr;
-    F.fb_off = nullptr;
-    F.fb_lvl2blk = nullptr;
-    F.fb_nblocks = 0;
-    F.fb_block0 = 0;
-    F.d_ups_base = F.d_ups_idx = F.d_out_slot = nullptr;
-    F.recompute = nullptr;
-    F.dt = r->dt;
-    F.use_lvl = 0;
-    std::memset(&F.I, 0, sizeof(F.I));
+    F.fb_lvl2blk = r->fb_lvl2blk_dev.p;
     hipStream_t s = r->ctx->stream;
-    const int NL = (int)r->NL;
     // ---- structures: levels of the site cells; every cell feeding a site must sit on the site's own level ----------
     std::vector<int> lv_sorted;
     int64_t nsites = 0;
@@ -1544,10 +1507,7 @@ int fused_impl(lf_router *r, const lf_substep_args *a, int nsteps, int64_t sidef
         }
     }
     int64_t launches = 0;
-    bool grid2d = false;
     {
-        const char *e2 = std::getenv("LF_FUSED_2D_GRID"); // A/B switch: one grid row per sub-step, sized by the widest
-        grid2d = e2 && e2[0] == '1';
         const char *e = std::getenv("LF_NO_INERT_SKIP"); // A/B switch
         if (!in && r->n_isolated > 0 && nsteps > 1 && !(e && e[0] == '1')) {
             if (!r->inert.p) LF_TRY(r->inert.alloc(n));
@@ -1557,232 +1517,67 @@ int fused_impl(lf_router *r, const lf_substep_args *a, int nsteps, int64_t sidef
             ++launches;
         }
     }
-    {
-        const char *e = std::getenv("LF_NO_RECOMPUTE"); // A/B switch: stream the derived statics as given
-        if (!(e && e[0] == '1') && nsteps > 1) {
-            if (!r->derived_ok.p) LF_TRY(r->derived_ok.alloc(1));
-            LF_HIP(hipMemsetD32Async((hipDeviceptr_t)r->derived_ok.p, 3, 1, s));
-            hipLaunchKernelGGL(k_check_derived, dim3(blocks_for(n)), dim3(kBlock), 0, s, (long long)n, *a, r->a1.p, r->a2.p,
-                               F.dx, r->dx_scalar, r->dt, r->derived_ok.p);
-            F.recompute = r->derived_ok.p;
-            ++launches;
-        }
-    }
-    // ---- few, wide levels: level after level, every level through all its sub-steps (k_fused_level_steps) ----------------
-    // LF_FUSED_TIME_MAJOR=0 / 1: never / whenever it applies (A/B switch); LF_FUSED_TIME_MAJOR_LEVELS: the level count up to
-    // which it is the default -- each launch carries a dependent chain of nsteps solves (~10 us), so NL launches of that
-    // kind must stay small beside what the saved traffic (~3.8 kB per cell and model step) is worth
-    {
-        static const int tm_levels = [] {
-            const char *e = std::getenv("LF_FUSED_TIME_MAJOR_LEVELS");
-            return e ? std::atoi(e) : 192;
-        }();
-        const char *e = std::getenv("LF_FUSED_TIME_MAJOR");
-        const bool applies = !in && !F.linked && nsteps > 1;
-        const bool want = e ? e[0] != '0' : (NL <= tm_levels && n >= 20000 * (int64_t)NL);
-        if (applies && want) {
-            const bool ok = lf_history_ensure(r->fused_hist1, r->fused_hist2, r->fused_hist_refused, (size_t)nsteps * n, a->split);
-            if (ok) {
-                F.hist1 = r->fused_hist1.p;
-                F.hist2 = r->fused_hist2.p;
-                for (int k = 0; k < NL; ++k) {
-                    const int64_t w = r->h_level_start[k + 1] - r->h_level_start[k];
-                    if (w <= 0) continue;
-                    const bool all35 = r->fused && a->Beta == 0.6;
-                    if (a->split && all35)
-                        hipLaunchKernelGGL((k_fused_level_steps<true, true>), dim3(blocks_for(w)), dim3(kBlock), 0, s, F, k);
-                    else if (a->split)
-                        hipLaunchKernelGGL((k_fused_level_steps<true, false>), dim3(blocks_for(w)), dim3(kBlock), 0, s, F, k);
-                    else if (all35)
-                        hipLaunchKernelGGL((k_fused_level_steps<false, true>), dim3(blocks_for(w)), dim3(kBlock), 0, s, F, k);
-                    else
-                        hipLaunchKernelGGL((k_fused_level_steps<false, false>), dim3(blocks_for(w)), dim3(kBlock), 0, s, F, k);
-                    ++launches;
-                }
-                LF_HIP(hipGetLastError());
-                r->last_stats[0] = launches;
-                r->last_stats[1] = launches;
-                r->last_stats[2] = 0;
-                r->last_stats[3] = r->NL;
-                return LF_OK;
-            }
-            // no room for the history inside its budget (remembered in fused_hist_refused): the skewed wavefront below
-        }
-    }
-    if (r->fb_lmax > 1 && nsteps <= kMaxPackedSteps) { // several levels per launch (k_fused_cones)
-        const int NB = (int)r->fb_level.size() - 1;
-        F.fb_level = r->fb_level_dev.p;
-        F.fb_row = r->fb_row_dev.p;
-        F.fb_cone = r->fb_cone.p;
-        F.fb_off = r->fb_off_dev.p;
-        F.fb_lvl2blk = r->fb_lvl2blk_dev.p;
-        F.fb_nblocks = NB;
-        std::vector<int> site_blocks; // sorted blocks of the lakes and reservoirs
-        for (int lv : lv_sorted) site_blocks.push_back(r->fb_lvl2blk[lv]);
-        auto cones = [&](int b) { return (int64_t)(r->fb_row[b + 1] - r->fb_row[b] - 1); };
-        auto multi = [&](int b) { return r->fb_level[b + 1] - r->fb_level[b] > 1; };
-        const bool all35 = r->fused && a->Beta == 0.6; // otherwise: run-time flags and inlined OCML pow, as fused_cell
-        for (int t = 0; t < NB + nsteps - 1; ++t) {
-            // (block t - q, sub-step q), q = 0 .. nsteps-1, are independent of each other: the blocks of several levels go
-            // to the cone kernel, the single (wide) levels to the level kernel, which streams them at full occupancy
-            F.t = t;
-            if (nsites > 0) { // sites of the blocks [t - nsteps + 1, t]: sub-step t - block, before the cells of that block
-                const int b_lo = std::max(0, t - nsteps + 1), b_hi = std::min(NB - 1, t);
-                auto it = std::lower_bound(site_blocks.begin(), site_blocks.end(), b_lo);
-                if (it != site_blocks.end() && *it <= b_hi) {
-                    hipLaunchKernelGGL(k_sites_blocks, dim3(blocks_for(nsites)), dim3(kBlock), 0, s, F);
-                    ++launches;
-                }
-            }
-            int64_t acc = 0;
-            for (int q = 0; q < nsteps; ++q) {
-                F.blk_start[q] = (int)acc;
-                const int b = t - q;
-                if (b >= 0 && b < NB && multi(b)) acc += cones(b);
-            }
-            F.blk_start[nsteps] = (int)acc;
-            if (acc >= ((int64_t)1 << 31)) return lf_set_error(LF_E_INVALID, "fused sub-steps: grid too large");
-            if (acc > 0) {
-                F.packed = 1;
-                F.use_lvl = 0;
-                const dim3 grid((unsigned)acc);
-#define LF_CONES_CW(ST, CW)                                                                                  \
-    do {                                                                                                     \
-        if (a->split && all35)                                                                               \
-            hipLaunchKernelGGL((k_fused_cones<true, true, ST, false, CW>), grid, dim3(CW), 0, s, F);         \
-        else if (a->split)                                                                                   \
-            hipLaunchKernelGGL((k_fused_cones<true, false, ST, false, CW>), grid, dim3(CW), 0, s, F);        \
-        else if (all35)                                                                                      \
-            hipLaunchKernelGGL((k_fused_cones<false, true, ST, false, CW>), grid, dim3(CW), 0, s, F);        \
-        else                                                                                                 \
-            hipLaunchKernelGGL((k_fused_cones<false, false, ST, false, CW>), grid, dim3(CW), 0, s, F);       \
-    } while (0)
-#define LF_CONES(ST)                                                                                         \
-    do {                                                                                                     \
-        if (r->fb_cw == 64)                                                                                  \
-            LF_CONES_CW(ST, 64);                                                                             \
-        else                                                                                                 \
-            LF_CONES_CW(ST, kBlock);                                                                         \
-    } while (0)
-                // The chain / supply form (lf_fused.h: k_fused_cones_split) where it applies and where the launch is
-                // chain-bound: up to ~1100 cones in flight (24 sub-steps x 2900 cells per level) it is 1.1 - 1.7 x faster,
-                // beyond that the launch is bound by throughput (three wavefronts and 31 KB of LDS per cone) and the
-                // one-wavefront kernel wins (deep 2000^2, ~860 cones: 7.7 vs 8.7 ms per model step,
-                // 3000^2, ~1220: 15.9 vs 14.5).  LF_FUSED_SPLIT=0 / 1: never / always (A/B switch).
-                static const int64_t split_max = [] {
-                    const char *e = std::getenv("LF_FUSED_SPLIT_MAX");
-                    return e ? std::atoll(e) : (long long)1100;
-                }();
-                // (with structures in the loop the supply wavefronts also carry the sideflow assembly and, on reaches with
-                // transmission loss, two OCML pow calls per cell: the crossover is lower -- 3000^2 with 256 sites: 5.5 vs 8.2 ms
-                // at 1000^2, 16.1 vs 15.2 at 2000^2)
-                static const int64_t split_max_struct = [] {
-                    const char *e = std::getenv("LF_FUSED_SPLIT_MAX_STRUCT");
-                    return e ? std::atoll(e) : (long long)600;
-                }();
-                const char *es = std::getenv("LF_FUSED_SPLIT");
-                // (with structures in the loop: on a graph with their links; without them: on a graph without links)
-                const bool split_form = all35 && !F.inert && (in ? F.linked != nullptr : F.linked == nullptr) && r->fb_cw == 64 &&
-                                        n < ((int64_t)1 << 29) && (es ? es[0] != '0' : acc <= (in ? split_max_struct : split_max));
-                if (split_form && in && a->split)
-                    hipLaunchKernelGGL((k_fused_cones_split<true, true>), grid, dim3(64 * (1 + kFusedKC)), 0, s, F);
-                else if (split_form && in)
-                    hipLaunchKernelGGL((k_fused_cones_split<false, true>), grid, dim3(64 * (1 + kFusedKC)), 0, s, F);
-                else if (split_form && a->split)
-                    hipLaunchKernelGGL((k_fused_cones_split<true>), grid, dim3(64 * (1 + kFusedKC)), 0, s, F);
-                else if (split_form)
-                    hipLaunchKernelGGL((k_fused_cones_split<false>), grid, dim3(64 * (1 + kFusedKC)), 0, s, F);
-                else if (in)
-                    LF_CONES(true);
-                else
-                    LF_CONES(false);
-#undef LF_CONES_CW
-#undef LF_CONES
-                ++launches;
-            }
-            int64_t acc1 = 0, widest = 0;
-            for (int q = 0; q < nsteps; ++q) {
-                F.blk_start[q] = (int)acc1;
-                F.lvl[q] = -1;
-                const int b = t - q;
-                if (b >= 0 && b < NB && !multi(b)) {
-                    const int k = r->fb_level[b];
-                    const int64_t w = r->h_level_start[k + 1] - r->h_level_start[k];
-                    F.lvl[q] = k;
-                    acc1 += blocks_for(w);
-                    widest = std::max(widest, w);
-                }
-            }
-            F.blk_start[nsteps] = (int)acc1;
-            if (acc1 > 0) {
-                F.use_lvl = 1;
-                F.packed = 0;
-                dim3 grid(blocks_for(widest), nsteps);
-                if (!grid2d && 2 * acc1 <= (int64_t)blocks_for(widest) * nsteps && acc1 < ((int64_t)1 << 31)) {
-                    F.packed = 1; // as below: packed where it halves the grid
-                    grid = dim3((unsigned)acc1, 1);
-                }
-                if (in && a->split)
-                    hipLaunchKernelGGL((k_fused_substeps<true, true>), grid, dim3(kBlock), 0, s, F);
-                else if (in)
-                    hipLaunchKernelGGL((k_fused_substeps<false, true>), grid, dim3(kBlock), 0, s, F);
-                else if (a->split)
-                    hipLaunchKernelGGL((k_fused_substeps<true, false>), grid, dim3(kBlock), 0, s, F);
-                else
-                    hipLaunchKernelGGL((k_fused_substeps<false, false>), grid, dim3(kBlock), 0, s, F);
-                ++launches;
-            }
-        }
-        LF_HIP(hipGetLastError());
-        r->last_stats[0] = launches;
-        r->last_stats[1] = launches;
-        r->last_stats[2] = 0;
-        r->last_stats[3] = r->NL;
-        return LF_OK;
-    }
-    for (int t = 0; t < NL + nsteps - 1; ++t) {
-        // widest level inside the window [t - nsteps + 1, t]
-        const int k_lo = std::max(0, t - nsteps + 1), k_hi = std::min(NL - 1, t);
-        int64_t widest = 0;
-        for (int k = k_lo; k <= k_hi; ++k) widest = std::max(widest, r->h_level_start[k + 1] - r->h_level_start[k]);
-        F.t = t;
-        if (nsites > 0) { // any site with a level in [k_lo, k_hi]?
-            auto it = std::lower_bound(lv_sorted.begin(), lv_sorted.end(), k_lo);
-            if (it != lv_sorted.end() && *it <= k_hi) {
-                hipLaunchKernelGGL(k_sites_wave, dim3(blocks_for(nsites)), dim3(kBlock), 0, s, F);
-                ++launches;
-            }
-        }
-        dim3 grid(blocks_for(widest), nsteps);
-        const dim3 block(kBlock);
-        // packed 1-D grid only where it saves at least half of the blocks: finding its sub-step costs a block ~1.7 us
-        // (24 scalar kernarg loads), which shows on latency-bound launches (deep 5000^2: 65.2 vs 56.7 ms per model
-        // step, same-call A/B) but is nothing against 360 000 empty blocks (2000^2 hot path: 14.5 vs 16.1 ms)
-        F.packed = 0;
-        if (nsteps <= kMaxPackedSteps && !grid2d) {
-            int64_t acc = 0;
-            for (int q = 0; q < nsteps; ++q) {
-                F.blk_start[q] = (int)acc;
-                const int k = t - q;
-                if (k >= 0 && k < NL) acc += blocks_for(r->h_level_start[k + 1] - r->h_level_start[k]);
-            }
-            F.blk_start[nsteps] = (int)acc;
-            if (2 * acc <= (int64_t)blocks_for(widest) * nsteps && acc < ((int64_t)1 << 31)) {
-                F.packed = 1;
-                grid = dim3((unsigned)std::max<int64_t>(acc, 1), 1);
-            }
-        }
-        if (in && a->split)
-            hipLaunchKernelGGL((k_fused_substeps<true, true>), grid, block, 0, s, F);
-        else if (in)
-            hipLaunchKernelGGL((k_fused_substeps<false, true>), grid, block, 0, s, F);
-        else if (a->split)
-            hipLaunchKernelGGL((k_fused_substeps<true, false>), grid, block, 0, s, F);
-        else
-            hipLaunchKernelGGL((k_fused_substeps<false, false>), grid, block, 0, s, F);
+    if (nsteps > 1 && fused_recompute()) {
+        LF_TRY(fused_check_derived(*r, *a, s));
+        F.recompute = r->derived_ok.p;
         ++launches;
     }
-    LF_HIP(hipGetLastError());
+    const bool all35 = r->fused && a->Beta == 0.6; // otherwise: run-time flags and inlined OCML pow, as fused_cell
+    auto cones = [&](int64_t ncones) {
+        const dim3 grid((unsigned)ncones);
+        // The chain / supply form (lf_fused.h: k_fused_cones_split) where it applies and where the launch is chain-bound: up
+        // to ~1100 cones in flight (24 sub-steps x 2900 cells per level) it is 1.1 - 1.7 x faster, beyond that the launch is
+        // bound by throughput (three wavefronts and 31 KB of LDS per cone) and the one-wavefront kernel wins (DESIGN.md
+        // section 4.3b; deep 2000^2, ~860 cones: 7.7 vs 8.7 ms per model step, 3000^2, ~1220: 15.9 vs 14.5).
+        // LF_FUSED_SPLIT=0 / 1: never / always (A/B switch).
+        static const int64_t split_max = [] {
+            const char *e = std::getenv("LF_FUSED_SPLIT_MAX");
+            return e ? std::atoll(e) : (long long)1100;
+        }();
+        // (with structures in the loop the supply wavefronts also carry the sideflow assembly and, on reaches with
+        // transmission loss, two OCML pow calls per cell: the crossover is lower -- 3000^2 with 256 sites: 5.5 vs 8.2 ms
+        // at 1000^2, 16.1 vs 15.2 at 2000^2)
+        static const int64_t split_max_struct = [] {
+            const char *e = std::getenv("LF_FUSED_SPLIT_MAX_STRUCT");
+            return e ? std::atoll(e) : (long long)600;
+        }();
+        const char *es = std::getenv("LF_FUSED_SPLIT");
+        // (with structures in the loop: on a graph with their links; without them: on a graph without links)
+        const bool split_form = all35 && !F.inert && (in ? F.linked != nullptr : F.linked == nullptr) && r->fb_cw == 64 &&
+                                n < ((int64_t)1 << 29) && (es ? es[0] != '0' : ncones <= (in ? split_max_struct : split_max));
+        if (split_form)
+            fused_pick(a->split, in, [&](auto sp, auto st) {
+                hipLaunchKernelGGL((k_fused_cones_split<sp, st>), grid, dim3(64 * (1 + kFusedKC)), 0, s, F);
+            });
+        else
+            fused_pick(a->split, all35, [&](auto sp, auto a35) {
+                fused_pick(in, r->fb_cw == 64, [&](auto st, auto cw64) {
+                    constexpr int CW = decltype(cw64)::value ? 64 : kBlock;
+                    hipLaunchKernelGGL((k_fused_cones<sp, a35, st, false, CW>), grid, dim3(CW), 0, s, F);
+                });
+            });
+    };
+    auto levels = [&](dim3 grid) {
+        fused_pick(a->split, in, [&](auto sp, auto st) {
+            hipLaunchKernelGGL((k_fused_substeps<sp, st>), grid, dim3(kBlock), 0, s, F);
+        });
+    };
+    // lakes and reservoirs of the blocks / levels [lo, hi]: sub-step t - block / level, before the cells of that block / level
+    std::vector<int> site_blocks; // sorted blocks of the lakes and reservoirs
+    if (r->fb_lmax > 1)
+        for (int lv : lv_sorted) site_blocks.push_back(r->fb_lvl2blk[lv]);
+    auto sites = [&](bool blocks, int lo, int hi) {
+        const std::vector<int> &units = blocks ? site_blocks : lv_sorted;
+        auto it = std::lower_bound(units.begin(), units.end(), lo);
+        if (it == units.end() || *it > hi) return;
+        if (blocks)
+            hipLaunchKernelGGL(k_sites_blocks, dim3(blocks_for(nsites)), dim3(kBlock), 0, s, F);
+        else
+            hipLaunchKernelGGL(k_sites_wave, dim3(blocks_for(nsites)), dim3(kBlock), 0, s, F);
+        ++launches;
+    };
+    const int NB = r->fb_lmax > 1 ? (int)r->fb_level.size() - 1 : -1;
+    LF_TRY(fused_wavefront<false>(*r, F, 0, (int)r->NL, 0, NB, !in && !F.linked, s, launches, cones, levels, sites));
     r->last_stats[0] = launches;
     r->last_stats[1] = launches;
     r->last_stats[2] = 0;
