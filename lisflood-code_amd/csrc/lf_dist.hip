@@ -769,11 +769,6 @@ int lf_comm_close(lf_comm *c)
 // device: distributed router
 // ------------------------------------------------------------------------------------------------
 namespace {
-struct dsegment {
-    int k0, k1;
-    bool wide;
-};
-
 __global__ void __launch_bounds__(kBlock) k_pack2(int n0, int n1, const int *__restrict__ pos0, const int *__restrict__ pos1,
                                                   const double *__restrict__ q, double *__restrict__ buf0,
                                                   double *__restrict__ buf1)
@@ -812,7 +807,7 @@ struct lf_dist_router {
     lf_dbuf<lf_rec24> rec24_1, rec24_2; // the level kernel's static values as one record per cell and section (dist_level_statics)
     bool statics_refused = false;
     std::vector<int64_t> h_level_start;
-    std::vector<std::vector<dsegment>> schedule; // per stage (2 * phase + part, see lf_dist_graph::crit)
+    std::vector<std::vector<level_segment>> schedule; // per stage (2 * phase + part, see lf_dist_graph::crit)
     // halo exchange beside the bulk part of a phase: second stream + events (lf_dist_router_route)
     hipStream_t comm_stream = nullptr;
     hipEvent_t ev_part0 = nullptr, ev_halo = nullptr;
@@ -847,9 +842,9 @@ namespace {
 // LF_LEVEL_STATICS=0, a graph of 2^28 cells or more, or no memory for them.
 const lf_rec24 *dist_level_statics(lf_dist_router *r, const sweep_args &A)
 {
-    if (!r->fused || !r->dx_per_pixel || r->statics_refused || r->N <= 0 || r->N >= ((int64_t)1 << 28)) return nullptr;
-    const char *e = std::getenv("LF_LEVEL_STATICS");
-    if (e && e[0] == '0') return nullptr;
+    if (!r->fused || !r->dx_per_pixel || r->statics_refused || r->N <= 0 || r->N >= ((int64_t)1 << 28) ||
+        !level_statics_enabled())
+        return nullptr;
     lf_dbuf<lf_rec24> &buf = (A.a == r->a1.p) ? r->rec24_1 : r->rec24_2;
     if (!buf.p) {
         if (r->ups_idx.n >= ((size_t)1 << 28) || buf.alloc((size_t)r->N) != LF_OK) {
@@ -868,29 +863,12 @@ const lf_rec24 *dist_level_statics(lf_dist_router *r, const sweep_args &A)
 int dist_compute_phase(lf_dist_router *r, double *q, const double *lat, int section, int phase, int part = -1,
                        const double *q_in = nullptr)
 {
-    if (section != LF_SECTION_MAIN && section != LF_SECTION_FLOODPLAINS)
-        return lf_set_error(LF_E_SECTION, "The section parameter must be either 'main_channel' or 'floodplain'!");
-    if (section == LF_SECTION_FLOODPLAINS && !r->has_floodplains)
-        return lf_set_error(LF_E_SECTION, "floodplains routing requested but alpha_floodplains was not given");
+    LF_TRY(check_section(*r, section));
     if (phase < 0 || phase >= r->nphases) return lf_set_error(LF_E_INVALID, "phase %d out of range", phase);
     hipStream_t s = r->ctx->stream;
-    sweep_args A;
-    A.ups_ptr = r->ups_ptr.p;
+    sweep_args A = sweep_args_of(*r, section, q, nullptr, lat);
     A.ups_idx = r->ups_idx.p;
     A.ups_base = r->ups_base.p;
-    A.perm = nullptr;
-    A.a = section == LF_SECTION_MAIN ? r->a1.p : r->a2.p;
-    A.constant = r->constant.p;
-    A.lat = lat;
-    A.dx = r->dx_per_pixel ? r->dx.p : nullptr;
-    A.dx_scalar = r->dx_scalar;
-    A.beta = r->beta;
-    A.inv_beta = r->inv_beta;
-    A.b_minus_1 = r->b_minus_1;
-    A.kmax = r->kmax;
-    A.qord = q;
-    A.q_pix = nullptr;
-    A.adx = nullptr;
     A.rec24 = dist_level_statics(r, A);
     A.qold_src = q_in; // pipelined calls: old discharge from the other state vector (beta = 3/5 path only)
     if (q_in && !r->fused) return lf_set_error(LF_E_INVALID, "separate input discharge needs the beta = 3/5 path");
@@ -900,61 +878,39 @@ int dist_compute_phase(lf_dist_router *r, double *q, const double *lat, int sect
                            r->dx_scalar, r->beta, r->constant.p);
         r->last_launches++;
     }
-    const char *cones_env = std::getenv("LF_ROUTE_CONES"); // (read at every call, as the single-domain router does)
-    const bool cones = !r->rb_stage_block.empty() && !(cones_env && cones_env[0] == '0');
+    // blocks of units cone by cone (k_sweep_cones_dist), single wide units and runs of narrow ones as in a call of the
+    // single domain
+    auto cones = [&](dim3 grid, const cone_plan_args &C, int64_t) {
+        if (r->fused)
+            hipLaunchKernelGGL((k_sweep_cones_dist<true>), grid, dim3(64), 0, s, C, A);
+        else
+            hipLaunchKernelGGL((k_sweep_cones_dist<false>), grid, dim3(64), 0, s, C, A);
+        return LF_OK;
+    };
+    auto level = [&](int first, int cells) {
+        const dim3 grid(level_blocks_for(cells)), block(kLevelBlock);
+        if (r->fused && A.rec24)
+            hipLaunchKernelGGL((k_level<true, true, true, 3>), grid, block, 0, s, first, cells, A);
+        else if (r->fused)
+            hipLaunchKernelGGL((k_level<true, true, true>), grid, block, 0, s, first, cells, A);
+        else
+            hipLaunchKernelGGL((k_level<false, true, true>), grid, block, 0, s, first, cells, A);
+        return LF_OK;
+    };
+    auto narrow = [&](int k0, int k1) {
+        if (r->fused)
+            hipLaunchKernelGGL((k_levels_narrow<true, true, true>), dim3(1), dim3(kNarrowBlock), 0, s, k0, k1, r->level_start.p, A);
+        else
+            hipLaunchKernelGGL((k_levels_narrow<false, true, true>), dim3(1), dim3(kNarrowBlock), 0, s, k0, k1, r->level_start.p, A);
+        return LF_OK;
+    };
+    const bool blocks = !r->rb_stage_block.empty();
+    launch_counts c;
     for (int st = 2 * phase + (part == 1 ? 1 : 0); st <= 2 * phase + (part == 0 ? 0 : 1); ++st) {
-        if (cones) { // blocks of units cone by cone (k_sweep_cones<DIST>), single wide units by the level kernel
-            for (int b = r->rb_stage_block[st]; b < r->rb_stage_block[st + 1]; ++b) {
-                const int k0 = r->rb_level[b], nl = r->rb_level[b + 1] - k0;
-                if (nl > 1) {
-                    cone_plan_args C;
-                    C.cone = r->rb_cone.p + r->rb_off[b];
-                    C.nl = nl;
-                    C.n_cells = 0; // (unused by k_sweep_cones_dist)
-                    const dim3 grid((unsigned)(r->rb_row[b + 1] - r->rb_row[b] - 1)), block(64);
-                    if (r->fused)
-                        hipLaunchKernelGGL((k_sweep_cones_dist<true>), grid, block, 0, s, C, A);
-                    else
-                        hipLaunchKernelGGL((k_sweep_cones_dist<false>), grid, block, 0, s, C, A);
-                } else {
-                    const int first = (int)r->h_level_start[k0];
-                    const int count = (int)(r->h_level_start[k0 + 1] - r->h_level_start[k0]);
-                    if (count <= 0) continue;
-                    const dim3 grid(level_blocks_for(count)), block(kLevelBlock);
-                    if (r->fused && A.rec24)
-                        hipLaunchKernelGGL((k_level<true, true, true, 3>), grid, block, 0, s, first, count, A);
-                    else if (r->fused)
-                        hipLaunchKernelGGL((k_level<true, true, true>), grid, block, 0, s, first, count, A);
-                    else
-                        hipLaunchKernelGGL((k_level<false, true, true>), grid, block, 0, s, first, count, A);
-                }
-                r->last_launches++;
-            }
-            continue;
-        }
-    for (const dsegment &g : r->schedule[st]) {
-        if (g.wide) {
-            const int first = (int)r->h_level_start[g.k0];
-            const int count = (int)(r->h_level_start[g.k1] - r->h_level_start[g.k0]);
-            const dim3 grid(level_blocks_for(count)), block(kLevelBlock);
-            if (r->fused && A.rec24)
-                hipLaunchKernelGGL((k_level<true, true, true, 3>), grid, block, 0, s, first, count, A);
-            else if (r->fused)
-                hipLaunchKernelGGL((k_level<true, true, true>), grid, block, 0, s, first, count, A);
-            else
-                hipLaunchKernelGGL((k_level<false, true, true>), grid, block, 0, s, first, count, A);
-        } else {
-            const dim3 grid(1), block(kNarrowBlock);
-            if (r->fused)
-                hipLaunchKernelGGL((k_levels_narrow<true, true, true>), grid, block, 0, s, g.k0, g.k1, r->level_start.p,
-                                   A);
-            else
-                hipLaunchKernelGGL((k_levels_narrow<false, true, true>), grid, block, 0, s, g.k0, g.k1,
-                                   r->level_start.p, A);
-        }
-        r->last_launches++;
+        const int b0 = blocks ? r->rb_stage_block[st] : 0, nb = blocks ? r->rb_stage_block[st + 1] - b0 : 0;
+        LF_TRY(route_schedule(*r, b0, nb, r->schedule[st], blocks, c, cones, level, narrow));
     }
-    }
+    r->last_launches += c.launches;
     LF_HIP(hipGetLastError());
     return LF_OK;
 }
@@ -1000,40 +956,13 @@ int lf_dist_router_create(const lf_dist_graph *g, const double *alpha, double be
     r->dt = dt;
     r->dx_per_pixel = dx != nullptr;
     r->has_floodplains = alpha_floodplains != nullptr;
-    const char *force_general = std::getenv("LF_GENERAL_POW");
-    r->fused = (beta == 0.6) && !(force_general && force_general[0] == '1');
+    r->fused = router_fused(beta);
     const int64_t n = g->N;
-    int rc = LF_OK;
-    {
-        std::vector<double> h(n);
-        auto fill = [&](const double *al) {
-            for (int64_t p = 0; p < n; ++p) {
-                const int32_t pix = g->perm[p];
-                h[p] = al[pix] * (dx ? dx[pix] : dx_scalar) / dt; // kinematic_wave_parallel.py:127
-            }
-        };
-        fill(alpha);
-        rc = r->a1.upload(h.data(), n);
-        if (rc == LF_OK && alpha_floodplains) {
-            fill(alpha_floodplains);
-            rc = r->a2.upload(h.data(), n);
-        }
-        if (rc == LF_OK && dx) {
-            for (int64_t p = 0; p < n; ++p) h[p] = dx[g->perm[p]];
-            rc = r->dx.upload(h.data(), n);
-        }
-    }
+    int rc = upload_sweep_statics(*r, g->perm, alpha, alpha_floodplains, dx, nullptr);
     if (rc == LF_OK) rc = r->perm.upload(g->perm.data(), n);
     if (rc == LF_OK) rc = r->ups_ptr.upload(g->ups_ptr.data(), n + 1);
     if (rc == LF_OK) rc = r->ups_idx.upload(g->ups_idx.data(), g->ups_idx.size());
-    if (rc == LF_OK) {
-        const char *e = std::getenv("LF_DIST_ALL_INDEXED"); // A/B switch: every cell through the index list
-        if (e && e[0] == '1') {
-            std::vector<int32_t> none(g->ups_base.size(), -1);
-            rc = r->ups_base.upload(none.data(), none.size());
-        } else
-            rc = r->ups_base.upload(g->ups_base.data(), g->ups_base.size());
-    }
+    if (rc == LF_OK) rc = r->ups_base.upload(g->ups_base.data(), g->ups_base.size());
     if (rc == LF_OK) {
         std::vector<long long> ls(g->level_start.begin(), g->level_start.end());
         rc = r->level_start.upload(ls.data(), ls.size());
@@ -1084,22 +1013,7 @@ int lf_dist_router_create(const lf_dist_graph *g, const double *alpha, double be
     }
     r->phase_level = g->phase_level;
     r->h_level_start = g->level_start;
-    r->schedule.resize(2 * (size_t)g->nphases);
-    for (int j = 0; j < 2 * g->nphases; ++j) {
-        const int64_t k_end = g->stage_level[j + 1];
-        for (int64_t k = g->stage_level[j]; k < k_end;) {
-            const int64_t size = g->level_start[k + 1] - g->level_start[k];
-            if (size > kNarrowMax) {
-                r->schedule[j].push_back({(int)k, (int)k + 1, true});
-                ++k;
-            } else {
-                int64_t e = k + 1;
-                while (e < k_end && g->level_start[e + 1] - g->level_start[e] <= kNarrowMax) ++e;
-                r->schedule[j].push_back({(int)k, (int)e, false});
-                k = e;
-            }
-        }
-    }
+    for (int j = 0; j < 2 * g->nphases; ++j) r->schedule.push_back(level_segments(g->level_start, g->stage_level[j], g->stage_level[j + 1]));
     *out = r;
     return LF_OK;
 }
@@ -1452,7 +1366,7 @@ int dist_fused_phase(lf_dist_router *r, const lf_substep_args *a, int nsteps, in
     hipStream_t s = r->ctx->stream;
     // the units of the phase and their level blocks through the DIST kernels (fused_wavefront, lf_fused.h); no sites
     auto cones = [&](int64_t ncones) {
-        fused_pick(a->split, r->fused && a->Beta == 0.6, [&](auto sp, auto a35) {
+        pick_flags(a->split, r->fused && a->Beta == 0.6, [&](auto sp, auto a35) {
             hipLaunchKernelGGL((k_fused_cones<sp, a35, false, true>), dim3((unsigned)ncones), dim3(kBlock), 0, s, F);
         });
     };

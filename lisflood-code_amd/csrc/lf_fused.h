@@ -1723,20 +1723,6 @@ __global__ void __launch_bounds__(64 * (1 + KC)) k_fused_cones_split(fused_args 
 // here have the same names and meanings.
 // ================================================================================================
 
-// The instantiation of a kernel for two run-time flags: fn(std::bool_constant<a>, std::bool_constant<b>)
-template <class Fn>
-void fused_pick(bool a, bool b, Fn &&fn)
-{
-    if (a && b)
-        fn(std::true_type(), std::true_type());
-    else if (a)
-        fn(std::true_type(), std::false_type());
-    else if (b)
-        fn(std::false_type(), std::true_type());
-    else
-        fn(std::false_type(), std::false_type());
-}
-
 // fused_args of nsteps sub-steps (msteps per model step) from the router's statics; the wave fields are the schedule's,
 // the rest (structures, slabs, recompute flag, ...) stays zero for the caller
 template <class R>
@@ -1823,7 +1809,7 @@ int fused_wavefront(R &r, fused_args &F, int level0, int nlevels, int b0, int nb
         for (int k = level0; k < level0 + nlevels; ++k) {
             const int64_t w = width(k);
             if (w <= 0) continue;
-            fused_pick(split, all35, [&](auto sp, auto a35) {
+            pick_flags(split, all35, [&](auto sp, auto a35) {
                 hipLaunchKernelGGL((k_fused_level_steps<sp, a35, DIST>), dim3(blocks_for(w)), dim3(kBlock), 0, s, F, k);
             });
             ++launches;

@@ -185,11 +185,6 @@ __global__ void __launch_bounds__(kBlock) k_count_nonfinite(long long n, const d
     if ((threadIdx.x & 63) == 0 && local) atomicAdd(count, local);
 }
 
-struct segment {
-    int k0, k1; // levels [k0, k1); wide segments have k1 == k0 + 1
-    bool wide;
-};
-
 } // namespace
 
 struct lf_router {
@@ -221,7 +216,7 @@ struct lf_router {
     const void *site_key[4] = {nullptr, nullptr, nullptr, nullptr}; // the site lists those levels were checked for
     int64_t site_cnt[2] = {-1, -1};
     std::vector<int64_t> h_level_start;
-    std::vector<segment> schedule;
+    std::vector<level_segment> schedule; // launches of a call without level blocks (level_segments)
     // level blocks of the fused sub-step wavefront (build_level_blocks): block b = levels [fb_level[b], fb_level[b+1]),
     // cut into cones = the upstream ranges of chunks of its last level, no range wider than a workgroup; block b has
     // fb_row[b+1] - fb_row[b] - 1 cones and one more row (the end of every level) in fb_cone, from entry fb_off[b] on,
@@ -302,38 +297,11 @@ struct lf_router {
 
 namespace {
 
-sweep_args make_sweep_args(lf_router *r, double *q_dev, const double *lat_dev, int section, bool ordered)
-{
-    sweep_args A;
-    A.ups_ptr = r->ups_ptr.p;
-    A.ups_idx = nullptr;
-    A.ups_base = nullptr;
-    A.perm = r->perm.p;
-    A.a = (section == LF_SECTION_MAIN) ? r->a1.p : r->a2.p;
-    A.constant = r->constant.p;
-    A.lat = lat_dev;
-    A.dx = r->dx_per_pixel ? r->dx.p : nullptr;
-    A.dx_scalar = r->dx_scalar;
-    A.beta = r->beta;
-    A.inv_beta = r->inv_beta;
-    A.b_minus_1 = r->b_minus_1;
-    A.kmax = r->kmax;
-    A.qord = ordered ? q_dev : r->qord.p;
-    A.q_pix = ordered ? nullptr : q_dev;
-    A.qold_src = nullptr;
-    A.adx = nullptr;
-    A.rec24 = nullptr;
-    return A;
-}
-
 // The (a, dx) records of A's section for the wide levels of an ordered beta = 3/5 call, or nullptr: dx is a scalar (the
-// sweep then has one static load anyway), LF_LEVEL_STATICS=0 (A/B switch, read at every call) or no memory for them
-// (16 bytes per cell and section).
+// sweep then has one static load anyway), LF_LEVEL_STATICS=0 or no memory for them (16 bytes per cell and section).
 const double2 *level_statics(lf_router *r, const sweep_args &A)
 {
-    if (!r->fused || !r->dx_per_pixel || r->statics_refused || r->N <= 0) return nullptr;
-    const char *e = std::getenv("LF_LEVEL_STATICS");
-    if (e && e[0] == '0') return nullptr;
+    if (!r->fused || !r->dx_per_pixel || r->statics_refused || r->N <= 0 || !level_statics_enabled()) return nullptr;
     lf_dbuf<double2> &buf = (A.a == r->a1.p) ? r->adx1 : r->adx2;
     if (!buf.p) {
         if (buf.alloc((size_t)r->N) != LF_OK) {
@@ -358,275 +326,113 @@ void launch_level_ordered_fused(lf_router *r, hipStream_t s, int first, int cell
         hipLaunchKernelGGL((k_level<true, true>), grid, block, 0, s, first, cells, A);
 }
 
-// A router call block by block (build_level_blocks): blocks of several levels cone by cone (k_sweep_cones), single wide
-// levels by the level kernel.  `count` routers of ONE graph share the launches.  LF_ROUTE_CONES=0: level by level.
-bool cones_enabled() // (read at every call: bench.py switches it for its A/B legs)
-{
-    const char *e = std::getenv("LF_ROUTE_CONES");
-    return !(e && e[0] == '0');
-}
-
-template <int NR, int CW>
-void launch_sweep_cones_cw(bool fused, bool ordered, dim3 grid, hipStream_t s, const cone_plan_args &C,
-                           const sweep_args_multi &M)
-{
-    if (fused && ordered)
-        hipLaunchKernelGGL((k_sweep_cones<true, true, NR, CW>), grid, dim3(CW), 0, s, C, M);
-    else if (fused)
-        hipLaunchKernelGGL((k_sweep_cones<true, false, NR, CW>), grid, dim3(CW), 0, s, C, M);
-    else if (ordered)
-        hipLaunchKernelGGL((k_sweep_cones<false, true, NR, CW>), grid, dim3(CW), 0, s, C, M);
-    else
-        hipLaunchKernelGGL((k_sweep_cones<false, false, NR, CW>), grid, dim3(CW), 0, s, C, M);
-}
 bool cone_split_enabled() // LF_ROUTE_SPLIT=0: one wavefront per cone does everything (the round-3 kernel; A/B switch)
 {
     const char *e = std::getenv("LF_ROUTE_SPLIT");
     return !(e && e[0] == '0');
 }
-// k_sweep_cones_split comes in two shapes for a single router.  FEW cones per launch (at most about one per CU: the
-// chain-bound networks) -> chunks of 8 levels and four supply wavefronts, 72 KB of LDS per cone; MANY cones (several per
-// CU: their wavefronts share the SIMDs, the launch is throughput-bound) -> chunks of 4 levels and two supply wavefronts,
-// 37 KB.  Several routers on one graph: chunks of 4 levels, two supply wavefronts.  LF_ROUTE_SPLIT_SHAPE=few|many forces
-// one shape (A/B switch); LF_ROUTE_SPLIT_FEW is the threshold in cones per launch.
+// One block of levels cone by cone, for NR routers of one graph.  k_sweep_cones_split comes in two shapes for a single
+// router.  FEW cones per launch (at most kFewCones: about one per CU, the chain-bound networks) -> chunks of 8 levels and
+// four supply wavefronts, 72 KB of LDS per cone; MANY cones (several per CU: their wavefronts share the SIMDs, the launch
+// is throughput-bound) -> chunks of 4 levels and two supply wavefronts, 37 KB.  Several routers on one graph: chunks of 4
+// levels, two supply wavefronts.
+constexpr int kFewCones = 256;
 template <bool FUSED, bool ORDERED, int NR, int KC, int NS>
 void launch_split(dim3 grid, hipStream_t s, const cone_plan_args &C, const sweep_args_multi &M)
 {
     hipLaunchKernelGGL((k_sweep_cones_split<FUSED, ORDERED, NR, KC, NS>), grid, dim3(64 * (1 + NS)), 0, s, C, M);
 }
-template <bool FUSED, bool ORDERED, int NR>
-void launch_split_shape(dim3 grid, hipStream_t s, const cone_plan_args &C, const sweep_args_multi &M)
-{
-    if (NR > 1) {
-        launch_split<FUSED, ORDERED, NR, 4, 2>(grid, s, C, M);
-        return;
-    }
-    static const int few_limit = [] {
-        const char *e = std::getenv("LF_ROUTE_SPLIT_FEW");
-        return e ? std::atoi(e) : 256;
-    }();
-    const char *shape = std::getenv("LF_ROUTE_SPLIT_SHAPE"); // (read at every call: A/B legs switch it)
-    const bool few = shape ? shape[0] == 'f' : (int)grid.x <= few_limit;
-    if (few)
-        launch_split<FUSED, ORDERED, 1, LF_CONE_KC, LF_CONE_NS>(grid, s, C, M);
-    else
-        launch_split<FUSED, ORDERED, 1, 4, 2>(grid, s, C, M);
-}
 template <int NR>
 void launch_sweep_cones(int cw, bool fused, bool ordered, dim3 grid, hipStream_t s, const cone_plan_args &C,
                         const sweep_args_multi &M)
 {
-    if (cw == 64 && cone_split_enabled() && C.n_cells < (1 << 29)) { // (byte offsets of the buffer stores: 32 bits)
-        if (fused && ordered)
-            launch_split_shape<true, true, NR>(grid, s, C, M);
-        else if (fused)
-            launch_split_shape<true, false, NR>(grid, s, C, M);
-        else if (ordered)
-            launch_split_shape<false, true, NR>(grid, s, C, M);
+    const bool split = cw == 64 && cone_split_enabled() && C.n_cells < (1 << 29); // (byte offsets of the buffer stores: 32 bits)
+    pick_flags(fused, ordered, [&](auto f, auto o) {
+        if (split && NR == 1 && (int)grid.x <= kFewCones)
+            launch_split<f, o, 1, LF_CONE_KC, LF_CONE_NS>(grid, s, C, M);
+        else if (split)
+            launch_split<f, o, NR, 4, 2>(grid, s, C, M);
+        else if (cw == 64)
+            hipLaunchKernelGGL((k_sweep_cones<f, o, NR, 64>), grid, dim3(64), 0, s, C, M);
         else
-            launch_split_shape<false, false, NR>(grid, s, C, M);
-    } else if (cw == 64)
-        launch_sweep_cones_cw<NR, 64>(fused, ordered, grid, s, C, M);
-    else
-        launch_sweep_cones_cw<NR, kBlock>(fused, ordered, grid, s, C, M);
+            hipLaunchKernelGGL((k_sweep_cones<f, o, NR, kBlock>), grid, dim3(kBlock), 0, s, C, M);
+    });
 }
 
-int enqueue_blocks(int count, lf_router **rs, const sweep_args_multi &M, bool ordered, int64_t *launches, int64_t *wide,
-                   int64_t *narrow)
-{
-    lf_router *r = rs[0];
-    hipStream_t s = r->ctx->stream;
-    const int NB = (int)r->rb_level.size() - 1;
-    for (int b = 0; b < NB; ++b) {
-        const int k0 = r->rb_level[b], nl = r->rb_level[b + 1] - k0;
-        if (nl > 1) {
-            cone_plan_args C;
-            C.cone = r->rb_cone.p + r->rb_off[b];
-            C.nl = nl;
-            C.n_cells = (int)r->N;
-            const dim3 grid((unsigned)(r->rb_row[b + 1] - r->rb_row[b] - 1));
-            LF_TRY(r->prof_begin(2, r->h_level_start[k0 + nl] - r->h_level_start[k0]));
-            if (count == 1)
-                launch_sweep_cones<1>(r->rb_cw, r->fused, ordered, grid, s, C, M);
-            else if (count == 2)
-                launch_sweep_cones<2>(r->rb_cw, r->fused, ordered, grid, s, C, M);
-            else if (count == 3)
-                launch_sweep_cones<3>(r->rb_cw, r->fused, ordered, grid, s, C, M);
-            else
-                launch_sweep_cones<4>(r->rb_cw, r->fused, ordered, grid, s, C, M);
-            LF_TRY(r->prof_end());
-            ++*narrow;
-        } else {
-            const int first = (int)r->h_level_start[k0];
-            const int cells = (int)(r->h_level_start[k0 + 1] - r->h_level_start[k0]);
-            const dim3 grid(blocks_for(cells), count), block(kBlock);
-            const dim3 grid1(level_blocks_for(cells)), block1(kLevelBlock);
-            LF_TRY(r->prof_begin(1, cells));
-            if (count == 1) {
-                if (r->fused && ordered)
-                    launch_level_ordered_fused(r, s, first, cells, M.r[0]);
-                else if (r->fused)
-                    hipLaunchKernelGGL((k_level<true, false>), grid1, block1, 0, s, first, cells, M.r[0]);
-                else if (ordered)
-                    hipLaunchKernelGGL((k_level<false, true>), grid1, block1, 0, s, first, cells, M.r[0]);
-                else
-                    hipLaunchKernelGGL((k_level<false, false>), grid1, block1, 0, s, first, cells, M.r[0]);
-            } else if (r->fused && ordered)
-                hipLaunchKernelGGL((k_level_multi<true, true>), grid, block, 0, s, first, cells, M);
-            else if (r->fused)
-                hipLaunchKernelGGL((k_level_multi<true, false>), grid, block, 0, s, first, cells, M);
-            else if (ordered)
-                hipLaunchKernelGGL((k_level_multi<false, true>), grid, block, 0, s, first, cells, M);
-            else
-                hipLaunchKernelGGL((k_level_multi<false, false>), grid, block, 0, s, first, cells, M);
-            LF_TRY(r->prof_end());
-            ++*wide;
-        }
-        ++*launches;
-    }
-    return LF_OK;
-}
-
-// `count` routers built on the same graph (same level schedule), swept level by level with ONE launch per level
-int enqueue_route_multi(int count, lf_router **rs, double **q_dev, const double **lat_dev, int section, bool ordered)
+// `count` (1 to 4) routers built on the same graph (same level schedule) swept together: one launch per level block, wide
+// level or run of narrow levels for all of them.  One router: k_level / k_levels_narrow / k_sweep_cones<.., 1, ..>;
+// several: k_level_multi / k_levels_narrow_multi (blockIdx.y / blockIdx.x picks the router) and, on one graph object with
+// one plan, k_sweep_cones<.., count, ..>.
+int enqueue_route(int count, lf_router **rs, double **q_dev, const double **lat_dev, int section, bool ordered)
 {
     lf_router *r = rs[0];
     hipStream_t s = r->ctx->stream;
     const int n = (int)r->N;
     sweep_args_multi M;
-    for (int i = 0; i < kMaxMulti; ++i) M.r[i] = make_sweep_args(rs[i < count ? i : 0], q_dev[i < count ? i : 0], lat_dev[i < count ? i : 0], section, ordered);
-    int64_t launches = 0, wide = 0, narrow = 0;
+    for (int i = 0; i < kMaxMulti; ++i) {
+        lf_router *ri = rs[i < count ? i : 0];
+        double *q = q_dev[i < count ? i : 0];
+        M.r[i] = sweep_args_of(*ri, section, ordered ? q : ri->qord.p, ordered ? nullptr : q, lat_dev[i < count ? i : 0]);
+    }
+    launch_counts c;
     if (n > 0 && !r->fused)
         for (int i = 0; i < count; ++i) {
+            LF_TRY(r->prof_begin(0, n));
             hipLaunchKernelGGL(k_prep, dim3(blocks_for(n)), dim3(kBlock), 0, s, n, ordered ? nullptr : rs[i]->perm.p, q_dev[i],
                                lat_dev[i], M.r[i].a, M.r[i].dx, rs[i]->dx_scalar, rs[i]->beta, rs[i]->constant.p);
-            ++launches;
+            LF_TRY(r->prof_end());
+            ++c.launches;
         }
-    bool same_graph = r->rb_lmax > 1 && cones_enabled();
-    for (int i = 1; i < count; ++i) same_graph = same_graph && rs[i]->graph_serial == r->graph_serial && r->graph_serial != 0 && rs[i]->rb_lmax == r->rb_lmax && rs[i]->rb_cw == r->rb_cw;
-    if (same_graph) {
-        LF_TRY(enqueue_blocks(count, rs, M, ordered, &launches, &wide, &narrow));
-        for (int i = 0; i < count; ++i) {
-            rs[i]->last_stats[0] = launches;
-            rs[i]->last_stats[1] = wide;
-            rs[i]->last_stats[2] = narrow;
-            rs[i]->last_stats[3] = rs[i]->NL;
-        }
-        return LF_OK;
-    }
-    for (const segment &g : r->schedule) {
-        if (g.wide) {
-            const int first = (int)r->h_level_start[g.k0];
-            const int cells = (int)(r->h_level_start[g.k1] - r->h_level_start[g.k0]);
-            const dim3 grid(blocks_for(cells), count), block(kBlock);
-            if (r->fused && ordered)
-                hipLaunchKernelGGL((k_level_multi<true, true>), grid, block, 0, s, first, cells, M);
-            else if (r->fused)
-                hipLaunchKernelGGL((k_level_multi<true, false>), grid, block, 0, s, first, cells, M);
-            else if (ordered)
-                hipLaunchKernelGGL((k_level_multi<false, true>), grid, block, 0, s, first, cells, M);
-            else
-                hipLaunchKernelGGL((k_level_multi<false, false>), grid, block, 0, s, first, cells, M);
-            ++wide;
-        } else {
-            const dim3 grid(count), block(kNarrowBlock);
-            if (r->fused && ordered)
-                hipLaunchKernelGGL((k_levels_narrow_multi<true, true>), grid, block, 0, s, g.k0, g.k1, r->level_start.p, M);
-            else if (r->fused)
-                hipLaunchKernelGGL((k_levels_narrow_multi<true, false>), grid, block, 0, s, g.k0, g.k1, r->level_start.p, M);
-            else if (ordered)
-                hipLaunchKernelGGL((k_levels_narrow_multi<false, true>), grid, block, 0, s, g.k0, g.k1, r->level_start.p, M);
-            else
-                hipLaunchKernelGGL((k_levels_narrow_multi<false, false>), grid, block, 0, s, g.k0, g.k1, r->level_start.p, M);
-            ++narrow;
-        }
-        ++launches;
-    }
+    bool blocks = r->rb_lmax > 1;
+    for (int i = 1; i < count; ++i) blocks = blocks && rs[i]->graph_serial == r->graph_serial && r->graph_serial != 0 && rs[i]->rb_lmax == r->rb_lmax && rs[i]->rb_cw == r->rb_cw;
+    LF_TRY(pick_count(count, [&](auto nr) {
+        constexpr int NR = nr;
+        auto cones = [&](dim3 grid, const cone_plan_args &C, int64_t cells) {
+            LF_TRY(r->prof_begin(2, cells));
+            launch_sweep_cones<NR>(r->rb_cw, r->fused, ordered, grid, s, C, M);
+            return r->prof_end();
+        };
+        auto level = [&](int first, int cells) {
+            LF_TRY(r->prof_begin(1, cells));
+            pick_flags(r->fused, ordered, [&](auto f, auto o) {
+                if constexpr (NR > 1)
+                    hipLaunchKernelGGL((k_level_multi<f, o>), dim3(blocks_for(cells), NR), dim3(kBlock), 0, s, first, cells, M);
+                else if constexpr (f && o)
+                    launch_level_ordered_fused(r, s, first, cells, M.r[0]);
+                else
+                    hipLaunchKernelGGL((k_level<f, o>), dim3(level_blocks_for(cells)), dim3(kLevelBlock), 0, s, first, cells, M.r[0]);
+            });
+            return r->prof_end();
+        };
+        auto narrow = [&](int k0, int k1) {
+            LF_TRY(r->prof_begin(2, r->h_level_start[k1] - r->h_level_start[k0]));
+            pick_flags(r->fused, ordered, [&](auto f, auto o) {
+                if constexpr (NR > 1)
+                    hipLaunchKernelGGL((k_levels_narrow_multi<f, o>), dim3(NR), dim3(kNarrowBlock), 0, s, k0, k1, r->level_start.p, M);
+                else
+                    hipLaunchKernelGGL((k_levels_narrow<f, o>), dim3(1), dim3(kNarrowBlock), 0, s, k0, k1, r->level_start.p, M.r[0]);
+            });
+            return r->prof_end();
+        };
+        return route_schedule(*r, 0, (int)r->rb_level.size() - 1, r->schedule, blocks, c, cones, level, narrow);
+    }));
     for (int i = 0; i < count; ++i) {
-        rs[i]->last_stats[0] = launches;
-        rs[i]->last_stats[1] = wide;
-        rs[i]->last_stats[2] = narrow;
+        rs[i]->last_stats[0] = c.launches;
+        rs[i]->last_stats[1] = c.wide;
+        rs[i]->last_stats[2] = c.narrow;
         rs[i]->last_stats[3] = rs[i]->NL;
     }
     return LF_OK;
 }
 
-int enqueue_route(lf_router *r, double *q_dev, const double *lat_dev, int section, bool ordered)
-{
-    hipStream_t s = r->ctx->stream;
-    const int n = (int)r->N;
-    int64_t launches = 0, wide = 0, narrow = 0;
-    sweep_args A = make_sweep_args(r, q_dev, lat_dev, section, ordered);
-    const double *a = A.a;
-    if (n > 0 && !r->fused) {
-        LF_TRY(r->prof_begin(0, n));
-        hipLaunchKernelGGL(k_prep, dim3(blocks_for(n)), dim3(kBlock), 0, s, n, ordered ? nullptr : r->perm.p, q_dev,
-                           lat_dev, a, A.dx, r->dx_scalar, r->beta, r->constant.p);
-        LF_TRY(r->prof_end());
-        ++launches;
-    }
-    if (r->rb_lmax > 1 && cones_enabled()) {
-        sweep_args_multi M;
-        for (int i = 0; i < kMaxMulti; ++i) M.r[i] = A;
-        lf_router *one[1] = {r};
-        LF_TRY(enqueue_blocks(1, one, M, ordered, &launches, &wide, &narrow));
-        r->last_stats[0] = launches;
-        r->last_stats[1] = wide;
-        r->last_stats[2] = narrow;
-        r->last_stats[3] = r->NL;
-        return LF_OK;
-    }
-    for (const segment &g : r->schedule) {
-        if (g.wide) {
-            const int first = (int)r->h_level_start[g.k0];
-            const int count = (int)(r->h_level_start[g.k1] - r->h_level_start[g.k0]);
-            LF_TRY(r->prof_begin(1, count));
-            const dim3 grid(level_blocks_for(count)), block(kLevelBlock);
-            if (r->fused && ordered)
-                launch_level_ordered_fused(r, s, first, count, A);
-            else if (r->fused)
-                hipLaunchKernelGGL((k_level<true, false>), grid, block, 0, s, first, count, A);
-            else if (ordered)
-                hipLaunchKernelGGL((k_level<false, true>), grid, block, 0, s, first, count, A);
-            else
-                hipLaunchKernelGGL((k_level<false, false>), grid, block, 0, s, first, count, A);
-            LF_TRY(r->prof_end());
-            ++wide;
-        } else {
-            LF_TRY(r->prof_begin(2, r->h_level_start[g.k1] - r->h_level_start[g.k0]));
-            const dim3 grid(1), block(kNarrowBlock);
-            if (r->fused && ordered)
-                hipLaunchKernelGGL((k_levels_narrow<true, true>), grid, block, 0, s, g.k0, g.k1, r->level_start.p, A);
-            else if (r->fused)
-                hipLaunchKernelGGL((k_levels_narrow<true, false>), grid, block, 0, s, g.k0, g.k1, r->level_start.p, A);
-            else if (ordered)
-                hipLaunchKernelGGL((k_levels_narrow<false, true>), grid, block, 0, s, g.k0, g.k1, r->level_start.p, A);
-            else
-                hipLaunchKernelGGL((k_levels_narrow<false, false>), grid, block, 0, s, g.k0, g.k1, r->level_start.p,
-                                   A);
-            LF_TRY(r->prof_end());
-            ++narrow;
-        }
-        ++launches;
-    }
-    r->last_stats[0] = launches;
-    r->last_stats[1] = wide;
-    r->last_stats[2] = narrow;
-    r->last_stats[3] = r->NL;
-    return LF_OK;
-}
-
 int route_device(lf_router *r, double *q_dev, const double *lat_dev, int section, bool ordered = false)
 {
-    if (section != LF_SECTION_MAIN && section != LF_SECTION_FLOODPLAINS)
-        return lf_set_error(LF_E_SECTION, "The section parameter must be either 'main_channel' or 'floodplain'!");
-    if (section == LF_SECTION_FLOODPLAINS && !r->has_floodplains)
-        return lf_set_error(LF_E_SECTION, "floodplains routing requested but alpha_floodplains was not given");
+    LF_TRY(check_section(*r, section));
     if (r->linked.p)
         return lf_set_error(LF_E_INVALID, "a router on a graph with structure links (lf_graph_create_ex) runs only the "
                             "fused sub-step path (lf_routing_substeps_fused*)");
     LF_HIP(hipSetDevice(r->device));
-    LF_TRY(enqueue_route(r, q_dev, lat_dev, section, ordered));
+    LF_TRY(enqueue_route(1, &r, &q_dev, &lat_dev, section, ordered));
     LF_HIP(hipGetLastError());
     if (r->profile) LF_TRY(r->prof_collect());
     return LF_OK;
@@ -801,34 +607,11 @@ int lf_router_create(const lf_graph *g, const double *alpha, double beta, const 
     r->dt = dt;
     r->dx_per_pixel = dx != nullptr;
     r->has_floodplains = alpha_floodplains != nullptr;
-    // beta == 3/5 (every LISFLOOD setting): fused prep + polynomial solve.  LF_GENERAL_POW=1 forces the
-    // general path (the reference's own Newton iteration with pow) for A/B parity and timing.
-    const char *force_general = std::getenv("LF_GENERAL_POW");
-    r->fused = (beta == 0.6) && !(force_general && force_general[0] == '1');
+    r->fused = router_fused(beta);
     const int64_t n = g->N;
-    int rc = LF_OK;
     const std::vector<int32_t> &g_perm = g->perm;
     const std::vector<int32_t> &g_ups_ptr = g->ups_ptr;
-    {
-        // a_dx_div_dt = alpha * dx / dt, evaluated left to right (:127), permuted into sweep order
-        std::vector<double> h(n);
-        auto fill = [&](const double *al) {
-            for (int64_t p = 0; p < n; ++p) {
-                const int32_t pix = g_perm[p];
-                h[p] = al[pix] * (dx ? dx[pix] : dx_scalar) / dt;
-            }
-        };
-        fill(alpha);
-        rc = r->a1.upload(h.data(), n, ctx->stream);
-        if (rc == LF_OK && alpha_floodplains) {
-            fill(alpha_floodplains);
-            rc = r->a2.upload(h.data(), n, ctx->stream);
-        }
-        if (rc == LF_OK && dx) {
-            for (int64_t p = 0; p < n; ++p) h[p] = dx[g_perm[p]];
-            rc = r->dx.upload(h.data(), n, ctx->stream);
-        }
-    }
+    int rc = upload_sweep_statics(*r, g_perm, alpha, alpha_floodplains, dx, ctx->stream);
     if (rc == LF_OK) rc = r->perm.upload(g_perm.data(), n, ctx->stream);
     if (rc == LF_OK) rc = r->ups_ptr.upload(g_ups_ptr.data(), n + 1, ctx->stream);
     if (rc == LF_OK && g->has_links) rc = r->linked.upload(g->linked.data(), n, ctx->stream);
@@ -861,22 +644,7 @@ int lf_router_create(const lf_graph *g, const double *alpha, double beta, const 
         return rc;
     }
     r->h_level_start = g->level_start;
-    // launch schedule: runs of narrow levels -> one single-workgroup launch each; wide levels -> one launch per level
-    {
-        const int64_t NL = g->NL;
-        auto level_size = [&](int64_t k) { return g->level_start[k + 1] - g->level_start[k]; };
-        for (int64_t k = 0; k < NL;) {
-            if (level_size(k) <= kNarrowMax) {
-                int64_t e = k + 1;
-                while (e < NL && level_size(e) <= kNarrowMax) ++e;
-                r->schedule.push_back({(int)k, (int)e, false});
-                k = e;
-            } else {
-                r->schedule.push_back({(int)k, (int)k + 1, true});
-                ++k;
-            }
-        }
-    }
+    r->schedule = level_segments(g->level_start, 0, g->NL);
     // (zero-length structure links need nothing special: such cells sit at the end of their level, inside the upstream
     // range of the LAST cell of the next level -- which adds their 0.0 -- and so inside the last cone of a block)
     rc = build_level_blocks(r, g, false);
@@ -914,8 +682,7 @@ int lf_router_route_device_multi(int count, lf_router **routers, double **discha
     if (count < 1 || !routers || !discharge_dev || !lateral_dev) return lf_set_error(LF_E_INVALID, "null argument");
     for (int i = 0; i < count; ++i)
         if (!routers[i] || !discharge_dev[i] || !lateral_dev[i]) return lf_set_error(LF_E_INVALID, "null argument");
-    if (section != LF_SECTION_MAIN && section != LF_SECTION_FLOODPLAINS)
-        return lf_set_error(LF_E_SECTION, "The section parameter must be either 'main_channel' or 'floodplain'!");
+    LF_TRY(check_section(*routers[0], section)); // (the other routers are checked where they are not swept together)
     bool together = count > 1 && count <= kMaxMulti;
     for (int i = 0; i < count && together; ++i) {
         const lf_router *r = routers[i], *r0 = routers[0];
@@ -929,7 +696,7 @@ int lf_router_route_device_multi(int count, lf_router **routers, double **discha
         return LF_OK;
     }
     LF_HIP(hipSetDevice(routers[0]->device));
-    LF_TRY(enqueue_route_multi(count, routers, discharge_dev, lateral_dev, section, engine_order != 0));
+    LF_TRY(enqueue_route(count, routers, discharge_dev, lateral_dev, section, engine_order != 0));
     LF_HIP(hipGetLastError());
     return LF_OK;
 }
@@ -981,8 +748,7 @@ int lf_router_from_engine_order(lf_router *r, const double *src_ord_dev, double 
 int lf_router_route_host(lf_router *r, double *discharge_host, const double *lateral_host, int section)
 {
     if (!r || !discharge_host || !lateral_host) return lf_set_error(LF_E_INVALID, "null argument");
-    if (section != LF_SECTION_MAIN && section != LF_SECTION_FLOODPLAINS)
-        return lf_set_error(LF_E_SECTION, "The section parameter must be either 'main_channel' or 'floodplain'!");
+    LF_TRY(check_section(*r, section));
     LF_HIP(hipSetDevice(r->device));
     const size_t bytes = sizeof(double) * (size_t)r->N;
     if (!r->io_q.p) LF_TRY(r->io_q.alloc(r->N));
@@ -1118,70 +884,27 @@ int lf_accuflux_ordered_multi_device(lf_router *r, int nv, const double *const *
         M.x[v] = x_ord_dev[v < nv ? v : 0];
         M.acc[v] = acc_ord_dev[v < nv ? v : 0];
     }
-    int64_t launches = 0;
-#define LF_ACCU(KERNEL, GRID, BLOCK, ...)                                                      \
-    do {                                                                                       \
-        if (nv == 1)                                                                           \
-            hipLaunchKernelGGL(KERNEL<1>, GRID, BLOCK, 0, s, __VA_ARGS__);                     \
-        else if (nv == 2)                                                                      \
-            hipLaunchKernelGGL(KERNEL<2>, GRID, BLOCK, 0, s, __VA_ARGS__);                     \
-        else if (nv == 3)                                                                      \
-            hipLaunchKernelGGL(KERNEL<3>, GRID, BLOCK, 0, s, __VA_ARGS__);                     \
-        else                                                                                   \
-            hipLaunchKernelGGL(KERNEL<4>, GRID, BLOCK, 0, s, __VA_ARGS__);                     \
-        ++launches;                                                                            \
-    } while (0)
-#define LF_ACCU_CW(NVV, GRID, ...)                                                            \
-    do {                                                                                       \
-        if (r->rb_cw == 64)                                                                    \
-            hipLaunchKernelGGL((k_accu_cones<NVV, 64>), GRID, dim3(64), 0, s, __VA_ARGS__);    \
-        else                                                                                   \
-            hipLaunchKernelGGL((k_accu_cones<NVV, kBlock>), GRID, dim3(kBlock), 0, s, __VA_ARGS__); \
-    } while (0)
-#define LF_ACCU_CONES(GRID, ...)                                                               \
-    do {                                                                                       \
-        if (nv == 1)                                                                           \
-            LF_ACCU_CW(1, GRID, __VA_ARGS__);                                                  \
-        else if (nv == 2)                                                                      \
-            LF_ACCU_CW(2, GRID, __VA_ARGS__);                                                  \
-        else if (nv == 3)                                                                      \
-            LF_ACCU_CW(3, GRID, __VA_ARGS__);                                                  \
-        else                                                                                   \
-            LF_ACCU_CW(4, GRID, __VA_ARGS__);                                                  \
-        ++launches;                                                                            \
-    } while (0)
-    if (r->rb_lmax > 1 && cones_enabled()) {
-        const int NB = (int)r->rb_level.size() - 1;
-        for (int b = 0; b < NB; ++b) {
-            const int k0 = r->rb_level[b], nl = r->rb_level[b + 1] - k0;
-            if (nl > 1) {
-                cone_plan_args C;
-                C.cone = r->rb_cone.p + r->rb_off[b];
-                C.nl = nl;
-                C.n_cells = (int)r->N;
-                const dim3 grid((unsigned)(r->rb_row[b + 1] - r->rb_row[b] - 1));
-                LF_ACCU_CONES(grid, C, r->ups_ptr.p, M);
-            } else {
-                const int first = (int)r->h_level_start[k0];
-                const int count = (int)(r->h_level_start[k0 + 1] - r->h_level_start[k0]);
-                LF_ACCU(k_accu_level, dim3(blocks_for(count)), dim3(kBlock), first, count, r->ups_ptr.p, M);
-            }
-        }
-    } else {
-        for (const segment &g : r->schedule) {
-            if (g.wide) {
-                const int first = (int)r->h_level_start[g.k0];
-                const int count = (int)(r->h_level_start[g.k0 + 1] - r->h_level_start[g.k0]);
-                LF_ACCU(k_accu_level, dim3(blocks_for(count)), dim3(kBlock), first, count, r->ups_ptr.p, M);
-            } else {
-                LF_ACCU(k_accu_narrow, dim3(1), dim3(kNarrowBlock), g.k0, g.k1, r->level_start.p, r->ups_ptr.p, M);
-            }
-        }
-    }
-#undef LF_ACCU
-#undef LF_ACCU_CONES
-#undef LF_ACCU_CW
-    r->last_stats[0] = launches;
+    launch_counts c;
+    LF_TRY(pick_count(nv, [&](auto nvc) {
+        constexpr int NV = nvc;
+        auto cones = [&](dim3 grid, const cone_plan_args &C, int64_t) {
+            if (r->rb_cw == 64)
+                hipLaunchKernelGGL((k_accu_cones<NV, 64>), grid, dim3(64), 0, s, C, r->ups_ptr.p, M);
+            else
+                hipLaunchKernelGGL((k_accu_cones<NV, kBlock>), grid, dim3(kBlock), 0, s, C, r->ups_ptr.p, M);
+            return LF_OK;
+        };
+        auto level = [&](int first, int cells) {
+            hipLaunchKernelGGL(k_accu_level<NV>, dim3(blocks_for(cells)), dim3(kBlock), 0, s, first, cells, r->ups_ptr.p, M);
+            return LF_OK;
+        };
+        auto narrow = [&](int k0, int k1) {
+            hipLaunchKernelGGL(k_accu_narrow<NV>, dim3(1), dim3(kNarrowBlock), 0, s, k0, k1, r->level_start.p, r->ups_ptr.p, M);
+            return LF_OK;
+        };
+        return route_schedule(*r, 0, (int)r->rb_level.size() - 1, r->schedule, r->rb_lmax > 1, c, cones, level, narrow);
+    }));
+    r->last_stats[0] = c.launches;
     r->last_stats[1] = r->last_stats[2] = 0;
     r->last_stats[3] = r->NL;
     LF_HIP(hipGetLastError());
@@ -1546,19 +1269,19 @@ int fused_impl(lf_router *r, const lf_substep_args *a, int nsteps, int64_t sidef
         const bool split_form = all35 && !F.inert && (in ? F.linked != nullptr : F.linked == nullptr) && r->fb_cw == 64 &&
                                 n < ((int64_t)1 << 29) && (es ? es[0] != '0' : ncones <= (in ? split_max_struct : split_max));
         if (split_form)
-            fused_pick(a->split, in, [&](auto sp, auto st) {
+            pick_flags(a->split, in, [&](auto sp, auto st) {
                 hipLaunchKernelGGL((k_fused_cones_split<sp, st>), grid, dim3(64 * (1 + kFusedKC)), 0, s, F);
             });
         else
-            fused_pick(a->split, all35, [&](auto sp, auto a35) {
-                fused_pick(in, r->fb_cw == 64, [&](auto st, auto cw64) {
+            pick_flags(a->split, all35, [&](auto sp, auto a35) {
+                pick_flags(in, r->fb_cw == 64, [&](auto st, auto cw64) {
                     constexpr int CW = decltype(cw64)::value ? 64 : kBlock;
                     hipLaunchKernelGGL((k_fused_cones<sp, a35, st, false, CW>), grid, dim3(CW), 0, s, F);
                 });
             });
     };
     auto levels = [&](dim3 grid) {
-        fused_pick(a->split, in, [&](auto sp, auto st) {
+        pick_flags(a->split, in, [&](auto sp, auto st) {
             hipLaunchKernelGGL((k_fused_substeps<sp, st>), grid, dim3(kBlock), 0, s, F);
         });
     };

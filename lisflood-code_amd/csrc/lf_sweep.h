@@ -1,5 +1,5 @@
-// lf_sweep.h -- device code of the level sweep, shared by the single-GPU router (lf_router.hip) and the
-// row-block distributed router (lf_dist.hip).  See lf_router.hip for the data layout.
+// lf_sweep.h -- the level sweep, shared by the single-GPU router (lf_router.hip) and the row-block distributed router
+// (lf_dist.hip): device code, then the host schedule of a router call.  See lf_router.hip for the data layout.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -16,6 +16,28 @@ constexpr int kNarrowBlock = 1024;
 constexpr int kNarrowMax = 1024; // levels up to this many cells are swept by the single-workgroup kernel
 
 inline int blocks_for(int64_t n) { return (int)((n + kBlock - 1) / kBlock); }
+
+// One launch of a router call without level blocks: a wide level, or a run of consecutive narrow levels
+struct level_segment {
+    int k0, k1; // levels [k0, k1); wide segments have k1 == k0 + 1
+    bool wide;
+};
+
+// Levels [k_lo, k_hi) of `level_start` as segments: a level of more than kNarrowMax cells is one wide segment, a run of
+// levels of at most kNarrowMax cells one narrow segment
+inline std::vector<level_segment> level_segments(const std::vector<int64_t> &level_start, int64_t k_lo, int64_t k_hi)
+{
+    auto narrow = [&](int64_t k) { return level_start[k + 1] - level_start[k] <= kNarrowMax; };
+    std::vector<level_segment> out;
+    for (int64_t k = k_lo; k < k_hi;) {
+        int64_t e = k + 1;
+        if (narrow(k))
+            while (e < k_hi && narrow(e)) ++e;
+        out.push_back({(int)k, (int)e, !narrow(k)});
+        k = e;
+    }
+    return out;
+}
 
 // solve1Pixel, kinematic_wave_parallel_tools.py:59-82 (c = const_plus_ups_infl)
 __device__ __forceinline__ double lf_solve_cell(double c, double a, double ba, double beta, double inv_beta,
@@ -482,7 +504,7 @@ __global__ void __launch_bounds__(CW) k_sweep_cones(cone_plan_args C, sweep_args
 // hands the chain wavefront c = ups + constant with an empty range (0.0 + c == c for every c that is solved; c == -0.0
 // gives 0 either way).  Arithmetic per cell = sweep_cell: bit-identical to the level sweep.
 #ifndef LF_CONE_KC
-#define LF_CONE_KC 8 /* levels per chunk and supply wavefronts of the few-cones shape (lf_router.hip: launch_split_shape) */
+#define LF_CONE_KC 8 /* levels per chunk and supply wavefronts of the few-cones shape (lf_router.hip: launch_sweep_cones) */
 #endif
 #ifndef LF_CONE_NS
 #define LF_CONE_NS 4
@@ -937,6 +959,167 @@ __global__ void __launch_bounds__(kNarrowBlock) k_levels_narrow(int k0, int k1, 
         __threadfence_block();
         __syncthreads();
     }
+}
+
+// ================================================================================================
+// Host side: the setup and the launch schedule of a plain router call, shared by the single domain (lf_router.hip) and the
+// row-block partition (lf_dist.hip).  R is lf_router or lf_dist_router, whose members used here have the same names and
+// meanings.
+// ================================================================================================
+
+// The instantiation of a kernel for two run-time flags: fn(std::bool_constant<a>, std::bool_constant<b>)
+template <class Fn>
+void pick_flags(bool a, bool b, Fn &&fn)
+{
+    if (a && b)
+        fn(std::true_type(), std::true_type());
+    else if (a)
+        fn(std::true_type(), std::false_type());
+    else if (b)
+        fn(std::false_type(), std::true_type());
+    else
+        fn(std::false_type(), std::false_type());
+}
+
+// ... for a count of 1 to 4 (routers swept together, accuflux vectors): fn(std::integral_constant<int, n>), its result
+template <class Fn>
+decltype(auto) pick_count(int n, Fn &&fn)
+{
+    if (n == 1) return fn(std::integral_constant<int, 1>());
+    if (n == 2) return fn(std::integral_constant<int, 2>());
+    if (n == 3) return fn(std::integral_constant<int, 3>());
+    return fn(std::integral_constant<int, 4>());
+}
+
+// beta == 3/5 (every LISFLOOD setting): prep fused into the sweep, polynomial closure solve (lf_math.h).  LF_GENERAL_POW=1
+// forces the general path (the reference's own Newton iteration with pow) for A/B parity and timing.
+inline bool router_fused(double beta)
+{
+    const char *e = std::getenv("LF_GENERAL_POW");
+    return beta == 0.6 && !(e && e[0] == '1');
+}
+
+// LF_LEVEL_STATICS=0: the wide levels read their static vectors as separate streams, not as one record per cell (A/B
+// switch, read at every call)
+inline bool level_statics_enabled()
+{
+    const char *e = std::getenv("LF_LEVEL_STATICS");
+    return !(e && e[0] == '0');
+}
+
+template <class R>
+int check_section(const R &r, int section)
+{
+    if (section != LF_SECTION_MAIN && section != LF_SECTION_FLOODPLAINS)
+        return lf_set_error(LF_E_SECTION, "The section parameter must be either 'main_channel' or 'floodplain'!");
+    if (section == LF_SECTION_FLOODPLAINS && !r.has_floodplains)
+        return lf_set_error(LF_E_SECTION, "floodplains routing requested but alpha_floodplains was not given");
+    return LF_OK;
+}
+
+// a_dx_div_dt = alpha * dx / dt, evaluated left to right (kinematic_wave_parallel.py:127), for the main channel (a1) and
+// the floodplains (a2, if given), and the per-pixel dx (if given), permuted into sweep order and uploaded on stream s
+template <class R>
+int upload_sweep_statics(R &r, const std::vector<int32_t> &perm, const double *alpha, const double *alpha_floodplains,
+                         const double *dx, hipStream_t s)
+{
+    const int64_t n = r.N;
+    std::vector<double> h(n);
+    auto fill = [&](const double *al) {
+        for (int64_t p = 0; p < n; ++p) {
+            const int32_t pix = perm[p];
+            h[p] = al[pix] * (dx ? dx[pix] : r.dx_scalar) / r.dt;
+        }
+    };
+    fill(alpha);
+    LF_TRY(r.a1.upload(h.data(), n, s));
+    if (alpha_floodplains) {
+        fill(alpha_floodplains);
+        LF_TRY(r.a2.upload(h.data(), n, s));
+    }
+    if (dx) {
+        for (int64_t p = 0; p < n; ++p) h[p] = dx[perm[p]];
+        LF_TRY(r.dx.upload(h.data(), n, s));
+    }
+    return LF_OK;
+}
+
+// sweep_args of a call on r's section: the new discharge goes to qord (sweep order) and, unless null, to q_pix (pixel
+// order); the INDEXED and STATICS fields stay null for the caller
+template <class R>
+sweep_args sweep_args_of(const R &r, int section, double *qord, double *q_pix, const double *lat)
+{
+    sweep_args A;
+    A.ups_ptr = r.ups_ptr.p;
+    A.ups_idx = nullptr;
+    A.ups_base = nullptr;
+    A.perm = r.perm.p;
+    A.a = (section == LF_SECTION_MAIN) ? r.a1.p : r.a2.p;
+    A.constant = r.constant.p;
+    A.lat = lat;
+    A.dx = r.dx_per_pixel ? r.dx.p : nullptr;
+    A.dx_scalar = r.dx_scalar;
+    A.beta = r.beta;
+    A.inv_beta = r.inv_beta;
+    A.b_minus_1 = r.b_minus_1;
+    A.kmax = r.kmax;
+    A.qord = qord;
+    A.q_pix = q_pix;
+    A.qold_src = nullptr;
+    A.adx = nullptr;
+    A.rec24 = nullptr;
+    return A;
+}
+
+struct launch_counts {
+    int64_t launches = 0, wide = 0, narrow = 0; // every launch; of them, the one-level ones; the cone and narrow-run ones
+};
+
+// The launch schedule of a router call.  With level blocks -- use_blocks, the caller's condition,
+// and LF_ROUTE_CONES not 0 (read at every call: bench.py switches it for its A/B legs) -- the blocks [b0, b0 + nblocks) of
+// r's rb_* plan, each one launch:
+//   several levels  cones(grid, C, cells): one workgroup per cone of the block;
+//   one level       level(first, cells), none for an empty level;
+// otherwise the segments `segs`:
+//   a wide level    level(first, cells);
+//   narrow levels   narrow(k0, k1): one workgroup walks the run.
+// The callbacks return an LF_ status; n counts the launches.
+template <class R, class Cones, class Level, class Narrow>
+int route_schedule(const R &r, int b0, int nblocks, const std::vector<level_segment> &segs, bool use_blocks,
+                   launch_counts &n, Cones &&cones, Level &&level, Narrow &&narrow)
+{
+    const char *e = std::getenv("LF_ROUTE_CONES");
+    auto cells = [&](int k0, int k1) { return r.h_level_start[k1] - r.h_level_start[k0]; };
+    if (use_blocks && !(e && e[0] == '0')) {
+        for (int b = b0; b < b0 + nblocks; ++b) {
+            const int k0 = r.rb_level[b], nl = r.rb_level[b + 1] - k0;
+            if (nl > 1) {
+                cone_plan_args C;
+                C.cone = r.rb_cone.p + r.rb_off[b];
+                C.nl = nl;
+                C.n_cells = (int)r.N;
+                LF_TRY(cones(dim3((unsigned)(r.rb_row[b + 1] - r.rb_row[b] - 1)), C, cells(k0, k0 + nl)));
+                ++n.narrow;
+            } else {
+                if (cells(k0, k0 + 1) <= 0) continue;
+                LF_TRY(level((int)r.h_level_start[k0], (int)cells(k0, k0 + 1)));
+                ++n.wide;
+            }
+            ++n.launches;
+        }
+        return LF_OK;
+    }
+    for (const level_segment &g : segs) {
+        if (g.wide) {
+            LF_TRY(level((int)r.h_level_start[g.k0], (int)cells(g.k0, g.k1)));
+            ++n.wide;
+        } else {
+            LF_TRY(narrow(g.k0, g.k1));
+            ++n.narrow;
+        }
+        ++n.launches;
+    }
+    return LF_OK;
 }
 
 } // namespace

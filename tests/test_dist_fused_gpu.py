@@ -111,13 +111,24 @@ def test_fused_model_step_on_row_blocks_config4_shape(amd, family, seed):
     kw.close()
 
 
-@pytest.mark.parametrize("family,seed,nblocks", [("deep", 2, 3), ("shallow", 1, 4), ("saddle", 6, 3), ("river", 7, 4)])
-def test_router_call_in_the_order_the_two_streams_allow(amd, oracle, family, seed, nblocks):
+# (family, seed, nblocks, environment): the default schedule; one launch per wide unit and per run of narrow ones
+# (LF_ROUTE_CONES=0); the wide units without their static records (LF_LEVEL_STATICS=0)
+_TWO_STREAMS_CASES = [("deep", 2, 3, {}), ("shallow", 1, 4, {}), ("saddle", 6, 3, {}), ("river", 7, 4, {}),
+                      ("deep", 2, 3, {"LF_ROUTE_CONES": "0"}), ("shallow", 1, 4, {"LF_ROUTE_CONES": "0"}),
+                      ("saddle", 6, 3, {"LF_ROUTE_CONES": "0"}), ("river", 7, 4, {"LF_ROUTE_CONES": "0"}),
+                      ("shallow", 1, 4, {"LF_LEVEL_STATICS": "0"})]
+
+
+@pytest.mark.parametrize("family,seed,nblocks,env", [
+    pytest.param(*c, id="-".join([str(x) for x in c[:3]] + ["%s=%s" % kv for kv in c[3].items()])) for c in _TWO_STREAMS_CASES])
+def test_router_call_in_the_order_the_two_streams_allow(amd, oracle, monkeypatch, family, seed, nblocks, env):
     """lf_dist_router_route runs a phase's boundary-critical part, hands the round's halo to a second stream and sweeps
     the bulk part beside it: the same order on one GPU (packs taken right after part 0, ghost slots filled after part 1)
     gives the single-domain oracle's discharge, three calls"""
     from lisflood_amd import dist as D
     from lisflood_amd import synthetic as syn
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
     H, W = 300, 260
     N = H * W
     codes = syn.make_ldd(family, H, W, seed)
