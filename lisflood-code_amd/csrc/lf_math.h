@@ -53,7 +53,8 @@ __device__ __forceinline__ double lf_cbrt(double x)
 
 __device__ __forceinline__ bool lf_fast_range(double x) { return x >= LF_FAST_MIN && x <= LF_FAST_MAX; }
 
-// x^0.6 for beta = 3/5; exact pow semantics outside the fast range (0, negatives, NaN, inf, extremes)
+// x^0.6 for beta = 3/5, within 3.6 ulp of the exact x^(3/5) in the fast range (r^3 of a root within ~1 ulp; measured in
+// tests/test_device_math_gpu.py); exact pow semantics outside the fast range (0, negatives, NaN, inf, extremes)
 __device__ __forceinline__ double lf_pow_3_5(double x)
 {
     if (x == 0.0) return 0.0; // pow(+-0, 0.6) = +0: dry cells are common and must not take the OCML path
@@ -93,7 +94,7 @@ __device__ __forceinline__ void lf_pow_3_5_n(const double (&x)[N], double (&out)
         if (!fast[i]) out[i] = (x[i] == 0.0) ? 0.0 : pow(x[i], 0.6); // zero, or beyond the fast range (rare)
 }
 
-// x^(1/0.6) = x^(5/3) = x * cbrt(x)^2
+// x^(1/0.6) = x^(5/3) = x * cbrt(x)^2, within 3.0 ulp of the exact x^(5/3) in the fast range (measured as above)
 __device__ __forceinline__ double lf_pow_5_3(double x)
 {
     if (x == 0.0) return 0.0; // pow(+-0, 5/3) = +0
@@ -179,8 +180,12 @@ __device__ __forceinline__ double lf_solve_3_5_pre(double c, double a, float af,
 // handling the soil kernel never needs (negative bases, integer-exponent tests, overflow).  This version is
 // exp2(y * log2(x)) with an fdlibm-style log (argument reduced to [sqrt(1/2), sqrt(2)), 7-term minimax in
 // s = f/(2+f)), the product y*e carried with its rounding error (fma), and a degree-13 polynomial for 2^r:
-// ~70 instructions, relative error ~1e-15 for |y log2 x| <= 50 (measured against OCML in the gpu tests).
-// x == 0 -> 0, x == 1 -> 1, NaN propagates, x == +inf -> +inf.
+// ~70 instructions, relative error <= 6.3e-15 for |y log2 x| <= 50 and <= 1.1e-14 beyond (normal results; the error of
+// y * log2(m) grows with |y|), results that overflow are +inf, results that underflow within one denormal ulp
+// (measured against a 240-bit reference: tests/test_device_math_gpu.py).  Bases: finite x >= 0 (0 -> 0, NaN -> NaN, a
+// negative x -> NaN); exponents: y > 0, finite.  x = +inf and a NaN y give NaN, where pow gives +inf and, at x = 1, 1
+// (frexp_mant(inf) = inf; y * 0 with a NaN y): no caller passes either -- the soil bases are saturation degrees in
+// [0, 1] and the exponents parameters, and lf_pow_scalar_exponent sends +inf, NaN exponents and negative bases to pow.
 // ------------------------------------------------------------------------------------------------
 #ifndef LF_RCP_SEED
 #define LF_RCP_SEED(d) __builtin_amdgcn_rcp(d)
@@ -305,7 +310,7 @@ __device__ __forceinline__ double lf_pow_pos(double x, double y)
 }
 
 // x^y of the transmission loss (transmission.py:76-87: (Q^p2 - sub)^p1, both exponents scalars of the settings): lf_pow_pos
-// for a finite positive exponent and a base that is not negative (0 -> 0, NaN -> NaN, as pow), OCML pow otherwise -- a
+// for a finite positive exponent and a finite base that is not negative (0 -> 0, NaN -> NaN, as pow), OCML pow otherwise -- a
 // NEGATIVE base must keep pow's semantics: with the settings' defaults TransPower1 = 2, TransSub = 0.3 the inner term is
 // negative on every reach below 0.09 m3/s and pow(-0.3, 2.0) = 0.09, not NaN (integer exponents are defined there).  ~75
 // instead of ~220 instructions per call on the common path; every kernel that computes the loss goes through here, so
@@ -319,6 +324,7 @@ static __device__ __attribute__((noinline)) double lf_pow_scalar_exponent(double
 {
     if (y == 2.0) return x * x;
     if (y == 0.5) return sqrt(x);
-    if (y > 0.0 && y < 1e6 && !(x < 0.0)) return lf_pow_pos(x, y); // (y is a kernel argument; negative bases are the rare lanes)
+    if (y > 0.0 && y < 1e6 && !(x < 0.0) && x != __builtin_inf()) return lf_pow_pos(x, y); // (y is a kernel argument;
+                                                                                           // negative / infinite bases are rare)
     return pow(x, y);
 }

@@ -1443,6 +1443,97 @@ def test_soil_columns_small_and_ragged_shapes(amd, oracle, N, V, L):
         a.free()
 
 
+def _soil_with_empty_pore_space(N, seed):
+    """syn.soil_params with ThetaS == ThetaR (WS == WRes, pore-space flag set) in layers of a third of the columns: in 1b,
+    2 or both, the water content above (by >= 1 mm), at and below WRes and KSat raised so that the columns need several
+    Courant sub-steps (no soil evaporation or infiltration there: either can leave a layer a hair above WRes, at a huge
+    Courant number); in
+    1a (every fourth such column), which phase 1 clamps to WS1a == WRes1a: NaN, as in the oracle.  The derived parameter
+    arrays are kept consistent (derived_parameters_hold)."""
+    from lisflood_amd import synthetic as syn
+    d = syn.soil_params(N, seed=seed)
+    rng = np.random.default_rng(seed)
+    lu = np.asarray(d["index_landuse_all"])
+    cols = np.flatnonzero(rng.random(N) < 0.35)
+    d["ESMax"][:, cols] = 0.0
+    d["Rain"][cols] = d["SnowMelt"][cols] = d["LeafDrainage"][:, cols] = 0.0
+    for j, col in enumerate(cols):
+        layers = (("1b",), ("2",), ("1b", "2"), ("1a",))[j % 4]
+        for name in layers:
+            if d["SoilDepth" + name][0, col] == 0:
+                continue
+            d["WS" + name][:, col] = d["WRes" + name][:, col]
+            d["KSat" + name][:, col] = rng.uniform(20.0, 60.0)
+            delta = (rng.uniform(1.0, 5.0), 0.0, -rng.uniform(1.0, 5.0))[(j // 4) % 3]
+            d["W" + name][:, col] = d["WRes" + name][lu, col] + delta
+    for k in ("WS", "WRes", "WFC", "WWP"):
+        d[k + "1"] = d[k + "1a"] + d[k + "1b"]
+    for name in ("1a", "1b", "2"):
+        d["PoreSpaceNotZero" + name] = (d["SoilDepth" + name] != 0) & (d["WS" + name] != 0)
+    d["W1"] = d["W1a"] + d["W1b"]
+    return d, cols
+
+
+@pytest.mark.parametrize("no_derived", ["0", "1"])
+@pytest.mark.parametrize("trip_cap", ["0", None])
+def test_soil_columns_with_empty_pore_space(amd, oracle, monkeypatch, no_derived, trip_cap):
+    """Layers with WS == WRes and the pore-space flag set (ThetaS == ThetaR != 0) in columns of several sub-steps: the
+    saturation degree is the IEEE quotient (w - WRes) / 0 (+inf -> 1 above WRes, -inf -> 0 below, NaN at WRes) in every
+    sub-step, as the oracle divides -- in the derived and the streamed parameter form, in the tile (LF_SOIL_TRIP_CAP=0)
+    and in k_soil_stragglers (the default cap).  NaN exactly where the oracle has NaN."""
+    import ctypes as C
+    from lisflood_amd import synthetic as syn
+    from lisflood_amd.soilloop import derived_parameters_hold
+    N = 6007
+    d, cols = _soil_with_empty_pore_space(N, seed=73)
+    assert derived_parameters_hold(d)
+    ref = {k: (v.copy() if hasattr(v, "copy") else v) for k, v in d.items()}
+    stats = np.zeros(4, np.int64)
+    oracle.soil_columns(ref)
+    oracle.lib().lfo_soil_stats(stats.ctypes.data_as(C.POINTER(C.c_int64)))
+    assert 0 < stats[1] and stats[3] < 400, stats        # multi-sub-step columns, no runaway trip count
+    assert np.isnan(ref["W1a"]).any() and np.isfinite(ref["W1a"][:, cols]).any()
+    monkeypatch.setenv("LF_SOIL_NO_DERIVED", no_derived)
+    if trip_cap is None:
+        monkeypatch.delenv("LF_SOIL_TRIP_CAP", raising=False)
+    else:
+        monkeypatch.setenv("LF_SOIL_TRIP_CAP", trip_cap)
+    dev = amd.soil.SoilColumnsDevice({k: (v.copy() if hasattr(v, "copy") else v) for k, v in d.items()})
+    dev.step()       # one step: the sub-steps move water into layers below WRes, a second step would start a hair above it
+    for k in syn.SOIL_WRITTEN:
+        got, w = dev.get(k), ref[k]
+        assert np.array_equal(np.isnan(got), np.isnan(w)), (k, np.flatnonzero(np.isnan(got) != np.isnan(w))[:5])
+        np.testing.assert_allclose(got, w, rtol=1e-9, atol=1e-11, equal_nan=True, err_msg=k)
+    for a in dev.dev.values():
+        a.free()
+
+
+def test_soil_pf_with_empty_pore_space(amd, oracle):
+    """soilloop.soil_pf (lf_soil_pf_device) against the oracle on the columns of test_soil_columns_with_empty_pore_space
+    (WS == WRes with the pore-space flag set: saturation 1, 0 or NaN) and ordinary ones."""
+    from lisflood_amd.soilloop import soilloop
+    N = 2003
+    d, cols = _soil_with_empty_pore_space(N, seed=79)
+    rng = np.random.default_rng(79)
+    for name in ("1a", "1b", "2"):
+        d["GenuInvAlpha" + name] = rng.uniform(20.0, 200.0, d["WS1a"].shape)
+        d["GenuInvN" + name] = rng.uniform(0.71, 0.91, d["WS1a"].shape)
+    d["HeadMax"] = 1e7
+    want = oracle.soil_pf(d, d["index_landuse_all"], d["HeadMax"])
+    v = _model_var(N)
+    for k in ("W1a", "W1b", "W2") + tuple(k + n for k in ("WRes", "WS", "PoreSpaceNotZero", "GenuInvAlpha", "GenuInvM",
+                                                               "GenuInvN") for n in ("1a", "1b", "2")):
+        setattr(v, k, np.array(d[k], copy=True))
+    v.HeadMax = d["HeadMax"]
+    m = soilloop(v, options={"simulatePF": True}); m.initial()
+    m.soil_pf()
+    for k, w in zip(("pF0", "pF1", "pF2"), want):
+        got = getattr(v, k)
+        assert np.array_equal(np.isnan(got), np.isnan(w)), k
+        np.testing.assert_allclose(got, w, rtol=1e-12, atol=1e-13, equal_nan=True, err_msg=k)
+    assert np.isnan(want[0][:, cols]).any() or (want[0][:, cols] == 7.0).any()
+
+
 @pytest.mark.parametrize("trip_cap", ["0", "1", "3", "6", "200"])
 def test_soil_columns_same_bits_whatever_the_trip_cap(amd, monkeypatch, trip_cap):
     """Which columns leave their tile for k_soil_stragglers (LF_SOIL_TRIP_CAP: none, every multi-sub-step one -- more than
