@@ -73,13 +73,13 @@ struct lf_dist_graph {
     std::vector<int32_t> out_slot;        // [N] by position: slot the cell's router outputs are stored in, -1 none
     std::vector<int32_t> ups_idx_f;       // as ups_idx: a same-phase local position, or -(slot) - 1
     int64_t n_slots = 0, slot_export[2] = {0, 0}, slot_ghost[2] = {0, 0}, slot_xphase = 0;
-    // level blocks and cones of every phase (lf_blocks.h; k_fused_cones<DIST>): blocks never span two phases
+    // level blocks and cones of every phase (lf_blocks.h; k_fused_cones<DIST>): blocks never span two phases, part =
+    // [nphases + 1] first block of every phase
     lf_block_plan fplan;
-    std::vector<int32_t> fplan_phase_block; // [nphases + 1] first block of every phase
     // the same for single router calls (k_sweep_cones<DIST>): blocks never span two STAGES (a phase's boundary-critical
-    // part and its bulk are swept separately), one wavefront per cone, blocks of up to LF_ROUTE_LEVELS (256) units
+    // part and its bulk are swept separately), one wavefront per cone, blocks of up to LF_ROUTE_LEVELS (256) units, part =
+    // [2 * nphases + 1] first block of every stage
     lf_block_plan rplan;
-    std::vector<int32_t> rplan_stage_block; // [2 * nphases + 1] first block of every stage
 };
 
 namespace {
@@ -437,15 +437,12 @@ int lf_dist_graph_finalize(lf_dist_graph *g, int nphases)
     }
     // ---- level blocks and cones of every phase ----
     {
-        int lmax = 16;
-        if (const char *e = std::getenv("LF_FUSED_LEVELS")) lmax = std::atoi(e);
-        lmax = lmax < 1 ? 1 : (lmax > 64 ? 64 : lmax);
-        if ((int64_t)n >= ((int64_t)1 << 29)) lmax = 1; // k_fused_cones: 32-bit byte offsets (see build_level_blocks)
-        int64_t wide = 262144;
-        if (const char *e = std::getenv("LF_FUSED_WIDE")) wide = std::atoll(e);
+        lf_block_knobs fk = lf_read_block_knobs(false, 16);
+        if ((int64_t)n >= ((int64_t)1 << 29)) fk.lmax = 1; // k_fused_cones: 32-bit byte offsets (see build_level_blocks)
+        const lf_block_knobs rk = lf_read_block_knobs(true, 256);
         g->fplan = lf_block_plan();
-        g->fplan_phase_block.assign(nphases + 1, 0);
-        try {
+        g->rplan = lf_block_plan();
+        LF_TRY(lf_build_blocks_guarded([&] {
             // child[a] = first position of the unit before whose SAME-PHASE downstream cell is at or behind a; cells that
             // drain into a later phase or another rank sit between the runs and go with the run behind them
             std::vector<int32_t> child((size_t)n, 0);
@@ -466,38 +463,19 @@ int lf_dist_graph_finalize(lf_dist_graph *g, int nphases)
                         child[(size_t)a] = (int32_t)u;
                     }
                 }
-            if (lmax > 1 && n < ((int64_t)1 << 31))
-                for (int j = 0; j < nphases; ++j) {
-                    g->fplan_phase_block[j] = (int32_t)g->fplan.level.size();
-                    lf_build_level_blocks(g->level_start, g->phase_level[j], g->phase_level[j + 1], lmax, wide, kBlock,
-                                          [&](int64_t pos) { return (int64_t)child[(size_t)pos]; }, g->fplan);
-                }
-            int rmax = 256;
-            if (const char *e = std::getenv("LF_ROUTE_LEVELS")) rmax = std::atoi(e);
-            rmax = rmax < 1 ? 1 : (rmax > 512 ? 512 : rmax);
-            g->rplan = lf_block_plan();
-            g->rplan_stage_block.assign(nstages + 1, 0);
-            if (rmax > 1 && n < ((int64_t)1 << 31))
-                for (int st = 0; st < nstages; ++st) {
-                    g->rplan_stage_block[st] = (int32_t)g->rplan.level.size();
-                    lf_build_level_blocks(g->level_start, g->stage_level[st], g->stage_level[st + 1], rmax, wide, 64,
-                                          [&](int64_t pos) { return (int64_t)child[(size_t)pos]; }, g->rplan);
-                }
-            g->rplan_stage_block[nstages] = (int32_t)g->rplan.level.size();
-            g->rplan.level.push_back((int)(g->level_start.size() - 1));
-            if (!g->rplan.any_multi || g->rplan.cone.size() >= ((size_t)1 << 31)) { // one launch per unit it is
-                g->rplan = lf_block_plan();
-                g->rplan_stage_block.clear();
-            }
-        } catch (const std::bad_alloc &) {
-            return lf_set_error(LF_E_INVALID, "out of host memory while building the level blocks");
-        }
-        g->fplan_phase_block[nphases] = (int32_t)g->fplan.level.size();
-        g->fplan.level.push_back((int)(g->level_start.size() - 1));
-        if (!g->fplan.any_multi || g->fplan.cone.size() >= ((size_t)1 << 31)) { // nothing to gain: the per-unit wavefront
-            g->fplan = lf_block_plan();
-            g->fplan_phase_block.clear();
-        }
+            // (without a block of several units the plans end up empty: the per-unit wavefront, one launch per unit)
+            auto build = [&](lf_block_plan &plan, const std::vector<int32_t> &range, const lf_block_knobs &k, int cw) {
+                if (k.lmax > 1 && n < ((int64_t)1 << 31))
+                    for (size_t i = 0; i + 1 < range.size(); ++i) {
+                        plan.begin_part();
+                        lf_build_level_blocks(g->level_start, range[i], range[i + 1], k.lmax, k.wide, cw,
+                                              [&](int64_t pos) { return (int64_t)child[(size_t)pos]; }, plan);
+                    }
+                plan.finish((int64_t)g->level_start.size() - 1);
+            };
+            build(g->fplan, g->phase_level, fk, kBlock);
+            build(g->rplan, g->stage_level, rk, 64);
+        }));
     }
     g->finalized = true;
     return LF_OK;
@@ -588,57 +566,46 @@ int lf_dist_graph_block_stats(const lf_dist_graph *g, int64_t out[4])
 {
     if (!g || !g->finalized || !out) return lf_set_error(LF_E_INVALID, "graph not finalized");
     out[0] = out[1] = out[2] = out[3] = 0;
-    if (g->fplan_phase_block.empty()) return LF_OK;
     const lf_block_plan &f = g->fplan;
-    out[0] = (int64_t)f.level.size() - 1;
-    for (size_t b = 0; b + 1 < f.level.size(); ++b) {
-        out[1] += f.level[b + 1] - f.level[b] > 1;
-        out[2] += f.row[b + 1] - f.row[b] - 1;
+    out[0] = f.nblocks();
+    for (int b = 0; b < f.nblocks(); ++b) {
+        out[1] += f.multi(b);
+        out[2] += f.ncones(b);
     }
     out[3] = (int64_t)f.cone.size();
     return LF_OK;
 }
-// the block plan of single router calls (k_sweep_cones<DIST>), for tests: sizes = {stages + 1, blocks + 1, rows (= blocks
-// + 1 entries), entries of the cone table, launch units + 1}; with the arrays NULL only the sizes are returned.  All sizes 0
-// when no block holds more than one unit.
+// A block plan for tests: sizes = {parts + 1, blocks + 1, rows (= blocks + 1 entries), entries of the cone table}; with the
+// arrays NULL only the sizes are returned.  All sizes 0 when no block holds more than one unit.
+static void plan_copy_out(const lf_block_plan &f, int64_t sizes[4], int32_t *part, int32_t *level, int32_t *row, int32_t *off,
+                          int32_t *cone)
+{
+    sizes[0] = (int64_t)f.part.size();
+    sizes[1] = (int64_t)f.level.size();
+    sizes[2] = (int64_t)f.row.size();
+    sizes[3] = (int64_t)f.cone.size();
+    if (part) std::memcpy(part, f.part.data(), sizeof(int32_t) * f.part.size());
+    if (level) std::memcpy(level, f.level.data(), sizeof(int32_t) * f.level.size());
+    if (row) std::memcpy(row, f.row.data(), sizeof(int32_t) * f.row.size());
+    if (off) std::memcpy(off, f.off.data(), sizeof(int32_t) * f.off.size());
+    if (cone) std::memcpy(cone, f.cone.data(), sizeof(int32_t) * f.cone.size());
+}
+// the block plan of single router calls (k_sweep_cones<DIST>): parts = stages; sizes[4] = launch units + 1
 int lf_dist_graph_get_route_plan(const lf_dist_graph *g, int64_t sizes[5], int32_t *stage_block, int32_t *level, int32_t *row,
                                  int32_t *off, int32_t *cone, int64_t *level_start)
 {
     if (!g || !g->finalized || !sizes) return lf_set_error(LF_E_INVALID, "graph not finalized");
-    sizes[0] = sizes[1] = sizes[2] = sizes[3] = 0;
     sizes[4] = (int64_t)g->level_start.size();
     if (level_start) std::memcpy(level_start, g->level_start.data(), sizeof(int64_t) * g->level_start.size());
-    if (g->rplan_stage_block.empty()) return LF_OK;
-    const lf_block_plan &f = g->rplan;
-    sizes[0] = (int64_t)g->rplan_stage_block.size();
-    sizes[1] = (int64_t)f.level.size();
-    sizes[2] = (int64_t)f.row.size();
-    sizes[3] = (int64_t)f.cone.size();
-    if (stage_block) std::memcpy(stage_block, g->rplan_stage_block.data(), sizeof(int32_t) * g->rplan_stage_block.size());
-    if (level) std::memcpy(level, f.level.data(), sizeof(int32_t) * f.level.size());
-    if (row) std::memcpy(row, f.row.data(), sizeof(int32_t) * f.row.size());
-    if (off) std::memcpy(off, f.off.data(), sizeof(int32_t) * f.off.size());
-    if (cone) std::memcpy(cone, f.cone.data(), sizeof(int32_t) * f.cone.size());
+    plan_copy_out(g->rplan, sizes, stage_block, level, row, off, cone);
     return LF_OK;
 }
-// the block plan of the fused sub-step path (one plan per phase, cones of <= 256 cells per unit), same layout and calling
-// convention; sizes = {phases + 1, blocks + 1, rows, entries of the cone table}
+// the block plan of the fused sub-step path (cones of <= 256 cells per unit): parts = phases
 int lf_dist_graph_get_fused_plan(const lf_dist_graph *g, int64_t sizes[4], int32_t *phase_block, int32_t *level, int32_t *row,
                                  int32_t *off, int32_t *cone)
 {
     if (!g || !g->finalized || !sizes) return lf_set_error(LF_E_INVALID, "graph not finalized");
-    sizes[0] = sizes[1] = sizes[2] = sizes[3] = 0;
-    if (g->fplan_phase_block.empty()) return LF_OK;
-    const lf_block_plan &f = g->fplan;
-    sizes[0] = (int64_t)g->fplan_phase_block.size();
-    sizes[1] = (int64_t)f.level.size();
-    sizes[2] = (int64_t)f.row.size();
-    sizes[3] = (int64_t)f.cone.size();
-    if (phase_block) std::memcpy(phase_block, g->fplan_phase_block.data(), sizeof(int32_t) * g->fplan_phase_block.size());
-    if (level) std::memcpy(level, f.level.data(), sizeof(int32_t) * f.level.size());
-    if (row) std::memcpy(row, f.row.data(), sizeof(int32_t) * f.row.size());
-    if (off) std::memcpy(off, f.off.data(), sizeof(int32_t) * f.off.size());
-    if (cone) std::memcpy(cone, f.cone.data(), sizeof(int32_t) * f.cone.size());
+    plan_copy_out(g->fplan, sizes, phase_block, level, row, off, cone);
     return LF_OK;
 }
 // the fused path's tables by position: out_slot[N], ups_idx_f[n_edges] (either may be NULL)
@@ -825,14 +792,12 @@ struct lf_dist_router {
     lf_dbuf<double> fused_hist1, fused_hist2; // [nsteps][N] router outputs of every sub-step (k_fused_level_steps<DIST>)
     size_t fused_hist_refused = SIZE_MAX;     // smallest history size that did not fit its budget (lf_history_ensure)
     std::vector<int32_t> phase_level; // [nphases + 1] first launch unit of every phase
-    // level blocks + cones of every phase (empty: one launch per unit)
-    std::vector<int> fb_level, fb_row, fb_off;
-    std::vector<int32_t> fb_phase_block;
-    lf_dbuf<int> fb_level_dev, fb_row_dev, fb_off_dev, fb_cone;
+    // level blocks + cones of every phase (lf_dist_graph::fplan; empty: one launch per unit)
+    lf_block_plan fplan;
+    lf_block_plan_dev fplan_dev;
     // level blocks + cones of every stage for single router calls (lf_dist_graph::rplan; empty: the segment schedule)
-    std::vector<int> rb_level, rb_row, rb_off;
-    std::vector<int32_t> rb_stage_block;
-    lf_dbuf<int> rb_cone;
+    lf_block_plan rplan;
+    lf_block_plan_dev rplan_dev;
 };
 
 namespace {
@@ -904,10 +869,10 @@ int dist_compute_phase(lf_dist_router *r, double *q, const double *lat, int sect
             hipLaunchKernelGGL((k_levels_narrow<false, true, true>), dim3(1), dim3(kNarrowBlock), 0, s, k0, k1, r->level_start.p, A);
         return LF_OK;
     };
-    const bool blocks = !r->rb_stage_block.empty();
+    const bool blocks = !r->rplan.empty();
     launch_counts c;
     for (int st = 2 * phase + (part == 1 ? 1 : 0); st <= 2 * phase + (part == 0 ? 0 : 1); ++st) {
-        const int b0 = blocks ? r->rb_stage_block[st] : 0, nb = blocks ? r->rb_stage_block[st + 1] - b0 : 0;
+        const int b0 = blocks ? r->rplan.part[st] : 0, nb = blocks ? r->rplan.part[st + 1] - b0 : 0;
         LF_TRY(route_schedule(*r, b0, nb, r->schedule[st], blocks, c, cones, level, narrow));
     }
     r->last_launches += c.launches;
@@ -977,34 +942,11 @@ int lf_dist_router_create(const lf_dist_graph *g, const double *alpha, double be
     }
     if (rc == LF_OK) rc = r->ups_idx_f.upload(g->ups_idx_f.data(), g->ups_idx_f.size());
     if (rc == LF_OK) rc = r->out_slot.upload(g->out_slot.data(), g->out_slot.size());
+    if (rc == LF_OK) rc = r->fplan_dev.upload(r->fplan = g->fplan, true);
+    if (rc == LF_OK) rc = r->rplan_dev.upload(r->rplan = g->rplan, false);
     if (rc != LF_OK) {
         delete r;
         return rc;
-    }
-    if (!g->fplan_phase_block.empty()) {
-        rc = r->fb_level_dev.upload(g->fplan.level.data(), g->fplan.level.size());
-        if (rc == LF_OK) rc = r->fb_row_dev.upload(g->fplan.row.data(), g->fplan.row.size());
-        if (rc == LF_OK) rc = r->fb_off_dev.upload(g->fplan.off.data(), g->fplan.off.size());
-        if (rc == LF_OK) rc = r->fb_cone.upload(g->fplan.cone.data(), g->fplan.cone.size());
-        if (rc != LF_OK) {
-            delete r;
-            return rc;
-        }
-        r->fb_level = g->fplan.level;
-        r->fb_row = g->fplan.row;
-        r->fb_off = g->fplan.off;
-        r->fb_phase_block = g->fplan_phase_block;
-    }
-    if (!g->rplan_stage_block.empty()) {
-        const int rc2 = r->rb_cone.upload(g->rplan.cone.data(), g->rplan.cone.size());
-        if (rc2 != LF_OK) {
-            delete r;
-            return rc2;
-        }
-        r->rb_level = g->rplan.level;
-        r->rb_row = g->rplan.row;
-        r->rb_off = g->rplan.off;
-        r->rb_stage_block = g->rplan_stage_block;
     }
     r->n_slots = g->n_slots;
     for (int side = 0; side < 2; ++side) {
@@ -1376,8 +1318,8 @@ int dist_fused_phase(lf_dist_router *r, const lf_substep_args *a, int nsteps, in
         else
             hipLaunchKernelGGL((k_fused_substeps<false, false, true>), grid, dim3(kBlock), 0, s, F);
     };
-    const int b0 = r->fb_phase_block.empty() ? 0 : r->fb_phase_block[phase];
-    const int NB = r->fb_phase_block.empty() ? -1 : r->fb_phase_block[phase + 1] - b0;
+    const int b0 = r->fplan.empty() ? 0 : r->fplan.part[phase];
+    const int NB = r->fplan.empty() ? -1 : r->fplan.part[phase + 1] - b0;
     return fused_wavefront<true>(*r, F, unit0, nunits, b0, NB, true, s, r->last_launches, cones, levels,
                                  [](bool, int, int) {});
 }

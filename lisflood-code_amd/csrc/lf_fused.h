@@ -461,7 +461,7 @@ __global__ void __launch_bounds__(kBlock) k_fused_substeps(fused_args F)
 // ~2.5 us boundary on a latency-bound network (deep 5000^2: 5024 launches, 58 ms per model step).  Grouping several
 // levels into one launch with a workgroup barrier between them does not help by itself (measured: 58 ms for 1, 2, 4 and
 // 8 levels per launch) -- the chain is the cost, not the boundary.  This kernel shortens the chain:
-//  * the levels are grouped into blocks of up to fb_lmax consecutive levels and launch t works on (block t - s,
+//  * the levels are grouped into blocks of up to lmax consecutive levels and launch t works on (block t - s,
 //    sub-step s).  Every cell below the last level has exactly one downstream cell, in the next level, and the upstream
 //    cells of a contiguous range of positions are a contiguous range of the level before (lf_common.h, sweep order): a
 //    workgroup that owns a chunk of the block's LAST level owns the whole cone above it, level by level one contiguous
@@ -1771,7 +1771,8 @@ int fused_check_derived(R &r, const lf_substep_args &a, hipStream_t s)
     return LF_OK;
 }
 
-// The wavefront over levels [level0, level0 + nlevels) -- and, if nblocks >= 0, their level blocks [b0, b0 + nblocks) --
+// The wavefront over levels [level0, level0 + nlevels) -- and, if nblocks >= 0, their level blocks [b0, b0 + nblocks) of
+// r.fplan --
 // for F.nsteps sub-steps; fills F's wave fields and adds its launches to `launches`.  Of the three schedules the first that
 // applies runs:
 //   time-major   (time_major: the caller's precondition) one k_fused_level_steps launch per level;
@@ -1826,14 +1827,12 @@ int fused_wavefront(R &r, fused_args &F, int level0, int nlevels, int b0, int nb
         return F.packed ? dim3((unsigned)std::max<int64_t>(packed_blocks, 1), 1) : dim3(blocks_for(widest), nsteps);
     };
     if (nblocks >= 0 && nsteps <= kMaxPackedSteps) { // several levels per launch (k_fused_cones)
-        F.fb_level = r.fb_level_dev.p;
-        F.fb_row = r.fb_row_dev.p;
-        F.fb_cone = r.fb_cone.p;
-        F.fb_off = r.fb_off_dev.p;
+        F.fb_level = r.fplan_dev.level.p;
+        F.fb_row = r.fplan_dev.row.p;
+        F.fb_cone = r.fplan_dev.cone.p;
+        F.fb_off = r.fplan_dev.off.p;
         F.fb_block0 = b0;
         F.fb_nblocks = nblocks;
-        auto ncones = [&](int b) { return (int64_t)(r.fb_row[b0 + b + 1] - r.fb_row[b0 + b] - 1); };
-        auto multi = [&](int b) { return r.fb_level[b0 + b + 1] - r.fb_level[b0 + b] > 1; };
         for (int t = 0; t < nblocks + nsteps - 1; ++t) {
             // (block t - q, sub-step q), q = 0 .. nsteps-1, are independent of each other: the blocks of several levels go
             // to the cone kernel, the single (wide) levels to the level kernel, which streams them at full occupancy
@@ -1843,7 +1842,7 @@ int fused_wavefront(R &r, fused_args &F, int level0, int nlevels, int b0, int nb
             for (int q = 0; q < nsteps; ++q) {
                 F.blk_start[q] = (int)acc;
                 const int b = t - q;
-                if (b >= 0 && b < nblocks && multi(b)) acc += ncones(b);
+                if (b >= 0 && b < nblocks && r.fplan.multi(b0 + b)) acc += r.fplan.ncones(b0 + b);
             }
             F.blk_start[nsteps] = (int)acc;
             if (acc >= ((int64_t)1 << 31)) return lf_set_error(LF_E_INVALID, "fused sub-steps: grid too large");
@@ -1858,8 +1857,8 @@ int fused_wavefront(R &r, fused_args &F, int level0, int nlevels, int b0, int nb
                 F.blk_start[q] = (int)acc1;
                 F.lvl[q] = -1;
                 const int b = t - q;
-                if (b >= 0 && b < nblocks && !multi(b)) {
-                    const int k = r.fb_level[b0 + b];
+                if (b >= 0 && b < nblocks && !r.fplan.multi(b0 + b)) {
+                    const int k = r.fplan.level[b0 + b];
                     F.lvl[q] = k - level0;
                     acc1 += blocks_for(width(k));
                     widest = std::max(widest, width(k));

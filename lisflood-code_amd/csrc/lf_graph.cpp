@@ -268,26 +268,13 @@ int lf_graph_block_plan_stats(const lf_graph *g, int lmax, int64_t wide, int max
     if (!g || !out || lmax < 1 || max_cone < 1) return lf_set_error(LF_E_INVALID, "bad argument");
     for (int i = 0; i < 6; ++i) out[i] = 0;
     if (g->NL < 1) return LF_OK;
-    lf_block_plan plan;
-    try {
+    lf_block_plan plan; // (closed, not finished: a plan without a block of several levels is reported as it is)
+    LF_TRY(lf_build_blocks_guarded([&] {
         lf_build_level_blocks(g->level_start, 0, g->NL, lmax, wide, max_cone,
                               [&](int64_t pos) { return (int64_t)g->ups_ptr[pos]; }, plan);
-    } catch (const std::bad_alloc &) {
-        return lf_set_error(LF_E_INVALID, "out of host memory while building the level blocks");
-    }
-    plan.level.push_back((int)g->NL);
-    const int NB = (int)plan.level.size() - 1;
-    out[0] = NB;
-    for (int b = 0; b < NB; ++b) {
-        const int k0 = plan.level[b], nl = plan.level[b + 1] - k0;
-        if (nl < 2) continue;
-        const int64_t cones = plan.row[b + 1] - plan.row[b] - 1;
-        out[1] += 1;
-        out[2] += cones;
-        out[3] += cones * nl;
-        out[4] += g->level_start[k0 + nl] - g->level_start[k0];
-        out[5] = cones > out[5] ? cones : out[5];
-    }
+        plan.close(g->NL);
+    }));
+    plan.stats(g->level_start, out);
     return LF_OK;
 }
 
@@ -312,18 +299,15 @@ int lf_graph_block_plan_check(const lf_graph *g, int lmax, int64_t wide, int max
     for (int i = 0; i < 4; ++i) out[i] = 0;
     if (g->NL < 1) return LF_OK;
     lf_block_plan plan;
-    try {
+    LF_TRY(lf_build_blocks_guarded([&] {
         lf_build_level_blocks(g->level_start, 0, g->NL, lmax, wide, max_cone,
                               [&](int64_t pos) { return (int64_t)g->ups_ptr[pos]; }, plan);
-    } catch (const std::bad_alloc &) {
-        return lf_set_error(LF_E_INVALID, "out of host memory while building the level blocks");
-    }
-    plan.level.push_back((int)g->NL);
-    const int NB = (int)plan.level.size() - 1;
-    for (int b = 0; b < NB; ++b) {
-        const int k0 = plan.level[b], nl = plan.level[b + 1] - k0;
-        if (nl < 2) continue;
-        const int64_t cones = plan.row[b + 1] - plan.row[b] - 1;
+        plan.close(g->NL);
+    }));
+    for (int b = 0; b < plan.nblocks(); ++b) {
+        if (!plan.multi(b)) continue;
+        const int nl = plan.nlevels(b);
+        const int64_t cones = plan.ncones(b);
         const int *rows = plan.cone.data() + plan.off[b];
         for (int64_t c = 0; c < cones; ++c) {
             const int *c0 = rows + c * nl, *c1 = c0 + nl;

@@ -217,25 +217,19 @@ struct lf_router {
     int64_t site_cnt[2] = {-1, -1};
     std::vector<int64_t> h_level_start;
     std::vector<level_segment> schedule; // launches of a call without level blocks (level_segments)
-    // level blocks of the fused sub-step wavefront (build_level_blocks): block b = levels [fb_level[b], fb_level[b+1]),
-    // cut into cones = the upstream ranges of chunks of its last level, no range wider than a workgroup; block b has
-    // fb_row[b+1] - fb_row[b] - 1 cones and one more row (the end of every level) in fb_cone, from entry fb_off[b] on,
-    // one start per level and row
-    std::vector<int> fb_level, fb_row, fb_off;
     uint64_t graph_serial = 0; // lf_graph::serial of the graph the router was built on: same object <=> same plan
-    lf_dbuf<int> fb_level_dev, fb_row_dev, fb_cone;
-    lf_dbuf<int> fb_off_dev, fb_lvl2blk_dev; // fb_lvl2blk: block of every level (the sites of the structures variant)
-    std::vector<int> fb_lvl2blk;
-    int fb_lmax = 0, fb_cw = kBlock;
-    // the same plan with longer blocks for plain router calls (k_sweep_cones: no sub-step dimension to fill the machine
-    // with, so fewer, longer launches pay): host tables + the cone starts on the device
-    std::vector<int> rb_level, rb_row, rb_off;
+    // level blocks and cones (lf_blocks.h, build_level_blocks) of the fused sub-step wavefront, with lvl2blk for the
+    // sites of the structures variant; empty: the level-by-level wavefront
+    lf_block_plan fplan;
+    lf_block_plan_dev fplan_dev;
+    // the same with longer blocks for plain router calls (k_sweep_cones: no sub-step dimension to fill the machine with,
+    // so fewer, longer launches pay); empty: the segment schedule
+    lf_block_plan rplan;
+    lf_block_plan_dev rplan_dev;
     // the static vectors of a cell as one record per section, for the wide levels of ordered beta = 3/5 calls (k_level<.., STATICS>):
     // built on the first such call; statics_refused: the allocation failed once, the separate streams stay
     lf_dbuf<double2> adx1, adx2;
     bool statics_refused = false;
-    lf_dbuf<int> rb_cone;
-    int rb_lmax = 0, rb_cw = kBlock; // levels per block, cells per level of a cone (LF_ROUTE_CONE_WIDTH: 64 or 256)
     int64_t last_stats[4] = {0, 0, 0, 0};
     // profiling
     bool profile = false;
@@ -383,13 +377,15 @@ int enqueue_route(int count, lf_router **rs, double **q_dev, const double **lat_
             LF_TRY(r->prof_end());
             ++c.launches;
         }
-    bool blocks = r->rb_lmax > 1;
-    for (int i = 1; i < count; ++i) blocks = blocks && rs[i]->graph_serial == r->graph_serial && r->graph_serial != 0 && rs[i]->rb_lmax == r->rb_lmax && rs[i]->rb_cw == r->rb_cw;
+    bool blocks = !r->rplan.empty();
+    for (int i = 1; i < count; ++i)
+        blocks = blocks && rs[i]->graph_serial == r->graph_serial && r->graph_serial != 0 &&
+                 rs[i]->rplan.lmax == r->rplan.lmax && rs[i]->rplan.cw == r->rplan.cw;
     LF_TRY(pick_count(count, [&](auto nr) {
         constexpr int NR = nr;
         auto cones = [&](dim3 grid, const cone_plan_args &C, int64_t cells) {
             LF_TRY(r->prof_begin(2, cells));
-            launch_sweep_cones<NR>(r->rb_cw, r->fused, ordered, grid, s, C, M);
+            launch_sweep_cones<NR>(r->rplan.cw, r->fused, ordered, grid, s, C, M);
             return r->prof_end();
         };
         auto level = [&](int first, int cells) {
@@ -414,7 +410,7 @@ int enqueue_route(int count, lf_router **rs, double **q_dev, const double **lat_
             });
             return r->prof_end();
         };
-        return route_schedule(*r, 0, (int)r->rb_level.size() - 1, r->schedule, blocks, c, cones, level, narrow);
+        return route_schedule(*r, 0, r->rplan.nblocks(), r->schedule, blocks, c, cones, level, narrow);
     }));
     for (int i = 0; i < count; ++i) {
         rs[i]->last_stats[0] = c.launches;
@@ -442,10 +438,11 @@ int route_device(lf_router *r, double *q_dev, const double *lat_dev, int section
 
 // Level blocks for the fused sub-step wavefront (k_fused_cones): runs of consecutive levels of at most `wide` cells are
 // cut into blocks of up to lmax levels (fused wavefront: LF_FUSED_LEVELS, default 16; plain router calls, k_sweep_cones:
-// LF_ROUTE_LEVELS, default 64; 1 = off); a wider level is a block of its own.  A
-// block is cut into cones: chunks of its last level, as long as possible with no level of the cone wider than kBlock
+// LF_ROUTE_LEVELS, default 256; 1 = off); a wider level is a block of its own.  A
+// block is cut into cones: chunks of its last level, as long as possible with no level of the cone wider than cw
 // cells; a block whose thinnest possible cone (one cell of the last level) is still too wide somewhere loses levels
-// until it fits (one level always does).  Nothing is built when no block holds more than one level.
+// until it fits (one level always does).  Nothing is built, and the router's plan stays as it is, when no block holds
+// more than one level.
 static int build_level_blocks(lf_router *r, const lf_graph *g, bool for_route, int lmax_override = 0)
 {
     int lmax = for_route ? 256 : 16; // LF_ROUTE_LEVELS / LF_FUSED_LEVELS (measured: §4.1c / §4.3b of DESIGN.md)
@@ -461,61 +458,28 @@ static int build_level_blocks(lf_router *r, const lf_graph *g, bool for_route, i
     // of levels is what it costs, and 8 levels per block balance chain against launch count (model step with structures, ms:
     // 2.29 / 1.96 / 1.96 / 2.20 / 2.96 for 2 / 4 / 8 / 16 / 32 levels per block)
     if (!for_route && g->N <= 65536) lmax = 8;
-    if (const char *e = std::getenv(for_route ? "LF_ROUTE_LEVELS" : "LF_FUSED_LEVELS")) lmax = std::atoi(e);
-    if (lmax_override > 0) lmax = lmax_override;
-    lmax = lmax < 1 ? 1 : (lmax > (for_route ? 512 : 64) ? (for_route ? 512 : 64) : lmax);
-    int64_t wide = 262144;
-    if (const char *e = std::getenv("LF_FUSED_WIDE")) wide = std::atoll(e);
-    const int64_t NL = g->NL;
+    const lf_block_knobs knobs = lf_read_block_knobs(for_route, lmax, lmax_override);
     // (the fused cone kernels address a cell by a 32-bit byte offset into its arrays: below 2^29 cells; a larger graph keeps
     // the level-by-level wavefront)
-    if (lmax <= 1 || NL < 2 || g->N >= ((int64_t)1 << (for_route ? 31 : 29))) return LF_OK;
-    int cw = kBlock;
-    if (for_route) { // one wavefront per cone: no barrier between the levels (deep 10 000^2: 11.3 -> 10.1 ms per call)
-        cw = 64;
-        if (const char *e = std::getenv("LF_ROUTE_CONE_WIDTH")) cw = std::atoi(e) == 64 ? 64 : kBlock;
-    } else {
-        // fused wavefront: one wavefront per cone (the chain / supply kernel needs it; k_fused_cones itself measured the
-        // same at 64 and 256: DESIGN.md section 8b)
-        cw = 64;
-        if (const char *e = std::getenv("LF_FUSED_CONE_WIDTH")) cw = std::atoi(e) == 64 ? 64 : kBlock;
-    }
+    if (knobs.lmax <= 1 || g->NL < 2 || g->N >= ((int64_t)1 << (for_route ? 31 : 29))) return LF_OK;
+    // one wavefront per cone.  Plain calls: no barrier between the levels (deep 10 000^2: 11.3 -> 10.1 ms per call); fused
+    // wavefront: the chain / supply kernel needs it (k_fused_cones itself measured the same at 64 and 256: DESIGN.md
+    // section 8b)
+    int cw = 64;
+    if (const char *e = std::getenv(for_route ? "LF_ROUTE_CONE_WIDTH" : "LF_FUSED_CONE_WIDTH"))
+        cw = std::atoi(e) == 64 ? 64 : kBlock;
     lf_block_plan plan;
-    try {
+    LF_TRY(lf_build_blocks_guarded([&] {
         // every cell below the last level drains into the next level, so the upstream ranges tile the level before:
         // the first position draining at or behind `pos` is the first upstream position of `pos`
-        lf_build_level_blocks(g->level_start, 0, NL, lmax, wide, cw, [&](int64_t pos) { return (int64_t)g->ups_ptr[pos]; },
-                              plan);
-    } catch (const std::bad_alloc &) {
-        return lf_set_error(LF_E_INVALID, "out of host memory while building the level blocks");
-    }
-    const bool any = plan.any_multi;
-    std::vector<int> &level = plan.level, &row = plan.row, &cone = plan.cone, &off = plan.off;
-    if (!any || cone.size() >= ((size_t)1 << 31)) return LF_OK;
-    level.push_back((int)NL);
-    if (for_route) {
-        LF_TRY(r->rb_cone.upload(cone.data(), cone.size(), r->ctx->stream));
-        r->rb_level = level;
-        r->rb_row = row;
-        r->rb_off = off;
-        r->rb_lmax = lmax;
-        r->rb_cw = cw;
-        return LF_OK;
-    }
-    LF_TRY(r->fb_level_dev.upload(level.data(), level.size(), r->ctx->stream));
-    LF_TRY(r->fb_row_dev.upload(row.data(), row.size(), r->ctx->stream));
-    LF_TRY(r->fb_off_dev.upload(off.data(), off.size(), r->ctx->stream));
-    LF_TRY(r->fb_cone.upload(cone.data(), cone.size(), r->ctx->stream));
-    std::vector<int> lvl2blk((size_t)NL, 0);
-    for (size_t b = 0; b + 1 < level.size(); ++b)
-        for (int k = level[b]; k < level[b + 1]; ++k) lvl2blk[k] = (int)b;
-    LF_TRY(r->fb_lvl2blk_dev.upload(lvl2blk.data(), lvl2blk.size(), r->ctx->stream));
-    r->fb_lvl2blk = lvl2blk;
-    r->fb_level = level;
-    r->fb_row = row;
-    r->fb_off = off;
-    r->fb_lmax = lmax;
-    r->fb_cw = cw;
+        lf_build_level_blocks(g->level_start, 0, g->NL, knobs.lmax, knobs.wide, cw,
+                              [&](int64_t pos) { return (int64_t)g->ups_ptr[pos]; }, plan);
+        plan.finish(g->NL);
+        if (!for_route && !plan.empty()) plan.index_levels();
+    }));
+    if (plan.empty()) return LF_OK;
+    LF_TRY((for_route ? r->rplan_dev : r->fplan_dev).upload(plan, !for_route, r->ctx->stream));
+    (for_route ? r->rplan : r->fplan) = std::move(plan);
     return LF_OK;
 }
 
@@ -543,13 +507,13 @@ static int tune_route_blocks(lf_router *r, const lf_graph *g)
     if (std::getenv("LF_ROUTE_LEVELS")) return LF_OK;
     if (const char *e = std::getenv("LF_ROUTE_TUNE"))
         if (e[0] == '0') return LF_OK;
-    if (r->rb_lmax <= 1 || r->N < 1000000) return LF_OK;
+    if (r->rplan.empty() || r->N < 1000000) return LF_OK;
     int64_t st[6];
     LF_TRY(lf_router_route_plan_stats(r, st));
-    const double lane_use = st[3] > 0 ? (double)st[4] / ((double)r->rb_cw * (double)st[3]) : 1.0;
+    const double lane_use = st[3] > 0 ? (double)st[4] / ((double)r->rplan.cw * (double)st[3]) : 1.0;
     if (lane_use >= 0.4 || st[5] <= 1024) return LF_OK; // lanes busy, or few enough cones per launch to be chain-bound
     auto it = tuned.find(g->serial);
-    if (g->serial != 0 && it != tuned.end()) return it->second == r->rb_lmax ? LF_OK : build_level_blocks(r, g, true, it->second);
+    if (g->serial != 0 && it != tuned.end()) return it->second == r->rplan.lmax ? LF_OK : build_level_blocks(r, g, true, it->second);
     lf_dbuf<double> Q, q;
     LF_TRY(Q.alloc((size_t)r->N));
     LF_TRY(q.alloc((size_t)r->N));
@@ -557,11 +521,11 @@ static int tune_route_blocks(lf_router *r, const lf_graph *g)
     hipEvent_t e0, e1;
     LF_HIP(hipEventCreate(&e0));
     LF_HIP(hipEventCreate(&e1));
-    int best = r->rb_lmax, rc = LF_OK;
+    int best = r->rplan.lmax, rc = LF_OK;
     float best_ms = 1e30f;
     for (int lmax : {256, 128, 64, 32, 16}) {
-        if (lmax != r->rb_lmax) rc = build_level_blocks(r, g, true, lmax);
-        if (rc != LF_OK || r->rb_lmax != lmax) break; // (no multi-level block at this length: nothing shorter will have one)
+        if (lmax != r->rplan.lmax) rc = build_level_blocks(r, g, true, lmax);
+        if (rc != LF_OK || r->rplan.lmax != lmax) break; // (no multi-level block at this length: nothing shorter will have one)
         hipLaunchKernelGGL(k_fill_f64, dim3(blocks_for(r->N)), dim3(kBlock), 0, s, (long long)r->N, Q.p, 1.0);
         hipLaunchKernelGGL(k_fill_f64, dim3(blocks_for(r->N)), dim3(kBlock), 0, s, (long long)r->N, q.p, 1.0e-4);
         rc = route_device(r, Q.p, q.p, 0, true); // warm
@@ -580,7 +544,7 @@ static int tune_route_blocks(lf_router *r, const lf_graph *g)
     }
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
-    if (rc == LF_OK && r->rb_lmax != best) rc = build_level_blocks(r, g, true, best);
+    if (rc == LF_OK && r->rplan.lmax != best) rc = build_level_blocks(r, g, true, best);
     if (rc == LF_OK && g->serial != 0) tuned[g->serial] = best;
     return rc;
 }
@@ -797,19 +761,7 @@ int lf_router_last_launches(const lf_router *r, int64_t stats[4])
 int lf_router_route_plan_stats(const lf_router *r, int64_t out[6])
 {
     if (!r || !out) return lf_set_error(LF_E_INVALID, "null argument");
-    for (int i = 0; i < 6; ++i) out[i] = 0;
-    const int NB = r->rb_level.empty() ? 0 : (int)r->rb_level.size() - 1;
-    out[0] = NB;
-    for (int b = 0; b < NB; ++b) {
-        const int k0 = r->rb_level[b], nl = r->rb_level[b + 1] - k0;
-        if (nl < 2) continue;
-        const int64_t cones = r->rb_row[b + 1] - r->rb_row[b] - 1;
-        out[1] += 1;
-        out[2] += cones;
-        out[3] += cones * nl;
-        out[4] += r->h_level_start[k0 + nl] - r->h_level_start[k0];
-        out[5] = cones > out[5] ? cones : out[5];
-    }
+    r->rplan.stats(r->h_level_start, out);
     return LF_OK;
 }
 
@@ -888,7 +840,7 @@ int lf_accuflux_ordered_multi_device(lf_router *r, int nv, const double *const *
     LF_TRY(pick_count(nv, [&](auto nvc) {
         constexpr int NV = nvc;
         auto cones = [&](dim3 grid, const cone_plan_args &C, int64_t) {
-            if (r->rb_cw == 64)
+            if (r->rplan.cw == 64)
                 hipLaunchKernelGGL((k_accu_cones<NV, 64>), grid, dim3(64), 0, s, C, r->ups_ptr.p, M);
             else
                 hipLaunchKernelGGL((k_accu_cones<NV, kBlock>), grid, dim3(kBlock), 0, s, C, r->ups_ptr.p, M);
@@ -902,7 +854,7 @@ int lf_accuflux_ordered_multi_device(lf_router *r, int nv, const double *const *
             hipLaunchKernelGGL(k_accu_narrow<NV>, dim3(1), dim3(kNarrowBlock), 0, s, k0, k1, r->level_start.p, r->ups_ptr.p, M);
             return LF_OK;
         };
-        return route_schedule(*r, 0, (int)r->rb_level.size() - 1, r->schedule, r->rb_lmax > 1, c, cones, level, narrow);
+        return route_schedule(*r, 0, r->rplan.nblocks(), r->schedule, !r->rplan.empty(), c, cones, level, narrow);
     }));
     r->last_stats[0] = c.launches;
     r->last_stats[1] = r->last_stats[2] = 0;
@@ -1165,7 +1117,7 @@ int fused_impl(lf_router *r, const lf_substep_args *a, int nsteps, int64_t sidef
     fused_args F = fused_args_of(*r, *a, nsteps, msteps, sideflow_stride, side_mstride);
     F.linked = r->linked.p;
     F.level_nlinked = r->level_nlinked.p;
-    F.fb_lvl2blk = r->fb_lvl2blk_dev.p;
+    F.fb_lvl2blk = r->fplan_dev.lvl2blk.p;
     hipStream_t s = r->ctx->stream;
     // ---- structures: levels of the site cells; every cell feeding a site must sit on the site's own level ----------
     std::vector<int> lv_sorted;
@@ -1266,7 +1218,7 @@ int fused_impl(lf_router *r, const lf_substep_args *a, int nsteps, int64_t sidef
         }();
         const char *es = std::getenv("LF_FUSED_SPLIT");
         // (with structures in the loop: on a graph with their links; without them: on a graph without links)
-        const bool split_form = all35 && !F.inert && (in ? F.linked != nullptr : F.linked == nullptr) && r->fb_cw == 64 &&
+        const bool split_form = all35 && !F.inert && (in ? F.linked != nullptr : F.linked == nullptr) && r->fplan.cw == 64 &&
                                 n < ((int64_t)1 << 29) && (es ? es[0] != '0' : ncones <= (in ? split_max_struct : split_max));
         if (split_form)
             pick_flags(a->split, in, [&](auto sp, auto st) {
@@ -1274,7 +1226,7 @@ int fused_impl(lf_router *r, const lf_substep_args *a, int nsteps, int64_t sidef
             });
         else
             pick_flags(a->split, all35, [&](auto sp, auto a35) {
-                pick_flags(in, r->fb_cw == 64, [&](auto st, auto cw64) {
+                pick_flags(in, r->fplan.cw == 64, [&](auto st, auto cw64) {
                     constexpr int CW = decltype(cw64)::value ? 64 : kBlock;
                     hipLaunchKernelGGL((k_fused_cones<sp, a35, st, false, CW>), grid, dim3(CW), 0, s, F);
                 });
@@ -1287,8 +1239,8 @@ int fused_impl(lf_router *r, const lf_substep_args *a, int nsteps, int64_t sidef
     };
     // lakes and reservoirs of the blocks / levels [lo, hi]: sub-step t - block / level, before the cells of that block / level
     std::vector<int> site_blocks; // sorted blocks of the lakes and reservoirs
-    if (r->fb_lmax > 1)
-        for (int lv : lv_sorted) site_blocks.push_back(r->fb_lvl2blk[lv]);
+    if (!r->fplan.empty())
+        for (int lv : lv_sorted) site_blocks.push_back(r->fplan.lvl2blk[lv]);
     auto sites = [&](bool blocks, int lo, int hi) {
         const std::vector<int> &units = blocks ? site_blocks : lv_sorted;
         auto it = std::lower_bound(units.begin(), units.end(), lo);
@@ -1299,7 +1251,7 @@ int fused_impl(lf_router *r, const lf_substep_args *a, int nsteps, int64_t sidef
             hipLaunchKernelGGL(k_sites_wave, dim3(blocks_for(nsites)), dim3(kBlock), 0, s, F);
         ++launches;
     };
-    const int NB = r->fb_lmax > 1 ? (int)r->fb_level.size() - 1 : -1;
+    const int NB = r->fplan.empty() ? -1 : r->fplan.nblocks();
     LF_TRY(fused_wavefront<false>(*r, F, 0, (int)r->NL, 0, NB, !in && !F.linked, s, launches, cones, levels, sites));
     r->last_stats[0] = launches;
     r->last_stats[1] = launches;

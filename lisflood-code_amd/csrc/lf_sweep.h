@@ -1077,7 +1077,7 @@ struct launch_counts {
 
 // The launch schedule of a router call.  With level blocks -- use_blocks, the caller's condition,
 // and LF_ROUTE_CONES not 0 (read at every call: bench.py switches it for its A/B legs) -- the blocks [b0, b0 + nblocks) of
-// r's rb_* plan, each one launch:
+// r's route plan (r.rplan, its cone table in r.rplan_dev), each one launch:
 //   several levels  cones(grid, C, cells): one workgroup per cone of the block;
 //   one level       level(first, cells), none for an empty level;
 // otherwise the segments `segs`:
@@ -1092,13 +1092,13 @@ int route_schedule(const R &r, int b0, int nblocks, const std::vector<level_segm
     auto cells = [&](int k0, int k1) { return r.h_level_start[k1] - r.h_level_start[k0]; };
     if (use_blocks && !(e && e[0] == '0')) {
         for (int b = b0; b < b0 + nblocks; ++b) {
-            const int k0 = r.rb_level[b], nl = r.rb_level[b + 1] - k0;
+            const int k0 = r.rplan.level[b], nl = r.rplan.nlevels(b);
             if (nl > 1) {
                 cone_plan_args C;
-                C.cone = r.rb_cone.p + r.rb_off[b];
+                C.cone = r.rplan_dev.cone.p + r.rplan.off[b];
                 C.nl = nl;
                 C.n_cells = (int)r.N;
-                LF_TRY(cones(dim3((unsigned)(r.rb_row[b + 1] - r.rb_row[b] - 1)), C, cells(k0, k0 + nl)));
+                LF_TRY(cones(dim3((unsigned)r.rplan.ncones(b)), C, cells(k0, k0 + nl)));
                 ++n.narrow;
             } else {
                 if (cells(k0, k0 + 1) <= 0) continue;
