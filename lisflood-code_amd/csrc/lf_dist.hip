@@ -746,34 +746,14 @@ __global__ void __launch_bounds__(kBlock) k_pack2(int n0, int n1, const int *__r
     else if (i < n0 + n1)
         buf1[i - n0] = q[pos1[i - n0]];
 }
-__global__ void __launch_bounds__(kBlock) k_dgather(int n, const int *__restrict__ perm, const double *__restrict__ src,
-                                                    double *__restrict__ dst)
-{
-    const int p = blockIdx.x * kBlock + threadIdx.x;
-    if (p < n) dst[p] = src[perm[p]];
-}
-__global__ void __launch_bounds__(kBlock) k_dscatter(int n, const int *__restrict__ perm, const double *__restrict__ src,
-                                                     double *__restrict__ dst)
-{
-    const int p = blockIdx.x * kBlock + threadIdx.x;
-    if (p < n) dst[perm[p]] = src[p];
-}
 } // namespace
 
-struct lf_dist_router {
-    int device = 0;
-    lf_device_ctx *ctx = nullptr;
-    int64_t N = 0, state_size = 0;
-    int nphases = 1, kmax = 8;
-    double beta = 0, inv_beta = 0, b_minus_1 = 0, dx_scalar = 0, dt = 0;
-    bool has_floodplains = false, dx_per_pixel = false, fused = false;
-    lf_dbuf<unsigned int> derived_ok; // fused sub-steps: flags of k_check_derived (fused_args::recompute)
-    lf_dbuf<int32_t> perm, ups_ptr, ups_idx, ups_base, export_pos[2];
-    lf_dbuf<long long> level_start;
-    lf_dbuf<double> a1, a2, dx, constant, sendbuf[2];
+struct lf_dist_router : lf_router_core {
+    int64_t state_size = 0;
+    int nphases = 1;
+    lf_dbuf<int32_t> ups_idx, ups_base, export_pos[2];
+    lf_dbuf<double> sendbuf[2];
     lf_dbuf<lf_rec24> rec24_1, rec24_2; // the level kernel's static values as one record per cell and section (dist_level_statics)
-    bool statics_refused = false;
-    std::vector<int64_t> h_level_start;
     std::vector<std::vector<level_segment>> schedule; // per stage (2 * phase + part, see lf_dist_graph::crit)
     // halo exchange beside the bulk part of a phase: second stream + events (lf_dist_router_route)
     hipStream_t comm_stream = nullptr;
@@ -784,20 +764,13 @@ struct lf_dist_router {
     std::vector<int64_t> export_off[2], ghost_off[2];
     int64_t ghost_base[2] = {0, 0};
     int64_t last_launches = 0;
-    // fused sub-steps (see lf_dist_graph): fused upstream lists, slab slot of every cell, router-output parity buffers,
-    // the slabs [slot][sub-step] of both sections, sized for slab_steps sub-steps
+    // fused sub-steps (see lf_dist_graph): fused upstream lists, slab slot of every cell, the slabs [slot][sub-step] of
+    // both sections, sized for slab_steps sub-steps
     lf_dbuf<int32_t> ups_idx_f, out_slot;
-    lf_dbuf<double> fused_qr1, fused_qr2, slab1, slab2;
+    lf_dbuf<double> slab1, slab2;
     int64_t n_slots = 0, slab_steps = 0, slot_export[2] = {0, 0}, slot_ghost[2] = {0, 0};
-    lf_dbuf<double> fused_hist1, fused_hist2; // [nsteps][N] router outputs of every sub-step (k_fused_level_steps<DIST>)
-    size_t fused_hist_refused = SIZE_MAX;     // smallest history size that did not fit its budget (lf_history_ensure)
     std::vector<int32_t> phase_level; // [nphases + 1] first launch unit of every phase
-    // level blocks + cones of every phase (lf_dist_graph::fplan; empty: one launch per unit)
-    lf_block_plan fplan;
-    lf_block_plan_dev fplan_dev;
-    // level blocks + cones of every stage for single router calls (lf_dist_graph::rplan; empty: the segment schedule)
-    lf_block_plan rplan;
-    lf_block_plan_dev rplan_dev;
+    // (the plans of lf_router_core are lf_dist_graph's: fplan holds the blocks of every phase, rplan those of every stage)
 };
 
 namespace {
@@ -807,16 +780,10 @@ namespace {
 // LF_LEVEL_STATICS=0, a graph of 2^28 cells or more, or no memory for them.
 const lf_rec24 *dist_level_statics(lf_dist_router *r, const sweep_args &A)
 {
-    if (!r->fused || !r->dx_per_pixel || r->statics_refused || r->N <= 0 || r->N >= ((int64_t)1 << 28) ||
-        !level_statics_enabled())
-        return nullptr;
+    if (r->N >= ((int64_t)1 << 28) || !level_records_wanted(*r)) return nullptr;
     lf_dbuf<lf_rec24> &buf = (A.a == r->a1.p) ? r->rec24_1 : r->rec24_2;
     if (!buf.p) {
-        if (r->ups_idx.n >= ((size_t)1 << 28) || buf.alloc((size_t)r->N) != LF_OK) {
-            r->statics_refused = true;
-            (void)hipGetLastError();
-            return nullptr;
-        }
+        if (!level_records_alloc(*r, buf, r->ups_idx.n < ((size_t)1 << 28))) return nullptr;
         hipLaunchKernelGGL(k_static_records_indexed, dim3((unsigned)((r->N + kLevelBlock - 1) / kLevelBlock)), dim3(kLevelBlock), 0,
                            r->ctx->stream, (long long)r->N, A.a, (const double *)r->dx.p, (const int *)r->ups_ptr.p,
                            (const int *)r->ups_base.p, buf.p);
@@ -908,31 +875,14 @@ int lf_dist_router_create(const lf_dist_graph *g, const double *alpha, double be
     lf_device_ctx *ctx;
     LF_TRY(lf_ctx(device, &ctx));
     lf_dist_router *r = new lf_dist_router();
-    r->device = device;
-    r->ctx = ctx;
-    r->N = g->N;
     r->state_size = lf_dist_graph_state_size(g);
     r->nphases = g->nphases;
-    r->kmax = std::min(8, g->K);
-    r->beta = beta;
-    r->inv_beta = 1 / beta;
-    r->b_minus_1 = beta - 1;
-    r->dx_scalar = dx_scalar;
-    r->dt = dt;
-    r->dx_per_pixel = dx != nullptr;
-    r->has_floodplains = alpha_floodplains != nullptr;
-    r->fused = router_fused(beta);
-    const int64_t n = g->N;
-    int rc = upload_sweep_statics(*r, g->perm, alpha, alpha_floodplains, dx, nullptr);
-    if (rc == LF_OK) rc = r->perm.upload(g->perm.data(), n);
-    if (rc == LF_OK) rc = r->ups_ptr.upload(g->ups_ptr.data(), n + 1);
+    // (uploads on the null stream; a sweep looks at no more than eight upstream cells)
+    int rc = router_core_init(*r, device, ctx, g->N, std::min(8, g->K), beta, dx_scalar, dt, g->perm, g->ups_ptr, alpha,
+                              alpha_floodplains, dx, nullptr);
     if (rc == LF_OK) rc = r->ups_idx.upload(g->ups_idx.data(), g->ups_idx.size());
     if (rc == LF_OK) rc = r->ups_base.upload(g->ups_base.data(), g->ups_base.size());
-    if (rc == LF_OK) {
-        std::vector<long long> ls(g->level_start.begin(), g->level_start.end());
-        rc = r->level_start.upload(ls.data(), ls.size());
-    }
-    if (rc == LF_OK && !r->fused) rc = r->constant.alloc(n);
+    if (rc == LF_OK) rc = router_core_init_levels(*r, g->level_start, nullptr);
     for (int side = 0; side < 2 && rc == LF_OK; ++side) {
         rc = r->export_pos[side].upload(g->export_pos[side].data(), g->export_pos[side].size());
         if (rc == LF_OK) rc = r->sendbuf[side].alloc(g->export_pos[side].size());
@@ -954,7 +904,6 @@ int lf_dist_router_create(const lf_dist_graph *g, const double *alpha, double be
         r->slot_ghost[side] = g->slot_ghost[side];
     }
     r->phase_level = g->phase_level;
-    r->h_level_start = g->level_start;
     for (int j = 0; j < 2 * g->nphases; ++j) r->schedule.push_back(level_segments(g->level_start, g->stage_level[j], g->stage_level[j + 1]));
     *out = r;
     return LF_OK;
@@ -983,24 +932,12 @@ int64_t lf_dist_router_last_launches(const lf_dist_router *r) { return r ? r->la
 int lf_dist_router_to_engine_order(lf_dist_router *r, const double *src_pix_dev, double *dst_ord_dev)
 {
     if (!r || !src_pix_dev || !dst_ord_dev) return lf_set_error(LF_E_INVALID, "null argument");
-    LF_HIP(hipSetDevice(r->device));
-    const int n = (int)r->N;
-    if (n > 0)
-        hipLaunchKernelGGL(k_dgather, dim3(blocks_for(n)), dim3(kBlock), 0, r->ctx->stream, n, r->perm.p, src_pix_dev,
-                           dst_ord_dev);
-    LF_HIP(hipGetLastError());
-    return LF_OK;
+    return core_to_engine_order(*r, src_pix_dev, dst_ord_dev);
 }
 int lf_dist_router_from_engine_order(lf_dist_router *r, const double *src_ord_dev, double *dst_pix_dev)
 {
     if (!r || !src_ord_dev || !dst_pix_dev) return lf_set_error(LF_E_INVALID, "null argument");
-    LF_HIP(hipSetDevice(r->device));
-    const int n = (int)r->N;
-    if (n > 0)
-        hipLaunchKernelGGL(k_dscatter, dim3(blocks_for(n)), dim3(kBlock), 0, r->ctx->stream, n, r->perm.p, src_ord_dev,
-                           dst_pix_dev);
-    LF_HIP(hipGetLastError());
-    return LF_OK;
+    return core_from_engine_order(*r, src_ord_dev, dst_pix_dev);
 }
 
 // sweep of the local cells of one phase (state vector q_ord_dev has lf_dist_router_state_size entries)
@@ -1045,6 +982,14 @@ int lf_dist_router_recv_slots(const lf_dist_router *r, int round, int64_t slot[2
     return LF_OK;
 }
 
+// does round j carry halo traffic: cells to send or to receive, on either side?
+static bool round_has_traffic(const lf_dist_router *r, int j)
+{
+    for (int side = 0; side < 2; ++side)
+        if (r->export_off[side][j + 1] > r->export_off[side][j] || r->ghost_off[side][j + 1] > r->ghost_off[side][j]) return true;
+    return false;
+}
+
 // pack + RCCL Send/Recv with the rank above (rank_top) and below (rank_bottom); -1 = no neighbour
 static int dist_exchange(lf_dist_router *r, lf_comm *comm, double *q_ord_dev, int round, int rank_top, int rank_bottom,
                          hipStream_t s)
@@ -1053,14 +998,12 @@ static int dist_exchange(lf_dist_router *r, lf_comm *comm, double *q_ord_dev, in
     LF_HIP(hipSetDevice(r->device));
     LF_TRY(dist_pack(r, q_ord_dev, round, s));
     const int peer[2] = {rank_top, rank_bottom};
-    bool any = false;
     for (int side = 0; side < 2; ++side) {
         const int64_t ns = r->export_off[side][round + 1] - r->export_off[side][round];
         const int64_t nr = r->ghost_off[side][round + 1] - r->ghost_off[side][round];
         if ((ns > 0 || nr > 0) && peer[side] < 0) return lf_set_error(LF_E_INVALID, "halo traffic without a neighbour rank");
-        any = any || ns > 0 || nr > 0;
     }
-    if (!any) return LF_OK;
+    if (!round_has_traffic(r, round)) return LF_OK;
     LF_NCCL(g_rccl.GroupStart());
     for (int side = 0; side < 2; ++side) {
         const int64_t ns = r->export_off[side][round + 1] - r->export_off[side][round];
@@ -1103,16 +1046,11 @@ int lf_dist_router_route(lf_dist_router *r, lf_comm *comm, double *q_ord_dev, co
     // RCCL Send/Recv) then goes to the communication stream and runs BESIDE the bulk part of the phase; phase j + 1 waits
     // for it.  The packs read export cells (part 0, final), the receives write ghost slots of round j that only later
     // phases read: no buffer is touched by both streams at once.
-    const char *e = std::getenv("LF_DIST_OVERLAP");
-    const bool overlap = comm && !(e && e[0] == '0');
+    const bool overlap = comm && dist_overlap_enabled();
     if (overlap) LF_TRY(ensure_comm_stream(r));
     hipStream_t s = r->ctx->stream;
     for (int j = 0; j < r->nphases; ++j) {
-        bool any = false;
-        if (j + 1 < r->nphases)
-            for (int side = 0; side < 2; ++side)
-                any = any || r->export_off[side][j + 1] > r->export_off[side][j] ||
-                      r->ghost_off[side][j + 1] > r->ghost_off[side][j];
+        const bool any = j + 1 < r->nphases && round_has_traffic(r, j);
         if (any && !comm) return lf_set_error(LF_E_COMM, "halo exchange needed but no communicator given");
         if (!any) {
             LF_TRY(dist_compute_phase(r, q_ord_dev, lat_ord_dev, section, j));
@@ -1159,8 +1097,7 @@ int lf_dist_router_route_many(lf_dist_router *r, lf_comm *comm, double *q_ord_de
     if (!r || !q_ord_dev || !lat_ord_dev || ncalls < 0) return lf_set_error(LF_E_INVALID, "bad argument");
     for (int s = 0; s < ncalls; ++s)
         if (!lat_ord_dev[s]) return lf_set_error(LF_E_INVALID, "null argument");
-    const char *e = std::getenv("LF_DIST_OVERLAP");
-    const bool pipelined = comm && r->fused && r->nphases > 1 && ncalls > 1 && !(e && e[0] == '0');
+    const bool pipelined = comm && r->fused && r->nphases > 1 && ncalls > 1 && dist_overlap_enabled();
     if (!pipelined) {
         for (int s = 0; s < ncalls; ++s)
             LF_TRY(lf_dist_router_route(r, comm, q_ord_dev, lat_ord_dev[s], section, rank_top, rank_bottom));
@@ -1184,12 +1121,7 @@ int lf_dist_router_route_many(lf_dist_router *r, lf_comm *comm, double *q_ord_de
     hipStream_t s0 = r->ctx->stream;
     double *B[2] = {q_ord_dev, r->pp_state.p};
     r->last_launches = 0;
-    auto traffic = [&](int j) {
-        if (j + 1 >= P) return false;
-        for (int side = 0; side < 2; ++side)
-            if (r->export_off[side][j + 1] > r->export_off[side][j] || r->ghost_off[side][j + 1] > r->ghost_off[side][j]) return true;
-        return false;
-    };
+    auto traffic = [&](int j) { return j + 1 < P && round_has_traffic(r, j); };
     // call c: in = B[c & 1], out = B[(c + 1) & 1]
     auto part = [&](int c, int j, int pt) {
         return dist_compute_phase(r, B[(c + 1) & 1], lat_ord_dev[c], section, j, pt, B[c & 1]);
@@ -1394,6 +1326,20 @@ int lf_dist_fused_exchange(lf_dist_router *r, lf_comm *comm, int round, int spli
     return LF_OK;
 }
 
+// (shared tail of the two calls below) slabs and flags for nsteps sub-steps, msteps per model step, then phase by phase:
+// the wavefront of the phase and the exchange of its slabs
+static int dist_fused_run(lf_dist_router *r, lf_comm *comm, const lf_substep_args *a, int nsteps, int64_t sideflow_stride,
+                          int msteps, int64_t side_mstride, int rank_top, int rank_bottom)
+{
+    LF_TRY(dist_fused_prepare(r, a, nsteps));
+    r->last_launches = 0;
+    for (int j = 0; j < r->nphases; ++j) {
+        LF_TRY(dist_fused_phase(r, a, nsteps, sideflow_stride, j, msteps, side_mstride));
+        if (j + 1 < r->nphases) LF_TRY(lf_dist_fused_exchange(r, comm, j, a->split, rank_top, rank_bottom));
+    }
+    return LF_OK;
+}
+
 // Several MODEL steps per call on the partition (lf_routing_model_steps_fused on the whole raster, bit for bit): every phase
 // runs the sub-steps of ALL n_model_steps model steps as one wavefront and hands over the slabs of all of them in ONE halo
 // block -- the pipeline fill of a phase and the exchange round are paid once per call instead of once per model step, which
@@ -1421,14 +1367,8 @@ int lf_dist_routing_model_steps_fused(lf_dist_router *r, lf_comm *comm, const lf
 {
     if (!a) return lf_set_error(LF_E_INVALID, "null argument");
     LF_TRY(check_model_steps(r, steps_per_model_step, n_model_steps, sideflow_model_stride));
-    const int nsteps = steps_per_model_step * n_model_steps;
-    LF_TRY(dist_fused_prepare(r, a, nsteps));
-    r->last_launches = 0;
-    for (int j = 0; j < r->nphases; ++j) {
-        LF_TRY(dist_fused_phase(r, a, nsteps, 0, j, steps_per_model_step, sideflow_model_stride));
-        if (j + 1 < r->nphases) LF_TRY(lf_dist_fused_exchange(r, comm, j, a->split, rank_top, rank_bottom));
-    }
-    return LF_OK;
+    return dist_fused_run(r, comm, a, steps_per_model_step * n_model_steps, 0, steps_per_model_step, sideflow_model_stride,
+                          rank_top, rank_bottom);
 }
 
 // nsteps x routing.dynamic() on the partition (= lf_routing_substeps_fused on the whole raster, bit for bit): phase by
@@ -1439,13 +1379,7 @@ int lf_dist_routing_model_steps_fused(lf_dist_router *r, lf_comm *comm, const lf
 int lf_dist_routing_substeps_fused(lf_dist_router *r, lf_comm *comm, const lf_substep_args *a, int nsteps,
                                    int64_t sideflow_stride, int rank_top, int rank_bottom)
 {
-    LF_TRY(dist_fused_prepare(r, a, nsteps));
-    r->last_launches = 0;
-    for (int j = 0; j < r->nphases; ++j) {
-        LF_TRY(dist_fused_phase(r, a, nsteps, sideflow_stride, j));
-        if (j + 1 < r->nphases) LF_TRY(lf_dist_fused_exchange(r, comm, j, a->split, rank_top, rank_bottom));
-    }
-    return LF_OK;
+    return dist_fused_run(r, comm, a, nsteps, sideflow_stride, 0, 0, rank_top, rank_bottom);
 }
 
 } // extern "C"

@@ -1719,14 +1719,14 @@ __global__ void __launch_bounds__(64 * (1 + KC)) k_fused_cones_split(fused_args 
 
 // ================================================================================================
 // Host side: the launch schedule of the wavefront, shared by the single domain (lf_router.hip: all levels) and the row-block
-// partition (lf_dist.hip: the levels and level blocks of one phase).  R is lf_router or lf_dist_router, whose members used
-// here have the same names and meanings.
+// partition (lf_dist.hip: the levels and level blocks of one phase), on the part the two routers share (lf_router_core,
+// lf_sweep.h).
 // ================================================================================================
 
 // fused_args of nsteps sub-steps (msteps per model step) from the router's statics; the wave fields are the schedule's,
 // the rest (structures, slabs, recompute flag, ...) stays zero for the caller
-template <class R>
-fused_args fused_args_of(const R &r, const lf_substep_args &a, int nsteps, int msteps, int64_t side_stride, int64_t side_mstride)
+inline fused_args fused_args_of(const lf_router_core &r, const lf_substep_args &a, int nsteps, int msteps, int64_t side_stride,
+                                int64_t side_mstride)
 {
     fused_args F;
     std::memset(&F, 0, sizeof(F));
@@ -1761,8 +1761,7 @@ inline bool fused_recompute()
 }
 
 // ... otherwise k_check_derived over the router's cells sets the flags in r.derived_ok
-template <class R>
-int fused_check_derived(R &r, const lf_substep_args &a, hipStream_t s)
+inline int fused_check_derived(lf_router_core &r, const lf_substep_args &a, hipStream_t s)
 {
     if (!r.derived_ok.p) LF_TRY(r.derived_ok.alloc(1));
     LF_HIP(hipMemsetD32Async((hipDeviceptr_t)r.derived_ok.p, 3, 1, s));
@@ -1782,8 +1781,8 @@ int fused_check_derived(R &r, const lf_substep_args &a, hipStream_t s)
 //   levels       per wave time t: levels(grid), level t - s for sub-step s.
 // sites(blocks, lo, hi) runs first at every wave time t, with the window [lo, hi] of the level blocks (blocks = true) or
 // levels in flight, counted from b0 / level0.
-template <bool DIST, class R, class Cones, class Levels, class Sites>
-int fused_wavefront(R &r, fused_args &F, int level0, int nlevels, int b0, int nblocks, bool time_major, hipStream_t s,
+template <bool DIST, class Cones, class Levels, class Sites>
+int fused_wavefront(lf_router_core &r, fused_args &F, int level0, int nlevels, int b0, int nblocks, bool time_major, hipStream_t s,
                     int64_t &launches, Cones &&cones, Levels &&levels, Sites &&sites)
 {
     const int nsteps = F.nsteps;

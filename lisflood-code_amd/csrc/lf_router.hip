@@ -30,13 +30,6 @@
 
 namespace {
 
-__global__ void __launch_bounds__(kBlock) k_gather(int n, const int *__restrict__ perm, const double *__restrict__ src_pix,
-                                                   double *__restrict__ dst_ord)
-{
-    const int p = blockIdx.x * kBlock + threadIdx.x;
-    if (p < n) dst_ord[p] = src_pix[perm[p]];
-}
-
 // out[pixel(p)] = sum of w over the upstream cells of p, ascending pixel id (np.bincount order)
 // (`linked`: zero-length structure links of lf_graph_create_ex sit behind the last range of a level -- skipped)
 __global__ void __launch_bounds__(kBlock) k_upstream_sum(int n, const int *__restrict__ perm,
@@ -168,13 +161,6 @@ __global__ void __launch_bounds__(CW) k_accu_cones(cone_plan_args C, const int *
     }
 }
 
-__global__ void __launch_bounds__(kBlock) k_scatter(int n, const int *__restrict__ perm, const double *__restrict__ src_ord,
-                                                    double *__restrict__ dst_pix)
-{
-    const int p = blockIdx.x * kBlock + threadIdx.x;
-    if (p < n) dst_pix[perm[p]] = src_ord[p];
-}
-
 __global__ void __launch_bounds__(kBlock) k_count_nonfinite(long long n, const double *__restrict__ x,
                                                             unsigned long long *count)
 {
@@ -187,21 +173,9 @@ __global__ void __launch_bounds__(kBlock) k_count_nonfinite(long long n, const d
 
 } // namespace
 
-struct lf_router {
-    int device = 0;
-    lf_device_ctx *ctx = nullptr;
-    int64_t N = 0, NL = 0;
-    double beta = 0, inv_beta = 0, b_minus_1 = 0, dx_scalar = 0, dt = 0;
-    bool has_floodplains = false, dx_per_pixel = false;
-    lf_dbuf<unsigned int> derived_ok; // fused sub-steps: flag of k_check_derived (fused_args::recompute)
-    int kmax = 8;
-    bool fused = false; // beta == 3/5: prep fused into the sweep, polynomial closure solve (lf_math.h)
-    lf_dbuf<int32_t> perm, ups_ptr;
-
-    lf_dbuf<long long> level_start;
-    lf_dbuf<double> a1, a2, dx, constant, qord, io_q, io_lat, tmp_ord, fused_qr1, fused_qr2;
-    lf_dbuf<double> fused_hist1, fused_hist2; // [nsteps][N] router outputs of every sub-step (k_fused_level_steps)
-    size_t fused_hist_refused = SIZE_MAX;     // smallest history size that did not fit its budget (lf_history_ensure)
+struct lf_router : lf_router_core {
+    int64_t NL = 0;
+    lf_dbuf<double> qord, io_q, io_lat, tmp_ord;
     lf_dbuf<unsigned long long> counter;
     lf_dbuf<uint8_t> linked; // zero-length structure links (lf_graph_create_ex); null without them
     lf_dbuf<int> level_nlinked; // ... and how many of them are parked at the end of every level (k_fused_cones_split)
@@ -215,21 +189,11 @@ struct lf_router {
     std::vector<int> site_level_sorted;
     const void *site_key[4] = {nullptr, nullptr, nullptr, nullptr}; // the site lists those levels were checked for
     int64_t site_cnt[2] = {-1, -1};
-    std::vector<int64_t> h_level_start;
     std::vector<level_segment> schedule; // launches of a call without level blocks (level_segments)
     uint64_t graph_serial = 0; // lf_graph::serial of the graph the router was built on: same object <=> same plan
-    // level blocks and cones (lf_blocks.h, build_level_blocks) of the fused sub-step wavefront, with lvl2blk for the
-    // sites of the structures variant; empty: the level-by-level wavefront
-    lf_block_plan fplan;
-    lf_block_plan_dev fplan_dev;
-    // the same with longer blocks for plain router calls (k_sweep_cones: no sub-step dimension to fill the machine with,
-    // so fewer, longer launches pay); empty: the segment schedule
-    lf_block_plan rplan;
-    lf_block_plan_dev rplan_dev;
-    // the static vectors of a cell as one record per section, for the wide levels of ordered beta = 3/5 calls (k_level<.., STATICS>):
-    // built on the first such call; statics_refused: the allocation failed once, the separate streams stay
-    lf_dbuf<double2> adx1, adx2;
-    bool statics_refused = false;
+    // (the fused plan of lf_router_core, fplan, is build_level_blocks' and carries lvl2blk for the sites of the structures
+    // variant; rplan feeds k_sweep_cones)
+    lf_dbuf<double2> adx1, adx2; // the (a, dx) records of k_level<.., STATICS = 1> per section (level_statics)
     int64_t last_stats[4] = {0, 0, 0, 0};
     // profiling
     bool profile = false;
@@ -295,14 +259,10 @@ namespace {
 // sweep then has one static load anyway), LF_LEVEL_STATICS=0 or no memory for them (16 bytes per cell and section).
 const double2 *level_statics(lf_router *r, const sweep_args &A)
 {
-    if (!r->fused || !r->dx_per_pixel || r->statics_refused || r->N <= 0 || !level_statics_enabled()) return nullptr;
+    if (!level_records_wanted(*r)) return nullptr;
     lf_dbuf<double2> &buf = (A.a == r->a1.p) ? r->adx1 : r->adx2;
     if (!buf.p) {
-        if (buf.alloc((size_t)r->N) != LF_OK) {
-            r->statics_refused = true;
-            (void)hipGetLastError();
-            return nullptr;
-        }
+        if (!level_records_alloc(*r, buf)) return nullptr;
         hipLaunchKernelGGL(k_static_records, dim3((unsigned)((r->N + kLevelBlock - 1) / kLevelBlock)), dim3(kLevelBlock), 0, r->ctx->stream,
                            (long long)r->N, A.a, (const double *)r->dx.p, buf.p);
     }
@@ -558,26 +518,12 @@ int lf_router_create(const lf_graph *g, const double *alpha, double beta, const 
     lf_device_ctx *ctx;
     LF_TRY(lf_ctx(device, &ctx));
     lf_router *r = new lf_router();
-    r->device = device;
-    r->ctx = ctx;
-    r->N = g->N;
     r->NL = g->NL;
     r->graph_serial = g->serial; // routers swept together (cone plan and upstream ranges of router 0) must share the graph
-    r->kmax = g->K;
-    r->beta = beta;
-    r->inv_beta = 1 / beta;      // kinematic_wave_parallel.py:125
-    r->b_minus_1 = beta - 1;     // :126
-    r->dx_scalar = dx_scalar;
-    r->dt = dt;
-    r->dx_per_pixel = dx != nullptr;
-    r->has_floodplains = alpha_floodplains != nullptr;
-    r->fused = router_fused(beta);
     const int64_t n = g->N;
     const std::vector<int32_t> &g_perm = g->perm;
-    const std::vector<int32_t> &g_ups_ptr = g->ups_ptr;
-    int rc = upload_sweep_statics(*r, g_perm, alpha, alpha_floodplains, dx, ctx->stream);
-    if (rc == LF_OK) rc = r->perm.upload(g_perm.data(), n, ctx->stream);
-    if (rc == LF_OK) rc = r->ups_ptr.upload(g_ups_ptr.data(), n + 1, ctx->stream);
+    int rc = router_core_init(*r, device, ctx, n, g->K, beta, dx_scalar, dt, g_perm, g->ups_ptr, alpha, alpha_floodplains, dx,
+                              ctx->stream);
     if (rc == LF_OK && g->has_links) rc = r->linked.upload(g->linked.data(), n, ctx->stream);
     if (rc == LF_OK && g->has_links) {
         std::vector<int> parked((size_t)g->NL, 0);
@@ -596,18 +542,13 @@ int lf_router_create(const lf_graph *g, const double *alpha, double beta, const 
         }
         if (r->n_isolated > 0) rc = r->isolated.upload(iso.data(), n, ctx->stream);
     }
-    if (rc == LF_OK) {
-        std::vector<long long> ls(g->level_start.begin(), g->level_start.end());
-        rc = r->level_start.upload(ls.data(), ls.size(), ctx->stream);
-    }
-    if (rc == LF_OK && !r->fused) rc = r->constant.alloc(n);
+    if (rc == LF_OK) rc = router_core_init_levels(*r, g->level_start, ctx->stream);
     if (rc == LF_OK) rc = r->qord.alloc(n);
     if (rc == LF_OK) rc = r->counter.alloc(1);
     if (rc != LF_OK) {
         delete r;
         return rc;
     }
-    r->h_level_start = g->level_start;
     r->schedule = level_segments(g->level_start, 0, g->NL);
     // (zero-length structure links need nothing special: such cells sit at the end of their level, inside the upstream
     // range of the LAST cell of the next level -- which adds their 0.0 -- and so inside the last cone of a block)
@@ -688,25 +629,13 @@ int lf_gather_device(int device, int64_t n, const int32_t *index_dev, const doub
 int lf_router_to_engine_order(lf_router *r, const double *src_pix_dev, double *dst_ord_dev)
 {
     if (!r || !src_pix_dev || !dst_ord_dev) return lf_set_error(LF_E_INVALID, "null argument");
-    LF_HIP(hipSetDevice(r->device));
-    const int n = (int)r->N;
-    if (n > 0)
-        hipLaunchKernelGGL(k_gather, dim3(blocks_for(n)), dim3(kBlock), 0, r->ctx->stream, n, r->perm.p, src_pix_dev,
-                           dst_ord_dev);
-    LF_HIP(hipGetLastError());
-    return LF_OK;
+    return core_to_engine_order(*r, src_pix_dev, dst_ord_dev);
 }
 
 int lf_router_from_engine_order(lf_router *r, const double *src_ord_dev, double *dst_pix_dev)
 {
     if (!r || !src_ord_dev || !dst_pix_dev) return lf_set_error(LF_E_INVALID, "null argument");
-    LF_HIP(hipSetDevice(r->device));
-    const int n = (int)r->N;
-    if (n > 0)
-        hipLaunchKernelGGL(k_scatter, dim3(blocks_for(n)), dim3(kBlock), 0, r->ctx->stream, n, r->perm.p, src_ord_dev,
-                           dst_pix_dev);
-    LF_HIP(hipGetLastError());
-    return LF_OK;
+    return core_from_engine_order(*r, src_ord_dev, dst_pix_dev);
 }
 
 int lf_router_route_host(lf_router *r, double *discharge_host, const double *lateral_host, int section)

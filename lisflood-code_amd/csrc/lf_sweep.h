@@ -5,6 +5,7 @@
 
 #include <type_traits>
 
+#include "lf_blocks.h"
 #include "lf_common.h"
 #include "lf_math.h"
 
@@ -962,10 +963,73 @@ __global__ void __launch_bounds__(kNarrowBlock) k_levels_narrow(int k0, int k1, 
 }
 
 // ================================================================================================
-// Host side: the setup and the launch schedule of a plain router call, shared by the single domain (lf_router.hip) and the
-// row-block partition (lf_dist.hip).  R is lf_router or lf_dist_router, whose members used here have the same names and
-// meanings.
+// Host side: what the single domain's router (lf_router.hip: lf_router) and the row-block partition's (lf_dist.hip:
+// lf_dist_router) have in common -- lf_router_core, its setup and the launch schedule of a plain router call.
 // ================================================================================================
+
+// The part of a router that both kinds share; lf_router and lf_dist_router derive from it and add what is theirs.
+struct lf_router_core {
+    int device = 0;
+    lf_device_ctx *ctx = nullptr;
+    int64_t N = 0;
+    int kmax = 8;
+    double beta = 0, inv_beta = 0, b_minus_1 = 0, dx_scalar = 0, dt = 0;
+    bool has_floodplains = false, dx_per_pixel = false;
+    bool fused = false; // beta == 3/5: prep fused into the sweep, polynomial closure solve (lf_math.h)
+    lf_dbuf<unsigned int> derived_ok; // fused sub-steps: flags of k_check_derived (fused_args::recompute)
+    lf_dbuf<int32_t> perm, ups_ptr;
+    lf_dbuf<long long> level_start;
+    lf_dbuf<double> a1, a2, dx, constant;
+    lf_dbuf<double> fused_qr1, fused_qr2;     // fused sub-steps: router outputs by sub-step parity (fused_args::qr1 / qr2)
+    lf_dbuf<double> fused_hist1, fused_hist2; // [nsteps][N] router outputs of every sub-step (k_fused_level_steps)
+    size_t fused_hist_refused = SIZE_MAX;     // smallest history size that did not fit its budget (lf_history_ensure)
+    std::vector<int64_t> h_level_start;
+    // level blocks and cones (lf_blocks.h) of the fused sub-step wavefront; empty: the level-by-level wavefront
+    lf_block_plan fplan;
+    lf_block_plan_dev fplan_dev;
+    // the same for plain router calls (longer blocks: no sub-step dimension to fill the machine with, so fewer, longer
+    // launches pay); empty: the segment schedule
+    lf_block_plan rplan;
+    lf_block_plan_dev rplan_dev;
+    // the static vectors of a cell as one record per section for the wide levels of ordered beta = 3/5 calls (k_level<..,
+    // STATICS>) are built on the first such call; statics_refused: the allocation failed once, the separate streams stay
+    bool statics_refused = false;
+};
+
+// position <-> pixel order of a vector through perm (dst_ord[p] = src_pix[perm[p]] and back)
+__global__ void __launch_bounds__(kBlock) k_gather(int n, const int *__restrict__ perm, const double *__restrict__ src_pix,
+                                                   double *__restrict__ dst_ord)
+{
+    const int p = blockIdx.x * kBlock + threadIdx.x;
+    if (p < n) dst_ord[p] = src_pix[perm[p]];
+}
+
+__global__ void __launch_bounds__(kBlock) k_scatter(int n, const int *__restrict__ perm, const double *__restrict__ src_ord,
+                                                    double *__restrict__ dst_pix)
+{
+    const int p = blockIdx.x * kBlock + threadIdx.x;
+    if (p < n) dst_pix[perm[p]] = src_ord[p];
+}
+
+// a vector of r's N cells from pixel order into engine (sweep) order and back, on r's stream
+inline int core_to_engine_order(lf_router_core &r, const double *src_pix_dev, double *dst_ord_dev)
+{
+    LF_HIP(hipSetDevice(r.device));
+    const int n = (int)r.N;
+    if (n > 0)
+        hipLaunchKernelGGL(k_gather, dim3(blocks_for(n)), dim3(kBlock), 0, r.ctx->stream, n, r.perm.p, src_pix_dev, dst_ord_dev);
+    LF_HIP(hipGetLastError());
+    return LF_OK;
+}
+inline int core_from_engine_order(lf_router_core &r, const double *src_ord_dev, double *dst_pix_dev)
+{
+    LF_HIP(hipSetDevice(r.device));
+    const int n = (int)r.N;
+    if (n > 0)
+        hipLaunchKernelGGL(k_scatter, dim3(blocks_for(n)), dim3(kBlock), 0, r.ctx->stream, n, r.perm.p, src_ord_dev, dst_pix_dev);
+    LF_HIP(hipGetLastError());
+    return LF_OK;
+}
 
 // The instantiation of a kernel for two run-time flags: fn(std::bool_constant<a>, std::bool_constant<b>)
 template <class Fn>
@@ -1007,8 +1071,33 @@ inline bool level_statics_enabled()
     return !(e && e[0] == '0');
 }
 
-template <class R>
-int check_section(const R &r, int section)
+// LF_DIST_OVERLAP=0: the row-block partition runs its halo rounds on the compute stream, not beside the bulk of a phase
+// (A/B switch, read at every call)
+inline bool dist_overlap_enabled()
+{
+    const char *e = std::getenv("LF_DIST_OVERLAP");
+    return !(e && e[0] == '0');
+}
+
+// Do the wide levels of r's ordered calls read one record per cell (lf_router_core::statics_refused)?  Not with a scalar
+// dx (the sweep then has one static load anyway), off the beta = 3/5 path, after a refusal or with LF_LEVEL_STATICS=0.
+inline bool level_records_wanted(const lf_router_core &r)
+{
+    return r.fused && r.dx_per_pixel && !r.statics_refused && r.N > 0 && level_statics_enabled();
+}
+
+// The records of one section on their first use: `buf` for r's N cells, which the caller then fills -> true; no memory
+// for them (or !fits, the caller's own limit) -> refused for good, the HIP error cleared
+template <class T>
+bool level_records_alloc(lf_router_core &r, lf_dbuf<T> &buf, bool fits = true)
+{
+    if (fits && buf.alloc((size_t)r.N) == LF_OK) return true;
+    r.statics_refused = true;
+    (void)hipGetLastError();
+    return false;
+}
+
+inline int check_section(const lf_router_core &r, int section)
 {
     if (section != LF_SECTION_MAIN && section != LF_SECTION_FLOODPLAINS)
         return lf_set_error(LF_E_SECTION, "The section parameter must be either 'main_channel' or 'floodplain'!");
@@ -1019,9 +1108,8 @@ int check_section(const R &r, int section)
 
 // a_dx_div_dt = alpha * dx / dt, evaluated left to right (kinematic_wave_parallel.py:127), for the main channel (a1) and
 // the floodplains (a2, if given), and the per-pixel dx (if given), permuted into sweep order and uploaded on stream s
-template <class R>
-int upload_sweep_statics(R &r, const std::vector<int32_t> &perm, const double *alpha, const double *alpha_floodplains,
-                         const double *dx, hipStream_t s)
+inline int upload_sweep_statics(lf_router_core &r, const std::vector<int32_t> &perm, const double *alpha, const double *alpha_floodplains,
+                                const double *dx, hipStream_t s)
 {
     const int64_t n = r.N;
     std::vector<double> h(n);
@@ -1044,10 +1132,43 @@ int upload_sweep_statics(R &r, const std::vector<int32_t> &perm, const double *a
     return LF_OK;
 }
 
+// What lf_router_create and lf_dist_router_create have in common, in two steps so that a create function keeps the order
+// of its device allocations (its own upstream tables go between the two).  First the scalars, the beta = 3/5 switch and,
+// on stream s, the sweep statics, perm and ups_ptr.  kmax: the largest in-degree a sweep has to look at.
+inline int router_core_init(lf_router_core &r, int device, lf_device_ctx *ctx, int64_t n, int kmax, double beta, double dx_scalar,
+                            double dt, const std::vector<int32_t> &perm, const std::vector<int32_t> &ups_ptr, const double *alpha,
+                            const double *alpha_floodplains, const double *dx, hipStream_t s)
+{
+    r.device = device;
+    r.ctx = ctx;
+    r.N = n;
+    r.kmax = kmax;
+    r.beta = beta;
+    r.inv_beta = 1 / beta;  // kinematic_wave_parallel.py:125
+    r.b_minus_1 = beta - 1; // :126
+    r.dx_scalar = dx_scalar;
+    r.dt = dt;
+    r.dx_per_pixel = dx != nullptr;
+    r.has_floodplains = alpha_floodplains != nullptr;
+    r.fused = router_fused(beta);
+    LF_TRY(upload_sweep_statics(r, perm, alpha, alpha_floodplains, dx, s));
+    LF_TRY(r.perm.upload(perm.data(), n, s));
+    return r.ups_ptr.upload(ups_ptr.data(), n + 1, s);
+}
+
+// ... then the levels: level_start on stream s and on the host, and `constant` off the beta = 3/5 path
+inline int router_core_init_levels(lf_router_core &r, const std::vector<int64_t> &level_start, hipStream_t s)
+{
+    const std::vector<long long> ls(level_start.begin(), level_start.end());
+    LF_TRY(r.level_start.upload(ls.data(), ls.size(), s));
+    if (!r.fused) LF_TRY(r.constant.alloc(r.N));
+    r.h_level_start = level_start;
+    return LF_OK;
+}
+
 // sweep_args of a call on r's section: the new discharge goes to qord (sweep order) and, unless null, to q_pix (pixel
 // order); the INDEXED and STATICS fields stay null for the caller
-template <class R>
-sweep_args sweep_args_of(const R &r, int section, double *qord, double *q_pix, const double *lat)
+inline sweep_args sweep_args_of(const lf_router_core &r, int section, double *qord, double *q_pix, const double *lat)
 {
     sweep_args A;
     A.ups_ptr = r.ups_ptr.p;
@@ -1084,8 +1205,8 @@ struct launch_counts {
 //   a wide level    level(first, cells);
 //   narrow levels   narrow(k0, k1): one workgroup walks the run.
 // The callbacks return an LF_ status; n counts the launches.
-template <class R, class Cones, class Level, class Narrow>
-int route_schedule(const R &r, int b0, int nblocks, const std::vector<level_segment> &segs, bool use_blocks,
+template <class Cones, class Level, class Narrow>
+int route_schedule(const lf_router_core &r, int b0, int nblocks, const std::vector<level_segment> &segs, bool use_blocks,
                    launch_counts &n, Cones &&cones, Level &&level, Narrow &&narrow)
 {
     const char *e = std::getenv("LF_ROUTE_CONES");
