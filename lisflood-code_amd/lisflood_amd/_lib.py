@@ -70,6 +70,16 @@ def u8(a):
     return np.ascontiguousarray(a, dtype=np.uint8)
 
 
+def _host(a):
+    """C-contiguous host array as the device holds it: flags go up as uint8 (a view, no copy)"""
+    a = np.ascontiguousarray(a)
+    return a.view(np.uint8) if a.dtype == np.bool_ else a
+
+
+def _shape(shape):
+    return shape if isinstance(shape, tuple) else tuple(np.atleast_1d(shape).tolist())
+
+
 def device_count():
     n = C.c_int(0)
     check(lib().lf_device_count(C.byref(n)))
@@ -88,7 +98,7 @@ class PinnedArray:
 
     def __init__(self, shape, dtype=np.float64, device=0):
         self.device = device
-        shape = tuple(np.atleast_1d(shape).tolist()) if not isinstance(shape, tuple) else shape
+        shape = _shape(shape)
         n = int(np.prod(shape)) * np.dtype(dtype).itemsize
         p = C.c_void_p()
         check(lib().lf_host_alloc(C.c_int(device), C.c_size_t(n), C.byref(p)))
@@ -112,7 +122,7 @@ class DeviceArray:
     """fp64 / uint8 vector resident in HBM (thin RAII wrapper over lf_device_alloc)."""
 
     def __init__(self, shape, dtype=np.float64, device=0):
-        self.shape = tuple(np.atleast_1d(shape).tolist()) if not isinstance(shape, tuple) else shape
+        self.shape = _shape(shape)
         self.dtype = np.dtype(dtype)
         self.device = device
         self.nbytes = int(np.prod(self.shape)) * self.dtype.itemsize
@@ -122,29 +132,18 @@ class DeviceArray:
 
     @classmethod
     def from_host(cls, a, device=0):
-        a = np.ascontiguousarray(a)
-        if a.dtype == np.bool_:
-            a = a.view(np.uint8)
-        d = cls(a.shape, a.dtype, device)
-        d.upload(a)
-        return d
+        a = _host(a)
+        return cls(a.shape, a.dtype, device).upload(a)
 
-    def upload(self, a):
-        a = np.ascontiguousarray(a)
-        if a.dtype == np.bool_:
-            a = a.view(np.uint8)
-        assert a.nbytes == self.nbytes and a.dtype == self.dtype, (a.shape, a.dtype, self.shape, self.dtype)
-        check(lib().lf_memcpy_h2d(C.c_int(self.device), self.ptr, ptr(a), C.c_size_t(self.nbytes)))
-        return self
-
-    def upload_staged(self, a):
-        """upload() that does not wait for the device (lf_memcpy_h2d_staged): `a` is copied to a page-locked staging slot
-        of the library before the call returns; the DMA runs in order on the stream the library calls currently go to"""
-        a = np.ascontiguousarray(a)
-        if a.dtype == np.bool_:
-            a = a.view(np.uint8)
-        assert a.nbytes == self.nbytes and a.dtype == self.dtype, (a.shape, a.dtype, self.shape, self.dtype)
-        check(lib().lf_memcpy_h2d_staged(C.c_int(self.device), self.ptr, ptr(a), C.c_size_t(self.nbytes)))
+    def upload(self, a, staged=False, prefix=False):
+        """host array -> device.  prefix: a shorter `a` goes into the first entries and the rest stays as it is.  staged: do
+        not wait for the device (lf_memcpy_h2d_staged): `a` is copied to a page-locked staging slot of the library before the
+        call returns; the DMA runs in order on the stream the library calls currently go to"""
+        a = _host(a)
+        assert a.dtype == self.dtype and (a.nbytes == self.nbytes or prefix and a.nbytes < self.nbytes), \
+            (a.shape, a.dtype, self.shape, self.dtype)
+        copy = lib().lf_memcpy_h2d_staged if staged else lib().lf_memcpy_h2d
+        check(copy(C.c_int(self.device), self.ptr, ptr(a), C.c_size_t(a.nbytes)))
         return self
 
     def download(self, out=None):
@@ -185,7 +184,7 @@ class BufferCache:
         self.device, self.buf = device, {}
 
     def get(self, name, shape, dtype=np.float64):
-        shape = tuple(np.atleast_1d(shape).tolist()) if not isinstance(shape, tuple) else shape
+        shape = _shape(shape)
         d = self.buf.get(name)
         if d is None or d.shape != shape or d.dtype != np.dtype(dtype):
             if d is not None:
@@ -194,9 +193,7 @@ class BufferCache:
         return d
 
     def put(self, name, host):
-        host = np.ascontiguousarray(host)
-        if host.dtype == np.bool_:
-            host = host.view(np.uint8)
+        host = _host(host)
         return self.get(name, host.shape, host.dtype).upload(host)
 
     @staticmethod
@@ -214,9 +211,7 @@ class BufferCache:
         the upload is skipped while the array's content checksum is the one of the last upload.  Maps the reference
         itself rewrites during a run (the land-use fractions: landusechange.py:107-139, evapowater.py:108-119) do not
         come through here at all.  static_uploads = False switches the check off."""
-        host = np.ascontiguousarray(host)
-        if host.dtype == np.bool_:
-            host = host.view(np.uint8)
+        host = _host(host)
         if not getattr(self, "static_uploads", True):
             return self.put(name, host)
         fp = self._fingerprint(host)

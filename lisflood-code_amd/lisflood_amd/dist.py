@@ -46,6 +46,8 @@ class DistGraph:
         L.lf_dist_graph_num_launch_units.restype = C.c_int64
         L.lf_dist_graph_num_noncontiguous.restype = C.c_int64
         L.lf_dist_graph_round_recv_slot.restype = C.c_int64
+        L.lf_dist_router_state_size.restype = C.c_int64
+        L.lf_dist_router_last_launches.restype = C.c_int64
         self.num_pixels = int(L.lf_dist_graph_num_pixels(self._h))
         c = (C.c_int64 * 4)()
         check(L.lf_dist_graph_counts(self._h, c))
@@ -549,9 +551,11 @@ class DistRouter:
         self._h = C.c_void_p()
         check(lib().lf_dist_router_create(graph._h, ptr(alpha), C.c_double(beta), ptr(dx), C.c_double(dxs),
                                           C.c_double(time_delta), ptr(a2), C.c_int(device), C.byref(self._h)))
-        lib().lf_dist_router_state_size.restype = C.c_int64
-        lib().lf_dist_router_last_launches.restype = C.c_int64
         self.state_size = graph.state_size
+
+    @property
+    def _ch(self):          # handle of the RCCL communicator, None for the in-process loopback
+        return self.comm._h if self.comm is not None else None
 
     def new_state(self, pix_values=None):
         """Device state vector (local cells in engine order + ghost slots), optionally initialised from a
@@ -573,17 +577,15 @@ class DistRouter:
 
     def route(self, q_state, lat_state, section="main_channel"):
         sec = _lib.SECTION[section]
-        ch = self.comm._h if self.comm is not None else None
-        check(lib().lf_dist_router_route(self._h, ch, q_state.ptr, lat_state.ptr, C.c_int(sec), C.c_int(self.rank_top),
+        check(lib().lf_dist_router_route(self._h, self._ch, q_state.ptr, lat_state.ptr, C.c_int(sec), C.c_int(self.rank_top),
                                          C.c_int(self.rank_bottom)))
 
     def route_many(self, q_state, lat_states, section="main_channel"):
         """len(lat_states) calls in a row, pipelined across calls (lf_dist_router_route_many); result in q_state"""
         sec = _lib.SECTION[section]
-        ch = self.comm._h if self.comm is not None else None
         n = len(lat_states)
         arr = (C.c_void_p * max(n, 1))(*[d.ptr.value for d in lat_states])
-        check(lib().lf_dist_router_route_many(self._h, ch, q_state.ptr, arr, C.c_int(n), C.c_int(sec),
+        check(lib().lf_dist_router_route_many(self._h, self._ch, q_state.ptr, arr, C.c_int(n), C.c_int(sec),
                                               C.c_int(self.rank_top), C.c_int(self.rank_bottom)))
 
     def compute_part_io(self, q_in, q_out, lat_state, phase, part, section="main_channel"):
@@ -608,8 +610,7 @@ class DistRouter:
     def exchange(self, q_state, rnd):
         """halo round `rnd` of a router call alone (lf_dist_router_exchange: pack, one grouped RCCL Send/Recv per neighbour
         on the library stream) -- what route() issues after part 0 of phase `rnd`"""
-        ch = self.comm._h if self.comm is not None else None
-        check(lib().lf_dist_router_exchange(self._h, ch, q_state.ptr, C.c_int(rnd), C.c_int(self.rank_top),
+        check(lib().lf_dist_router_exchange(self._h, self._ch, q_state.ptr, C.c_int(rnd), C.c_int(self.rank_top),
                                             C.c_int(self.rank_bottom)))
 
     def recv_slots(self, rnd):
@@ -640,37 +641,18 @@ class DistRoutingStep:
 
     def __init__(self, router, values, split, Beta, InvDtRouting, DtSec):
         """values: name -> host vector of the rank's cells in local pixel order (names of lf_substep_args)."""
-        from .routing import _OUT, _STATE, _STATIC, _SubstepArgs
+        from .routing import _STATE, _STATIC, SubstepVectors, substep_host_vectors
         self.router, self.split, self.device = router, bool(split), router.device
         N = self.N = router.num_pixels
         self.perm = router.graph.layout()[0].astype(np.int64)
-        self.dev = {}
-        zeros = np.zeros(N)
-        for k in _STATIC + _STATE:
-            x = values.get(k)
-            if x is None:
-                x = np.ones(N, bool) if k == "IsChannelKinematic" else zeros
-            x = np.broadcast_to(x, (N,))[self.perm]
-            if k in ("ChanQKin", "Chan2QKin"):          # router state vectors: ghost slots behind the N cells
-                st = DeviceArray(max(router.state_size, 1), np.float64, self.device).zero()
-                _upload_prefix(st, f64(x), self.device)
-                self.dev[k] = st
-            else:
-                self.dev[k] = DeviceArray.from_host(_lib.u8(x) if k == "IsChannelKinematic" else f64(x), self.device)
-        for k in _OUT + ["scratch0", "scratch1"]:
-            self.dev[k] = DeviceArray(max(N, 1), np.float64, self.device).zero()
-        side = np.broadcast_to(values.get("SideflowChanM3", zeros), (N,))[self.perm]
-        self.dev["SideflowChanM3"] = DeviceArray.from_host(f64(side), self.device)
-        a = self.args = _SubstepArgs()
-        for k, d in self.dev.items():
-            setattr(a, k, d.ptr.value)
-        a.Beta, a.InvBeta, a.InvDtRouting, a.DtSec = float(Beta), 1.0 / float(Beta), float(InvDtRouting), float(DtSec)
-        a.split, a.engine_order = (1 if self.split else 0), 1
+        host = substep_host_vectors(values, N, self.perm, _STATIC + _STATE + ["SideflowChanM3"])
+        self.vectors = SubstepVectors(host, N, Beta, InvDtRouting, DtSec, self.split, True, self.device,
+                                      state_size=router.state_size)       # router state: ghost slots behind the N cells
+        self.dev, self.args = self.vectors.dev, self.vectors.args
 
     def substep(self):
         r = self.router
-        ch = r.comm._h if r.comm is not None else None
-        check(lib().lf_dist_routing_substep(r._h, ch, C.byref(self.args), C.c_int(r.rank_top), C.c_int(r.rank_bottom)))
+        check(lib().lf_dist_routing_substep(r._h, r._ch, C.byref(self.args), C.c_int(r.rank_top), C.c_int(r.rank_bottom)))
 
     def stage(self, i):
         check(lib().lf_substep_stage(C.c_int(self.device), C.c_int(i), C.c_int64(self.N), C.byref(self.args)))
@@ -679,8 +661,7 @@ class DistRoutingStep:
     def substeps_fused(self, nsteps):
         """nsteps x routing.dynamic() = lf_routing_substeps_fused on the whole raster (lf_dist_routing_substeps_fused)"""
         r = self.router
-        ch = r.comm._h if r.comm is not None else None
-        check(lib().lf_dist_routing_substeps_fused(r._h, ch, C.byref(self.args), C.c_int(nsteps), C.c_int64(0),
+        check(lib().lf_dist_routing_substeps_fused(r._h, r._ch, C.byref(self.args), C.c_int(nsteps), C.c_int64(0),
                                                    C.c_int(r.rank_top), C.c_int(r.rank_bottom)))
 
     def fused_prepare(self, nsteps):
@@ -691,23 +672,17 @@ class DistRoutingStep:
 
     # --- several model steps per call: the sub-steps of all of them as one wavefront per phase, one halo block per phase ----
     def _model_step_args(self, sums, sideflows):
-        from .routing import _SubstepArgs
-        a = _SubstepArgs.from_buffer_copy(self.args)
-        a.sumDisDay = sums.ptr.value
-        stride = 0
-        if sideflows is not None:
-            a.SideflowChanM3 = sideflows.ptr.value
-            stride = self.N
-        return a, stride
+        if sideflows is None:
+            return self.vectors.with_overrides(sumDisDay=sums.ptr.value), 0
+        return self.vectors.with_overrides(sumDisDay=sums.ptr.value, SideflowChanM3=sideflows.ptr.value), self.N
 
     def model_steps_fused(self, nsteps, nmodel, sums, sideflows=None):
         """nmodel model steps of nsteps sub-steps in one call (lf_dist_routing_model_steps_fused).  sums: device array
         [nmodel, N] (zeroed by the caller) that receives every model step's discharge sum; sideflows: device array
         [nmodel, N] in the rank's engine order, or None for the resident vector in every model step."""
         r = self.router
-        ch = r.comm._h if r.comm is not None else None
         a, stride = self._model_step_args(sums, sideflows)
-        check(lib().lf_dist_routing_model_steps_fused(r._h, ch, C.byref(a), C.c_int(nsteps), C.c_int(nmodel), C.c_int64(stride),
+        check(lib().lf_dist_routing_model_steps_fused(r._h, r._ch, C.byref(a), C.c_int(nsteps), C.c_int(nmodel), C.c_int64(stride),
                                                       C.c_int(r.rank_top), C.c_int(r.rank_bottom)))
 
     def fused_phase_model_steps(self, nsteps, nmodel, phase, sums, sideflows=None):
@@ -732,15 +707,8 @@ class DistRoutingStep:
         return out
 
     def free(self):
-        for d in self.dev.values():
-            d.free()
+        self.vectors.free()
         self.dev = {}
-
-
-def _upload_prefix(dst, host, device):
-    """host vector -> the first host.size entries of a larger device array"""
-    if host.size:
-        check(lib().lf_memcpy_h2d(C.c_int(device), dst.ptr, ptr(host), C.c_size_t(host.nbytes)))
 
 
 def loopback_substep(steps):

@@ -131,8 +131,6 @@ class HotPathDevice:
             self.river = m.river_router
             if "QInM3Old" in structures:       # inflow hydrographs: QInM3 of the previous model step, channel domain
                 self._qin_old = f64(np.broadcast_to(structures["QInM3Old"], (Nk,))).copy()
-            for k in chan_names | set(RT._OUT) | {"SideflowChanM3"}:
-                self.d[k] = m._dev[k]
         self.perm = self.river.graph.layout()[0].astype(np.int64)        # engine position -> channel-domain pixel
         self.gpix = self.ids[self.perm]                                   # engine position -> land pixel
         # position -> pixel of the overland graph's sweep order (None: the non-channel vectors stay in pixel order)
@@ -145,20 +143,25 @@ class HotPathDevice:
             src = self.gpix
         self._gidx = DeviceArray.from_host(src.astype(np.int32), device)
         # ---- device vectors ------------------------------------------------------------------------
+        if self.rmod is None:       # the channel vectors, in the engine order of the river router, and their argument block
+            chan = {"IsChannelKinematic": np.zeros(Nk, bool)}     # (where it is not given, no pixel is a channel pixel)
+            chan.update({k: values[k] for k in chan_names if k in values})
+            vec = RT.SubstepVectors(RT.substep_host_vectors(chan, Nk, self.perm), Nk, sc["Beta"], 1 / sc["DtRouting"],
+                                    sc["DtSec"], self.split, True, device, order=RT._STATIC + RT._STATE)
+        else:       # self.d and self.rout alias the routing module's own vectors and block (free() frees each array once)
+            vec = self.rmod._vectors
+        self.d.update(vec.dev)
         bool_names = SL._BOOL | {"IsChannel", "IsChannelKinematic"}
         for k, a in values.items():
             a = np.asarray(a)
             if self.report is not None and k in OPTIONAL_MAPS and k not in self._kept():
                 continue                              # an optional map nobody asked for: no device vector at all
-            if k in chan_names:                       # channel vectors: engine order of the river router
-                if self.rmod is not None:
-                    continue
-                a = np.broadcast_to(a, (Nk,))[self.perm]
-            elif self.pixel_of_position is not None and a.ndim >= 1 and a.shape[-1] == N and k not in bool_names:
+            if k in chan_names:                       # channel vectors: made above
+                continue
+            if self.pixel_of_position is not None and a.ndim >= 1 and a.shape[-1] == N and k not in bool_names:
                 self.d[k] = self._upload_ordered(f64(a))      # permuted on the device (a host gather of ~100 fields is slow)
                 continue
-            else:
-                a = self._ordered(a)
+            a = self._ordered(a)
             self.d[k] = DeviceArray.from_host(u8(a) if k in bool_names else f64(a), device)
         if getattr(self, "_perm_tmp", None) is not None:
             self._perm_tmp.free(); self._perm_idx.free()
@@ -213,10 +216,10 @@ class HotPathDevice:
         f.Beta, f.MMtoM3, f.M3toMM = sc["Beta"], sc["MMtoM3"], sc["M3toMM"]
         f.PixelLength, f.InvPixelLength = sc["PixelLength"], 1 / sc["PixelLength"]
         f.DtSec, f.InvDtSec, f.InvNoRoutSteps, f.N = sc["DtSec"], 1 / sc["DtSec"], 1 / sc["NoRoutSteps"], N
-        r = self.rout = RT._SubstepArgs()
-        fill(r, RT._STATIC + ["SideflowChanM3"] + RT._STATE + RT._OUT + ["scratch0", "scratch1"], lambda k: max(Nk, 1))
-        r.Beta, r.InvBeta, r.InvDtRouting, r.DtSec = sc["Beta"], 1 / sc["Beta"], 1 / sc["DtRouting"], sc["DtSec"]
-        r.split, r.engine_order = (1 if self.split else 0), 1
+        if self.rmod is None:       # outputs, scratch and sideflow come last, where they always were allocated
+            vec.allocate(["SideflowChanM3"] + RT._OUT + ["scratch0", "scratch1"])
+            self.d.update(vec.dev)
+        self.rout = vec.args
         self.steps_done = 0
 
     def _kept(self):
@@ -345,8 +348,8 @@ class HotPathDevice:
         if side:
             check(L.lf_side_stream_begin(d))
         try:
-            dev["QInM3Old"].upload_staged(f64(m._up(self._qin_old)))
-            dev["QDelta"].upload_staged(f64(m._up(delta)))
+            dev["QInM3Old"].upload(f64(m._up(self._qin_old)), staged=True)
+            dev["QDelta"].upload(f64(m._up(delta)), staged=True)
         finally:
             if side:
                 check(L.lf_side_stream_end(d))
@@ -525,12 +528,11 @@ class HotPathDevice:
 
     def load_state(self, path):
         z = np.load(path)
-        chan = set(RT._STATIC + RT._STATE + RT._OUT)
         for k in self.state_names():
             if k not in z.files and k in OPTIONAL_MAPS:
                 continue                              # a state file written by an object that did not report this map
             a = z[k]
-            if k in chan:
+            if k in _CHANNEL_NAMES:
                 if self.Nk < self.N:
                     rest = np.ones(self.N, bool); rest[self.ids] = False
                     if np.any(a[rest] != 0):

@@ -36,6 +36,74 @@ class _SubstepArgs(C.Structure):  # lf_substep_args, include/lisflood_amd.h
                  ("split", C.c_int32), ("engine_order", C.c_int32)])
 
 
+def result_names(split):
+    """the vectors a routing sub-step writes: all of the state under split routing, else the main channel's alone"""
+    return (_STATE if split else ["ChanQKin", "ChanM3Kin", "ChanQ", "sumDisDay"]) + _OUT
+
+
+def substep_host_vectors(values, n, perm=None, names=_STATIC + _STATE):
+    """name -> host vector as lf_substep_args wants it: `values[name]` (a mapping, or a namespace like `var`) broadcast
+    to (n,), gathered through `perm` (position -> host index; None: as it is), C-contiguous, the channel flag as uint8 and
+    everything else as float64.  A missing name is zeros -- but every pixel is a channel pixel when nothing says otherwise."""
+    get = values.get if hasattr(values, "get") else lambda k: getattr(values, k, None)
+    out = {}
+    for k in names:
+        x = get(k)
+        if x is None:
+            x = np.ones(n, bool) if k == "IsChannelKinematic" else np.zeros(n)
+        x = np.broadcast_to(x, (n,))
+        out[k] = (u8 if k == "IsChannelKinematic" else f64)(x if perm is None else x[perm])
+    return out
+
+
+class SubstepVectors:
+    """The device vectors behind lf_substep_args and the argument block that points at them -- the one place where
+    either is made.  `host`: name -> vector of n_dev entries (substep_host_vectors); a name it does not hold is zeroed.
+    state_size: length of the two router state vectors (ChanQKin, Chan2QKin) where ghost slots follow the n_dev cells;
+    sideflow: host [rows, n_dev] (default: one zeroed row).  No buffer is shorter than one element.  `order`: the names the
+    constructor allocates, in that order (each caller keeps the buffer placement it had); allocate() makes the rest later."""
+
+    def __init__(self, host, n_dev, Beta, InvDtRouting, DtSec, split, engine_order, device=0, state_size=None,
+                 sideflow=None, order=_STATIC + _STATE + _OUT + ["scratch0", "scratch1", "SideflowChanM3"]):
+        self.device, self.dev, self._host = device, {}, dict(host)
+        self._len = {k: n_dev for k, t in _SubstepArgs._fields_ if t is C.c_void_p}      # entries of a name's host vector
+        if sideflow is not None:
+            self._host["SideflowChanM3"] = f64(sideflow).reshape(-1)
+            self._len["SideflowChanM3"] = self._host["SideflowChanM3"].size
+        self._size = dict(self._len, **({} if state_size is None else dict(ChanQKin=state_size, Chan2QKin=state_size)))
+        a = self.args = _SubstepArgs()
+        a.Beta, a.InvBeta, a.InvDtRouting, a.DtSec = float(Beta), 1.0 / float(Beta), float(InvDtRouting), float(DtSec)
+        a.split, a.engine_order = (1 if split else 0), (1 if engine_order else 0)
+        self.allocate(order)
+
+    def allocate(self, names):
+        for k in names:
+            dtype = np.uint8 if k == "IsChannelKinematic" else np.float64
+            self.dev[k] = DeviceArray(max(int(self._size[k]), 1), dtype, self.device).zero()
+            if k in self._host:
+                self.upload(k, self._host.pop(k))
+            setattr(self.args, k, self.dev[k].ptr.value)
+
+    def upload(self, name, host):
+        """host vector of the name's own length -> device (ghost slots and the padding element behind it stay as they are)"""
+        assert np.size(host) == self._len[name], (name, np.shape(host), self._len[name])
+        self.dev[name].upload(host, prefix=True)
+
+    def download(self, name):
+        return self.dev[name].download()
+
+    def with_overrides(self, **ptrs):
+        """a copy of the argument block with the named pointer fields replaced; `args` itself stays as it is"""
+        a = _SubstepArgs.from_buffer_copy(self.args)
+        for k, p in ptrs.items():
+            setattr(a, k, p)
+        return a
+
+    def free(self):
+        for d in self.dev.values():
+            d.free()
+
+
 _INLOOP_PTRS = (
     "ChanQ n_lakes lake_cell lake_ups_ptr lake_ups_idx LakeFactor LakeFactorSqr LakeAreaCC LakeStorageM3CC "
     "LakeInflowOldCC LakeOutflowCC LakeStorageM3BalanceCC LakeLevelCC LakeInflowCC QLakeOutM3Dt n_res res_cell "
@@ -401,25 +469,14 @@ class routing(HydroModule):
         return bool(self.options["SplitRouting"]) and not self.options["InitLisflood"]   # routing.py:518
 
     def _ensure_device(self):
-        v = self.var
-        N, Nk = self._nfull, self.river_router.num_pixels      # host vectors / device vectors (compact domain)
         if "scratch0" in self._dev:
             return
-        zeros = np.zeros(N)
-        for k in _STATIC:
-            a = getattr(v, k, None)
-            if a is None:
-                a = np.ones(N, bool) if k == "IsChannelKinematic" else zeros
-            a = self._up(np.broadcast_to(a, (N,)))
-            a = u8(a) if k == "IsChannelKinematic" else f64(a)
-            self._dev[k] = DeviceArray.from_host(a, self.device)
-        for k in _STATE + _OUT + ["SideflowChanM3", "scratch0", "scratch1"]:
-            self._dev[k] = DeviceArray(max(Nk, 1), np.float64, self.device).zero()
-        a = self._args = _SubstepArgs()
-        for k, d in self._dev.items():
-            setattr(a, k, d.ptr.value)
-        a.Beta, a.InvBeta, a.InvDtRouting, a.DtSec = float(v.Beta), float(v.InvBeta), float(v.InvDtRouting), float(v.DtSec)
-        a.engine_order = 1 if self.engine_order else 0
+        v = self.var
+        host = substep_host_vectors(v, self._nfull, self._perm if self.engine_order else None, _STATIC)
+        self._vectors = SubstepVectors(host, self.river_router.num_pixels, v.Beta, v.InvDtRouting, v.DtSec, self._split(),
+                                       self.engine_order, self.device,       # the state is uploaded by _upload_state
+                                       order=_STATIC + _STATE + _OUT + ["SideflowChanM3", "scratch0", "scratch1"])
+        self._dev, self._args = self._vectors.dev, self._vectors.args
 
     def _upload_state(self):
         v = self.var
@@ -433,9 +490,7 @@ class routing(HydroModule):
 
     def _download_state(self):
         v = self.var
-        split = self._split()
-        names = _STATE + _OUT if split else ["ChanQKin", "ChanM3Kin", "ChanQ", "sumDisDay"] + _OUT
-        for k in names:
+        for k in result_names(self._split()):
             cur = getattr(v, k, None)
             inplace = isinstance(cur, np.ndarray) and cur.dtype == np.float64 and cur.flags.c_contiguous and \
                 cur.size == self._nfull and cur.flags.writeable
@@ -681,8 +736,7 @@ class routing(HydroModule):
 
 def _fused(self, sideflows):
     """See routing.dynamic_fused."""
-    v = self.var
-    r = self.river_router
+    v, r = self.var, self.river_router
     N, Nk = self._nfull, r.num_pixels                         # host vectors / device vectors (compact domain)
     perm = self._perm if self.engine_order else self._ids[r.graph.layout()[0].astype(np.int64)]
     sideflows = np.ascontiguousarray(np.atleast_2d(np.asarray(sideflows, dtype=np.float64)))
@@ -690,34 +744,14 @@ def _fused(self, sideflows):
     nsteps = int(v.NoRoutSteps)
     if stride and nsteps_in != nsteps:
         raise ValueError("need one sideflow vector, or NoRoutSteps of them")
-    a = _SubstepArgs()
-    dev = {}
-    zeros = np.zeros(N)
-    for k in _STATIC:
-        x = getattr(v, k, None)
-        if x is None:
-            x = np.ones(N, bool) if k == "IsChannelKinematic" else zeros
-        x = np.broadcast_to(x, (N,))[perm]
-        dev[k] = DeviceArray.from_host(u8(x) if k == "IsChannelKinematic" else f64(x), self.device)
-    for k in _STATE:
-        x = getattr(v, k, None)
-        dev[k] = DeviceArray.from_host(f64(np.broadcast_to(zeros if x is None else x, (N,))[perm]), self.device)
-    for k in _OUT + ["scratch0", "scratch1"]:
-        dev[k] = DeviceArray(max(Nk, 1), np.float64, self.device).zero()
-    dev["SideflowChanM3"] = DeviceArray.from_host(np.ascontiguousarray(sideflows[:, perm]), self.device)
-    for k, d in dev.items():
-        setattr(a, k, d.ptr.value)
-    a.Beta, a.InvBeta, a.InvDtRouting, a.DtSec = float(v.Beta), float(v.InvBeta), float(v.InvDtRouting), float(v.DtSec)
-    a.split = 1 if self._split() else 0
-    a.engine_order = 1
-    check(lib().lf_routing_substeps_fused(r._h, C.byref(a), C.c_int(nsteps), C.c_int64(stride)))
-    names = _STATE + _OUT if self._split() else ["ChanQKin", "ChanM3Kin", "ChanQ", "sumDisDay"] + _OUT
-    for k in names:
+    sv = SubstepVectors(substep_host_vectors(v, N, perm), Nk, v.Beta, v.InvDtRouting, v.DtSec, self._split(), True,
+                        self.device, sideflow=sideflows[:, perm])
+    check(lib().lf_routing_substeps_fused(r._h, C.byref(sv.args), C.c_int(nsteps), C.c_int64(stride)))
+    for k in result_names(self._split()):
         out = np.zeros(N)                # pixels outside a compact domain keep their zero state
-        out[perm] = dev[k].download()[:Nk]
+        out[perm] = sv.download(k)[:Nk]
         setattr(v, k, out)
-    for d in dev.values():
-        d.free()
+    sv.free()
 
 
 def var_from_fixture(g):
