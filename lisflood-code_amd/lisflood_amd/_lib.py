@@ -13,6 +13,83 @@ LF_E_INVALID, LF_E_CYCLE, LF_E_NO_DEVICE, LF_E_HIP, LF_E_SECTION, LF_E_COMM = -1
 SECTION = {"main_channel": 0, "floodplains": 1}
 
 
+# Every function of include/lisflood_amd.h by signature: one letter per parameter (p pointer or array, i int, u unsigned
+# int, q int64_t, z size_t, d double), then ">" and the return kind where it is not int (q, v void, s const char *);
+# names without their lf_ prefix.  lib() declares them all to ctypes, so call sites pass plain Python values and a value
+# of the wrong kind is an ArgumentError instead of a truncated argument.  tests/test_host_cpu.py holds the table to the
+# header, prototype by prototype.
+_KIND = {"p": C.c_void_p, "i": C.c_int, "u": C.c_uint, "q": C.c_int64, "z": C.c_size_t, "d": C.c_double,
+         "v": None, "s": C.c_char_p}
+_SIGNATURES = {
+    "": "version",
+    "i": "side_stream_begin side_stream_end side_stream_join lane_fork lane_join device_trim "
+         "device_synchronize timer_start",
+    "ii": "upload_begin upload_end upload_wait compute_acquire compute_release lane_select",
+    "iippq": "calibration_streams",
+    "iiqp": "substep_stage",
+    "ip": "device_free host_free timer_stop canopy_device soil_pf_device inloop_structures "
+          "pixel_aggregates_device interception_host soil_columns_host interception_device soil_columns_device "
+          "soil_columns_device_derived soil_last_deferred",
+    "ipi": "soil_substep_histogram",
+    "ipiz": "memset",
+    "ippii": "lddrepair_raster_device",
+    "ipppi": "land_columns_device",
+    "ipppii": "router_route_device_multi upstream_sum_raster_device lddmask_raster_device ldd_raster_host",
+    "ipppqq": "scale_rows_device",
+    "ippqi": "calibration_copy",
+    "ippz": "memcpy_h2d memcpy_h2d_staged upload_copy upload_copy_f32 memcpy_d2h memcpy_d2d",
+    "ipqp": "count_nonfinite",
+    "ipz": "device_name",
+    "iqppp": "gather_device",
+    "iup": "xcd_contiguous_order",
+    "izp": "device_alloc host_alloc",
+    "p": "struct_sizes device_count graph_max_upstream router_device router_reset_site_cache "
+         "dist_graph_local_num_phases dist_graph_num_phases comm_unique_id comm_close",
+    "pi": "router_profile_enable dist_graph_finalize",
+    "piiip": "comm_create",
+    "piip": "dist_graph_round_send_positions dist_fused_halo_block dist_graph_part_range",
+    "pip": "dist_graph_phase_range dist_graph_round_counts dist_fused_slab",
+    "pipp": "catchment_totals_multi_device catchment_totals_multi_host accuflux_ordered_multi_device "
+            "dist_router_recv_slots",
+    "piqip": "graph_block_plan_stats graph_block_plan_check",
+    "pp": "graph_get_links router_last_launches router_route_plan_stats routing_substep dist_graph_counts "
+          "dist_graph_slab_layout dist_graph_block_stats",
+    "ppdpddpip": "router_create dist_router_create",
+    "ppi": "router_profile_read dist_fused_prepare",
+    "ppiiii": "dist_fused_exchange",
+    "ppiip": "graph_create graph_create_raster",
+    "ppiipp": "graph_create_ex",
+    "ppiippppp": "dist_graph_create",
+    "ppiiq": "routing_model_steps_fused",
+    "ppiiqi": "dist_fused_phase_model_steps",
+    "ppipp": "dist_router_pack",
+    "ppiq": "routing_substeps_fused",
+    "ppiqi": "dist_fused_phase",
+    "ppp": "graph_get_orders router_to_engine_order router_from_engine_order upstream_sum_device "
+           "upstream_sum_host accuflux_host accuflux_ordered_device downstream_device downstream_host "
+           "catchments_device catchments catchment_totals_device catchment_totals_host "
+           "dist_graph_get_export_phases dist_graph_get_layout dist_router_to_engine_order "
+           "dist_router_from_engine_order dist_graph_get_fused_tables",
+    "pppi": "router_route_host router_route_device router_route_ordered routing_substeps_fused_structures",
+    "pppii": "dist_routing_substep dist_router_compute_phase",
+    "pppiii": "dist_router_compute_part dist_router_exchange",
+    "pppiiqii": "dist_routing_model_steps_fused",
+    "pppiqii": "dist_routing_substeps_fused",
+    "pppp": "graph_get_lookups graph_get_layout surface_step surface_step_ordered dist_graph_set_ghost_phases "
+            "dist_graph_get_csr",
+    "ppppiii": "dist_router_route dist_router_compute_part_io",
+    "ppppiiii": "dist_router_route_many",
+    "ppppppp": "dist_graph_get_fused_plan",
+    "pppppppp": "dist_graph_get_route_plan",
+    "p>q": "graph_num_pixels graph_num_levels router_num_pixels dist_graph_num_pixels dist_graph_state_size "
+           "dist_graph_num_launch_units dist_graph_num_noncontiguous dist_router_state_size "
+           "dist_router_last_launches",
+    "pii>q": "dist_graph_round_recv_slot",
+    ">s": "last_error",
+    "p>v": "graph_destroy router_destroy dist_graph_destroy comm_destroy dist_router_destroy",
+}
+
+
 class LisfloodAmdError(RuntimeError):
     def __init__(self, code, message):
         super().__init__("lisflood_amd error %d: %s" % (code, message))
@@ -33,16 +110,14 @@ def lib():
             raise LisfloodAmdError(LF_E_NO_DEVICE, "%s not found - build it with `make -C lisflood-code_amd` "
                                    "(or __graft_entry__.build()); lisflood_amd has no CPU fallback" % path)
         L = C.CDLL(path)
-        L.lf_last_error.restype = C.c_char_p
-        L.lf_graph_num_pixels.restype = C.c_int64
-        L.lf_graph_num_levels.restype = C.c_int64
-        L.lf_graph_num_pixels.argtypes = [C.c_void_p]
-        L.lf_graph_num_levels.argtypes = [C.c_void_p]
-        L.lf_graph_max_upstream.argtypes = [C.c_void_p]
-        L.lf_graph_destroy.argtypes = [C.c_void_p]
-        L.lf_graph_destroy.restype = None
-        L.lf_router_destroy.argtypes = [C.c_void_p]
-        L.lf_router_destroy.restype = None
+        for sig, names in _SIGNATURES.items():
+            args, _, ret = sig.partition(">")
+            for name in names.split():
+                try:
+                    f = getattr(L, "lf_" + name)
+                except AttributeError:
+                    raise LisfloodAmdError(LF_E_INVALID, "%s does not export lf_%s" % (path, name)) from None
+                f.argtypes, f.restype = [_KIND[k] for k in args], _KIND[ret or "i"]
         _lib = L
     return _lib
 
@@ -88,7 +163,7 @@ def device_count():
 
 def device_name(device=0):
     buf = C.create_string_buffer(256)
-    check(lib().lf_device_name(C.c_int(device), buf, C.c_size_t(256)))
+    check(lib().lf_device_name(device, buf, 256))
     return buf.value.decode()
 
 
@@ -101,14 +176,14 @@ class PinnedArray:
         shape = _shape(shape)
         n = int(np.prod(shape)) * np.dtype(dtype).itemsize
         p = C.c_void_p()
-        check(lib().lf_host_alloc(C.c_int(device), C.c_size_t(n), C.byref(p)))
+        check(lib().lf_host_alloc(device, n, C.byref(p)))
         self.ptr = C.c_void_p(p.value)
         self.a = np.frombuffer((C.c_char * max(n, 1)).from_address(p.value), dtype=dtype, count=int(np.prod(shape))).reshape(shape)
 
     def free(self):
         if getattr(self, "ptr", None) is not None and self.ptr.value:
             self.a = None
-            lib().lf_host_free(C.c_int(self.device), self.ptr)
+            lib().lf_host_free(self.device, self.ptr)
             self.ptr = C.c_void_p(None)
 
     def __del__(self):
@@ -127,7 +202,7 @@ class DeviceArray:
         self.device = device
         self.nbytes = int(np.prod(self.shape)) * self.dtype.itemsize
         p = C.c_void_p()
-        check(lib().lf_device_alloc(C.c_int(device), C.c_size_t(self.nbytes), C.byref(p)))
+        check(lib().lf_device_alloc(device, self.nbytes, C.byref(p)))
         self.ptr = C.c_void_p(p.value)
 
     @classmethod
@@ -143,28 +218,28 @@ class DeviceArray:
         assert a.dtype == self.dtype and (a.nbytes == self.nbytes or prefix and a.nbytes < self.nbytes), \
             (a.shape, a.dtype, self.shape, self.dtype)
         copy = lib().lf_memcpy_h2d_staged if staged else lib().lf_memcpy_h2d
-        check(copy(C.c_int(self.device), self.ptr, ptr(a), C.c_size_t(a.nbytes)))
+        check(copy(self.device, self.ptr, ptr(a), a.nbytes))
         return self
 
     def download(self, out=None):
         if out is None:
             out = np.empty(self.shape, self.dtype)
         assert out.nbytes == self.nbytes and out.flags.c_contiguous
-        check(lib().lf_memcpy_d2h(C.c_int(self.device), ptr(out), self.ptr, C.c_size_t(self.nbytes)))
+        check(lib().lf_memcpy_d2h(self.device, ptr(out), self.ptr, self.nbytes))
         return out
 
     def copy_from(self, other):
         assert other.nbytes == self.nbytes
-        check(lib().lf_memcpy_d2d(C.c_int(self.device), self.ptr, other.ptr, C.c_size_t(self.nbytes)))
+        check(lib().lf_memcpy_d2d(self.device, self.ptr, other.ptr, self.nbytes))
         return self
 
     def zero(self):
-        check(lib().lf_memset(C.c_int(self.device), self.ptr, C.c_int(0), C.c_size_t(self.nbytes)))
+        check(lib().lf_memset(self.device, self.ptr, 0, self.nbytes))
         return self
 
     def free(self):
         if getattr(self, "ptr", None) is not None and self.ptr.value:
-            lib().lf_device_free(C.c_int(self.device), self.ptr)
+            lib().lf_device_free(self.device, self.ptr)
             self.ptr = C.c_void_p(None)
 
     def __del__(self):
@@ -234,14 +309,14 @@ class BufferCache:
 
 
 def synchronize(device=0):
-    check(lib().lf_device_synchronize(C.c_int(device)))
+    check(lib().lf_device_synchronize(device))
 
 
 def timer_start(device=0):
-    check(lib().lf_timer_start(C.c_int(device)))
+    check(lib().lf_timer_start(device))
 
 
 def timer_stop(device=0):
     ms = C.c_double(0.0)
-    check(lib().lf_timer_stop(C.c_int(device), C.byref(ms)))
+    check(lib().lf_timer_stop(device, C.byref(ms)))
     return ms.value

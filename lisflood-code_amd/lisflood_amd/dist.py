@@ -38,19 +38,11 @@ class DistGraph:
                 None if mask_top is None else u8(mask_top), conv(ldd_bottom),
                 None if mask_bottom is None else u8(mask_bottom)]
         self._h = C.c_void_p()
-        check(lib().lf_dist_graph_create(ptr(keep[0]), ptr(keep[1]), C.c_int(Hl), C.c_int(W), ptr(keep[2]),
-                                         ptr(keep[3]), ptr(keep[4]), ptr(keep[5]), C.byref(self._h)))
-        L = lib()
-        L.lf_dist_graph_num_pixels.restype = C.c_int64
-        L.lf_dist_graph_state_size.restype = C.c_int64
-        L.lf_dist_graph_num_launch_units.restype = C.c_int64
-        L.lf_dist_graph_num_noncontiguous.restype = C.c_int64
-        L.lf_dist_graph_round_recv_slot.restype = C.c_int64
-        L.lf_dist_router_state_size.restype = C.c_int64
-        L.lf_dist_router_last_launches.restype = C.c_int64
-        self.num_pixels = int(L.lf_dist_graph_num_pixels(self._h))
+        check(lib().lf_dist_graph_create(ptr(keep[0]), ptr(keep[1]), Hl, W, ptr(keep[2]), ptr(keep[3]), ptr(keep[4]),
+                                         ptr(keep[5]), C.byref(self._h)))
+        self.num_pixels = int(lib().lf_dist_graph_num_pixels(self._h))
         c = (C.c_int64 * 4)()
-        check(L.lf_dist_graph_counts(self._h, c))
+        check(lib().lf_dist_graph_counts(self._h, c))
         self.n_export = (int(c[0]), int(c[1]))
         self.n_ghost = (int(c[2]), int(c[3]))
         self.finalized = False
@@ -74,7 +66,7 @@ class DistGraph:
         return int(lib().lf_dist_graph_local_num_phases(self._h))
 
     def finalize(self, nphases):
-        check(lib().lf_dist_graph_finalize(self._h, C.c_int(nphases)))
+        check(lib().lf_dist_graph_finalize(self._h, nphases))
         self.finalized = True
         self.num_phases = nphases
         self.state_size = int(lib().lf_dist_graph_state_size(self._h))
@@ -98,29 +90,29 @@ class DistGraph:
 
     def phase_range(self, phase):
         o = (C.c_int64 * 2)()
-        check(lib().lf_dist_graph_phase_range(self._h, C.c_int(phase), o))
+        check(lib().lf_dist_graph_phase_range(self._h, phase, o))
         return int(o[0]), int(o[1])
 
     def part_range(self, phase, part):
         """positions [begin, end) of a phase's boundary-critical cells (part 0: its exports and what drains into them
         inside the phase) or of the rest (part 1); the two parts are independent of each other"""
         o = (C.c_int64 * 2)()
-        check(lib().lf_dist_graph_part_range(self._h, C.c_int(phase), C.c_int(part), o))
+        check(lib().lf_dist_graph_part_range(self._h, phase, part, o))
         return int(o[0]), int(o[1])
 
     def round_counts(self, rnd):
         o = (C.c_int64 * 4)()
-        check(lib().lf_dist_graph_round_counts(self._h, C.c_int(rnd), o))
+        check(lib().lf_dist_graph_round_counts(self._h, rnd, o))
         return dict(send=(int(o[0]), int(o[1])), recv=(int(o[2]), int(o[3])))
 
     def round_send_positions(self, rnd, side):
         n = self.round_counts(rnd)["send"][side]
         pos = np.empty(n, np.int32)
-        check(lib().lf_dist_graph_round_send_positions(self._h, C.c_int(rnd), C.c_int(side), ptr(pos)))
+        check(lib().lf_dist_graph_round_send_positions(self._h, rnd, side, ptr(pos)))
         return pos
 
     def round_recv_slot(self, rnd, side):
-        return int(lib().lf_dist_graph_round_recv_slot(self._h, C.c_int(rnd), C.c_int(side)))
+        return int(lib().lf_dist_graph_round_recv_slot(self._h, rnd, side))
 
     def slab_layout(self):
         """slab slots of the fused sub-step path: dict(slots, export=(top, bottom), ghost=(top, bottom), xphase)"""
@@ -523,7 +515,7 @@ class Comm:
 
     def __init__(self, uid, nranks, rank, device):
         self._h = C.c_void_p()
-        check(lib().lf_comm_create(C.c_char_p(uid), C.c_int(nranks), C.c_int(rank), C.c_int(device), C.byref(self._h)))
+        check(lib().lf_comm_create(C.c_char_p(uid), nranks, rank, device, C.byref(self._h)))
 
     def close(self):
         """tears the communicator down; raises if RCCL reports an error of an earlier (asynchronous) operation"""
@@ -549,8 +541,8 @@ class DistRouter:
             dx, dxs = f64(space_delta), 0.0
         a2 = None if alpha_floodplains is None else f64(np.broadcast_to(alpha_floodplains, (N,)))
         self._h = C.c_void_p()
-        check(lib().lf_dist_router_create(graph._h, ptr(alpha), C.c_double(beta), ptr(dx), C.c_double(dxs),
-                                          C.c_double(time_delta), ptr(a2), C.c_int(device), C.byref(self._h)))
+        check(lib().lf_dist_router_create(graph._h, ptr(alpha), beta, ptr(dx), dxs, time_delta, ptr(a2), device,
+                                          C.byref(self._h)))
         self.state_size = graph.state_size
 
     @property
@@ -577,46 +569,44 @@ class DistRouter:
 
     def route(self, q_state, lat_state, section="main_channel"):
         sec = _lib.SECTION[section]
-        check(lib().lf_dist_router_route(self._h, self._ch, q_state.ptr, lat_state.ptr, C.c_int(sec), C.c_int(self.rank_top),
-                                         C.c_int(self.rank_bottom)))
+        check(lib().lf_dist_router_route(self._h, self._ch, q_state.ptr, lat_state.ptr, sec, self.rank_top,
+                                         self.rank_bottom))
 
     def route_many(self, q_state, lat_states, section="main_channel"):
         """len(lat_states) calls in a row, pipelined across calls (lf_dist_router_route_many); result in q_state"""
         sec = _lib.SECTION[section]
         n = len(lat_states)
         arr = (C.c_void_p * max(n, 1))(*[d.ptr.value for d in lat_states])
-        check(lib().lf_dist_router_route_many(self._h, self._ch, q_state.ptr, arr, C.c_int(n), C.c_int(sec),
-                                              C.c_int(self.rank_top), C.c_int(self.rank_bottom)))
+        check(lib().lf_dist_router_route_many(self._h, self._ch, q_state.ptr, arr, n, sec, self.rank_top,
+                                              self.rank_bottom))
 
     def compute_part_io(self, q_in, q_out, lat_state, phase, part, section="main_channel"):
-        check(lib().lf_dist_router_compute_part_io(self._h, q_in.ptr, q_out.ptr, lat_state.ptr,
-                                                   C.c_int(_lib.SECTION[section]), C.c_int(phase), C.c_int(part)))
+        check(lib().lf_dist_router_compute_part_io(self._h, q_in.ptr, q_out.ptr, lat_state.ptr, _lib.SECTION[section],
+                                                   phase, part))
 
     # pieces, for the in-process loopback
     def compute_phase(self, q_state, lat_state, phase, section="main_channel"):
-        check(lib().lf_dist_router_compute_phase(self._h, q_state.ptr, lat_state.ptr, C.c_int(_lib.SECTION[section]),
-                                                 C.c_int(phase)))
+        check(lib().lf_dist_router_compute_phase(self._h, q_state.ptr, lat_state.ptr, _lib.SECTION[section], phase))
 
     def compute_part(self, q_state, lat_state, phase, part, section="main_channel"):
-        check(lib().lf_dist_router_compute_part(self._h, q_state.ptr, lat_state.ptr, C.c_int(_lib.SECTION[section]),
-                                                C.c_int(phase), C.c_int(part)))
+        check(lib().lf_dist_router_compute_part(self._h, q_state.ptr, lat_state.ptr, _lib.SECTION[section], phase,
+                                                part))
 
     def pack(self, q_state, rnd):
         ptrs = (C.c_void_p * 2)()
         cnt = (C.c_int64 * 2)()
-        check(lib().lf_dist_router_pack(self._h, q_state.ptr, C.c_int(rnd), ptrs, cnt))
+        check(lib().lf_dist_router_pack(self._h, q_state.ptr, rnd, ptrs, cnt))
         return [(ptrs[i], int(cnt[i])) for i in range(2)]
 
     def exchange(self, q_state, rnd):
         """halo round `rnd` of a router call alone (lf_dist_router_exchange: pack, one grouped RCCL Send/Recv per neighbour
         on the library stream) -- what route() issues after part 0 of phase `rnd`"""
-        check(lib().lf_dist_router_exchange(self._h, self._ch, q_state.ptr, C.c_int(rnd), C.c_int(self.rank_top),
-                                            C.c_int(self.rank_bottom)))
+        check(lib().lf_dist_router_exchange(self._h, self._ch, q_state.ptr, rnd, self.rank_top, self.rank_bottom))
 
     def recv_slots(self, rnd):
         slot = (C.c_int64 * 2)()
         cnt = (C.c_int64 * 2)()
-        check(lib().lf_dist_router_recv_slots(self._h, C.c_int(rnd), slot, cnt))
+        check(lib().lf_dist_router_recv_slots(self._h, rnd, slot, cnt))
         return [(int(slot[i]), int(cnt[i])) for i in range(2)]
 
     def last_launches(self):
@@ -652,23 +642,23 @@ class DistRoutingStep:
 
     def substep(self):
         r = self.router
-        check(lib().lf_dist_routing_substep(r._h, r._ch, C.byref(self.args), C.c_int(r.rank_top), C.c_int(r.rank_bottom)))
+        check(lib().lf_dist_routing_substep(r._h, r._ch, C.byref(self.args), r.rank_top, r.rank_bottom))
 
     def stage(self, i):
-        check(lib().lf_substep_stage(C.c_int(self.device), C.c_int(i), C.c_int64(self.N), C.byref(self.args)))
+        check(lib().lf_substep_stage(self.device, i, self.N, C.byref(self.args)))
 
     # --- a whole model step: every sub-step of a phase as one wavefront, one halo exchange per phase -----------------
     def substeps_fused(self, nsteps):
         """nsteps x routing.dynamic() = lf_routing_substeps_fused on the whole raster (lf_dist_routing_substeps_fused)"""
         r = self.router
-        check(lib().lf_dist_routing_substeps_fused(r._h, r._ch, C.byref(self.args), C.c_int(nsteps), C.c_int64(0),
-                                                   C.c_int(r.rank_top), C.c_int(r.rank_bottom)))
+        check(lib().lf_dist_routing_substeps_fused(r._h, r._ch, C.byref(self.args), nsteps, 0, r.rank_top,
+                                                   r.rank_bottom))
 
     def fused_prepare(self, nsteps):
-        check(lib().lf_dist_fused_prepare(self.router._h, C.byref(self.args), C.c_int(nsteps)))
+        check(lib().lf_dist_fused_prepare(self.router._h, C.byref(self.args), nsteps))
 
     def fused_phase(self, nsteps, phase):
-        check(lib().lf_dist_fused_phase(self.router._h, C.byref(self.args), C.c_int(nsteps), C.c_int64(0), C.c_int(phase)))
+        check(lib().lf_dist_fused_phase(self.router._h, C.byref(self.args), nsteps, 0, phase))
 
     # --- several model steps per call: the sub-steps of all of them as one wavefront per phase, one halo block per phase ----
     def _model_step_args(self, sums, sideflows):
@@ -682,23 +672,22 @@ class DistRoutingStep:
         [nmodel, N] in the rank's engine order, or None for the resident vector in every model step."""
         r = self.router
         a, stride = self._model_step_args(sums, sideflows)
-        check(lib().lf_dist_routing_model_steps_fused(r._h, r._ch, C.byref(a), C.c_int(nsteps), C.c_int(nmodel), C.c_int64(stride),
-                                                      C.c_int(r.rank_top), C.c_int(r.rank_bottom)))
+        check(lib().lf_dist_routing_model_steps_fused(r._h, r._ch, C.byref(a), nsteps, nmodel, stride, r.rank_top,
+                                                      r.rank_bottom))
 
     def fused_phase_model_steps(self, nsteps, nmodel, phase, sums, sideflows=None):
         a, stride = self._model_step_args(sums, sideflows)
-        check(lib().lf_dist_fused_phase_model_steps(self.router._h, C.byref(a), C.c_int(nsteps), C.c_int(nmodel),
-                                                    C.c_int64(stride), C.c_int(phase)))
+        check(lib().lf_dist_fused_phase_model_steps(self.router._h, C.byref(a), nsteps, nmodel, stride, phase))
 
     def fused_halo_block(self, rnd, side):
         """(send offset, send count, recv offset, recv count) in doubles inside the slab of a section"""
         o = (C.c_int64 * 4)()
-        check(lib().lf_dist_fused_halo_block(self.router._h, C.c_int(rnd), C.c_int(side), o))
+        check(lib().lf_dist_fused_halo_block(self.router._h, rnd, side, o))
         return tuple(int(x) for x in o)
 
     def fused_slab(self, section):
         p = C.c_void_p()
-        check(lib().lf_dist_fused_slab(self.router._h, C.c_int(section), C.byref(p)))
+        check(lib().lf_dist_fused_slab(self.router._h, section, C.byref(p)))
         return p.value or 0
 
     def download(self, name):
@@ -737,16 +726,16 @@ def loopback_substeps_fused(steps, nsteps, lanes=False):
         s.fused_prepare(nsteps)
     for j in range(nph):
         if lanes:
-            check(L.lf_lane_fork(C.c_int(dev)))
+            check(L.lf_lane_fork(dev))
         try:
             for k, s in enumerate(steps):
                 if lanes:
-                    check(L.lf_lane_select(C.c_int(dev), C.c_int(k + 1)))
+                    check(L.lf_lane_select(dev, k + 1))
                 s.fused_phase(nsteps, j)
         finally:
             if lanes:
-                check(L.lf_lane_select(C.c_int(dev), C.c_int(0)))
-                check(L.lf_lane_join(C.c_int(dev)))
+                check(L.lf_lane_select(dev, 0))
+                check(L.lf_lane_join(dev))
         if j + 1 < nph:
             _loopback_halo(steps, j)
 
@@ -765,8 +754,7 @@ def _loopback_halo(steps, j):
                     continue
                 so, sc, _ro, _rc = blocks[src_rank][src_side]
                 assert sc == rc, (k, j, side, sc, rc)
-                check(lib().lf_memcpy_d2d(C.c_int(dev), C.c_void_p(slabs[k] + 8 * ro),
-                                          C.c_void_p(slabs[src_rank] + 8 * so), C.c_size_t(8 * rc)))
+                check(lib().lf_memcpy_d2d(dev, slabs[k] + 8 * ro, slabs[src_rank] + 8 * so, 8 * rc))
 
 
 def loopback_model_steps_fused(steps, nsteps, nmodel, sums, sideflows=None, lanes=True):
@@ -782,16 +770,16 @@ def loopback_model_steps_fused(steps, nsteps, nmodel, sums, sideflows=None, lane
         s.fused_prepare(nsteps * nmodel)
     for j in range(nph):
         if lanes:
-            check(L.lf_lane_fork(C.c_int(dev)))
+            check(L.lf_lane_fork(dev))
         try:
             for k, s in enumerate(steps):
                 if lanes:
-                    check(L.lf_lane_select(C.c_int(dev), C.c_int(k + 1)))
+                    check(L.lf_lane_select(dev, k + 1))
                 s.fused_phase_model_steps(nsteps, nmodel, j, sums[k], None if sideflows is None else sideflows[k])
         finally:
             if lanes:
-                check(L.lf_lane_select(C.c_int(dev), C.c_int(0)))
-                check(L.lf_lane_join(C.c_int(dev)))
+                check(L.lf_lane_select(dev, 0))
+                check(L.lf_lane_join(dev))
         if j + 1 < nph:
             _loopback_halo(steps, j)
 
@@ -829,8 +817,7 @@ def loopback_route_many(routers, q_states, lat_lists, late_halo=False, section="
                     continue
                 sp, sn = sends[src_rank][src_side]
                 assert sn == n
-                check(lib().lf_memcpy_d2d(C.c_int(dev), C.c_void_p(out[k].ptr.value + 8 * slot), C.c_void_p(sp),
-                                          C.c_size_t(8 * n)))
+                check(lib().lf_memcpy_d2d(dev, out[k].ptr.value + 8 * slot, sp, 8 * n))
 
     def issue_round(c, j):
         if j + 1 >= P:
@@ -859,7 +846,7 @@ def loopback_route_many(routers, q_states, lat_lists, late_halo=False, section="
         for k in range(R):
             n = routers[k].num_pixels
             if n:
-                check(lib().lf_memcpy_d2d(C.c_int(dev), q_states[k].ptr, second[k].ptr, C.c_size_t(8 * n)))
+                check(lib().lf_memcpy_d2d(dev, q_states[k].ptr, second[k].ptr, 8 * n))
     _lib.synchronize(dev)
     for d in second:
         d.free()
@@ -896,5 +883,4 @@ def loopback_route(routers, q_states, lat_states, section="main_channel", overla
                         continue
                     sp, sn = sends[src_rank][src_side]
                     assert sn == n, (k, j, side, sn, n)
-                    dst = C.c_void_p(q_states[k].ptr.value + 8 * slot)
-                    check(lib().lf_memcpy_d2d(C.c_int(dev), dst, C.c_void_p(sp), C.c_size_t(8 * n)))
+                    check(lib().lf_memcpy_d2d(dev, q_states[k].ptr.value + 8 * slot, sp, 8 * n))

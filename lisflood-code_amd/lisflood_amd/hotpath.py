@@ -12,6 +12,7 @@ device buffers from one stage to the next.  Channel vectors live in the channel 
 vector that crosses from the surface graph to the channel graph (ToChanM3RunoffDt) is permuted on the device.
 """
 import ctypes as C
+import os
 import types
 
 import numpy as np
@@ -20,7 +21,7 @@ from . import pixel_aggregates as PA
 from . import routing as RT
 from . import soilloop as SL
 from . import surface_routing as SR
-from ._lib import DeviceArray, check, f64, lib, u8
+from ._lib import DeviceArray, PinnedArray, check, f64, lib, timer_start, timer_stop, u8
 from .kinematic_wave_parallel import Graph, kinematicWave
 
 FORCING = ("Rain", "SnowMelt", "EWRef", "ETRef", "ESRef")
@@ -69,7 +70,6 @@ class HotPathDevice:
         # land_fused: canopy + ESMax + soil columns as ONE pass over the columns (lf_land_columns_device; the three prescribed
         # fractions map to their own land-use rows, which is what it needs).  None: on, unless LF_LAND_FUSED=0 (A/B switch);
         # False: the three separate launches of rounds 1-5 -- same bits either way
-        import os
         self.land_fused = (os.environ.get("LF_LAND_FUSED", "1") != "0") if land_fused is None else bool(land_fused)
         # report: which of the OPTIONAL maps (OPTIONAL_MAPS below: diagnostics and cumulative sums nothing else on the hot
         # path reads) are wanted.  None: all of them, as the reference computes them every step; an iterable of names: only
@@ -245,8 +245,7 @@ class HotPathDevice:
         rows = a.reshape(-1, N)
         for r in range(rows.shape[0]):
             self._perm_tmp.upload(np.ascontiguousarray(rows[r]))
-            check(L.lf_gather_device(C.c_int(dev), C.c_int64(N), self._perm_idx.ptr, self._perm_tmp.ptr,
-                                     C.c_void_p(dst.ptr.value + r * N * 8)))
+            check(L.lf_gather_device(dev, N, self._perm_idx.ptr, self._perm_tmp.ptr, dst.ptr.value + r * N * 8))
         return dst
 
     def _ordered(self, a):
@@ -270,15 +269,15 @@ class HotPathDevice:
         L, dev = lib(), self.device
         as_is = lambda a: np.ascontiguousarray(a) if np.asarray(a).dtype == np.float32 else f64(a)
         host = [as_is(forcing[k]) if ordered else as_is(self._ordered(forcing[k])) for k in FORCING]
-        check(L.lf_upload_begin(C.c_int(dev), C.c_int(b)))
+        check(L.lf_upload_begin(dev, b))
         for k, a in zip(FORCING, host):
             if a.size != self.N:
                 raise ValueError("forcing vector %s must have %d entries" % (k, self.N))
             if a.dtype == np.float32:
-                check(L.lf_upload_copy_f32(C.c_int(dev), self.force[b][k].ptr, a.ctypes.data_as(C.c_void_p), C.c_size_t(a.size)))
+                check(L.lf_upload_copy_f32(dev, self.force[b][k].ptr, a.ctypes.data_as(C.c_void_p), a.size))
                 continue
-            check(L.lf_upload_copy(C.c_int(dev), self.force[b][k].ptr, a.ctypes.data_as(C.c_void_p), C.c_size_t(a.nbytes)))
-        check(L.lf_upload_end(C.c_int(dev), C.c_int(b)))
+            check(L.lf_upload_copy(dev, self.force[b][k].ptr, a.ctypes.data_as(C.c_void_p), a.nbytes))
+        check(L.lf_upload_end(dev, b))
         self._keep[b] = host                 # the host vectors stay alive until the set is uploaded again
 
     def pinned_forcing(self, dtype=np.float64):
@@ -287,7 +286,6 @@ class HotPathDevice:
         PCIe rate instead of a staged, blocking copy.  The arrays belong to this object (freed by free()).
         The DMA reads the arrays AFTER prefetch() / step() has returned: call upload_wait() before writing the next
         time step into a set that was handed over (or alternate between two pinned sets and wait before reuse)."""
-        from ._lib import PinnedArray
         bufs = {k: PinnedArray(self.N, dtype, self.device) for k in FORCING}
         self.__dict__.setdefault("_pinned", []).append(bufs)
         return {k: b.a for k, b in bufs.items()}
@@ -296,7 +294,7 @@ class HotPathDevice:
         """Block until the forcing uploads started by prefetch() / step() have left the host arrays (lf_upload_wait):
         after it the arrays of pinned_forcing() may be refilled in place.  buffer_set: 0 / 1, default both."""
         for b in ((0, 1) if buffer_set is None else (int(buffer_set),)):
-            check(lib().lf_upload_wait(C.c_int(self.device), C.c_int(b)))
+            check(lib().lf_upload_wait(self.device, b))
 
     def prefetch(self, forcing, ordered=False):
         """Start uploading the forcing of the NEXT step() call now: the copies run on a second stream while the kernels
@@ -318,7 +316,7 @@ class HotPathDevice:
         """The prescribed leaf area index of the coming steps: what leafarea.dynamic sets once per ten-day interval
         (leafarea.py:80-91: LAI of the interval, LAITerm = exp(-kgb * LAI)), [3, N] each, pixel order.  Waits for the
         step in flight (its canopy kernel reads the vectors)."""
-        check(lib().lf_device_synchronize(C.c_int(self.device)))
+        check(lib().lf_device_synchronize(self.device))
         for k, a in (("LAI", LAI), ("LAITerm", LAITerm)):
             a = np.asarray(a, np.float64)
             if a.shape != (3, self.N):
@@ -343,7 +341,7 @@ class HotPathDevice:
         # Only the channel wavefront reads the two vectors: they go up on ITS stream (the side stream when the wavefront
         # runs there), behind the wavefront of the step before and ahead of the next one, without a host wait and without
         # making the main stream wait for the side stream (lf_memcpy_h2d would do both)
-        L, d = lib(), C.c_int(self.device)
+        L, d = lib(), self.device
         side = self.overlap_channel
         if side:
             check(L.lf_side_stream_begin(d))
@@ -356,10 +354,12 @@ class HotPathDevice:
         self._qin_old = q
 
     def step(self, forcing, time_since_start=None, QInM3=None, ordered=False):
-        d, dev = self.d, self.device
-        L = lib()
         if QInM3 is not None:
             self.set_inflow(QInM3)
+        self._step(forcing, time_since_start, ordered)
+
+    def _step(self, forcing, time_since_start, ordered, stage_ms=None):
+        L, dev = lib(), self.device
         b = self.steps_done % 2
         if forcing is None:          # the vectors this buffer set already holds (uploaded for an earlier step): no PCIe traffic
             if self._keep[b] is None:
@@ -367,19 +367,18 @@ class HotPathDevice:
         elif self._prefetched[b] is not forcing:
             self._upload(b, forcing, ordered)
         self._prefetched[b] = None
-        check(L.lf_compute_acquire(C.c_int(dev), C.c_int(b)))
+        check(L.lf_compute_acquire(dev, b))
         self._use_set(b)
         try:
-            self._enqueue(time_since_start)
+            self._enqueue(time_since_start, stage_ms)
         finally:
-            check(L.lf_compute_release(C.c_int(dev), C.c_int(b)))
+            check(L.lf_compute_release(dev, b))
 
     def _enqueue(self, time_since_start, stage_ms=None):
         """stage_ms: a dict -> every stage is bracketed by the device stopwatch (which synchronises) and its
         milliseconds are added under its name; the channel wavefront then runs on the main stream (step_profile)."""
         d, dev = self.d, self.device
         L = lib()
-        from . import _lib as LB
 
         class stage:                       # `with stage("soil"):` -- a no-op unless stage_ms was passed
             def __init__(self, name):
@@ -387,30 +386,29 @@ class HotPathDevice:
 
             def __enter__(self):
                 if stage_ms is not None:
-                    LB.timer_start(dev)
+                    timer_start(dev)
 
             def __exit__(self, *exc):
                 if stage_ms is not None and exc[0] is None:
-                    stage_ms[self.name] = stage_ms.get(self.name, 0.0) + LB.timer_stop(dev)
+                    stage_ms[self.name] = stage_ms.get(self.name, 0.0) + timer_stop(dev)
                 return False
         if self.land_fused:
             # canopy, ESMax and the soil columns in ONE pass (k_soil_fused<.., CANOPY>): the lane that runs a column's canopy
             # carries LeafDrainage / Interception / W1a / W1b / W1 / ESMax into its soil water balance in registers
             with stage("land_surface"):
-                check(L.lf_land_columns_device(C.c_int(dev), C.byref(self.canopy), C.byref(self.soil), d["ESRef"].ptr,
-                                               C.c_int(1 if self.soil_derived else 0)))                 # dyn.py:114-123
+                check(L.lf_land_columns_device(dev, C.byref(self.canopy), C.byref(self.soil), d["ESRef"].ptr,
+                                               1 if self.soil_derived else 0))                         # dyn.py:114-123
         else:
             with stage("canopy"):
-                check(L.lf_canopy_device(C.c_int(dev), C.byref(self.canopy)))                           # dyn.py:114
-                check(L.lf_scale_rows_device(C.c_int(dev), d["ESRef"].ptr, d["LAITerm"].ptr, d["ESMax"].ptr,
-                                             C.c_int64(3), C.c_int64(self.N)))                         # soilloop.py:638
+                check(L.lf_canopy_device(dev, C.byref(self.canopy)))                                    # dyn.py:114
+                check(L.lf_scale_rows_device(dev, d["ESRef"].ptr, d["LAITerm"].ptr, d["ESMax"].ptr, 3, self.N))  # soilloop.py:638
             with stage("soil_columns"):
                 soil_fn = L.lf_soil_columns_device_derived if self.soil_derived else L.lf_soil_columns_device
-                check(soil_fn(C.c_int(dev), C.byref(self.soil)))                                        # dyn.py:123
+                check(soil_fn(dev, C.byref(self.soil)))                                                 # dyn.py:123
         self.steps_done += 1
         self.pixel.TimeSinceStart = float(time_since_start if time_since_start else self.steps_done)
         with stage("pixel_aggregates"):
-            check(L.lf_pixel_aggregates_device(C.c_int(dev), C.byref(self.pixel)))                      # dyn.py:129-149
+            check(L.lf_pixel_aggregates_device(dev, C.byref(self.pixel)))                               # dyn.py:129-149
         with stage("overland"):
             step_fn = L.lf_surface_step_ordered if self.pixel_of_position is not None else L.lf_surface_step
             check(step_fn(self.r_direct._h, self.r_other._h, self.r_forest._h, C.byref(self.surface)))   # dyn.py:165
@@ -418,46 +416,35 @@ class HotPathDevice:
         # step's canopy / soil / aggregate / overland kernels reads a channel vector: it runs on the side stream, beside
         # them (a latency-bound chain of small launches beside bandwidth-bound streaming kernels).  Before the gather
         # overwrites the sideflow the main stream waits for the wavefront of the step before; downloads join by themselves.
-        check(L.lf_side_stream_join(C.c_int(dev)))
+        check(L.lf_side_stream_join(dev))
         with stage("sideflow_gather"):
             if self.rmod is not None:       # lakes / reservoirs / inflow / transmission loss inside the wavefront
                 m = self.rmod
-                check(L.lf_gather_device(C.c_int(dev), C.c_int64(self.Nk), self._gidx.ptr, d["ToChanM3RunoffDt"].ptr,
+                check(L.lf_gather_device(dev, self.Nk, self._gidx.ptr, d["ToChanM3RunoffDt"].ptr,
                                          m._st["dev"]["ToChanM3RunoffDt"].ptr))
             else:
-                check(L.lf_gather_device(C.c_int(dev), C.c_int64(self.Nk), self._gidx.ptr, d["ToChanM3RunoffDt"].ptr,
+                check(L.lf_gather_device(dev, self.Nk, self._gidx.ptr, d["ToChanM3RunoffDt"].ptr,
                                          d["SideflowChanM3"].ptr))
         side = self.overlap_channel and stage_ms is None
         if side:
-            check(L.lf_side_stream_begin(C.c_int(dev)))
+            check(L.lf_side_stream_begin(dev))
         try:
             with stage("channel_wavefront"):
                 d["sumDisDay"].zero()                                                                   # dyn.py:177
                 if self.rmod is not None:
                     m = self.rmod
                     check(L.lf_routing_substeps_fused_structures(self.river._h, C.byref(m._args), C.byref(m._inloop),
-                                                                 C.c_int(int(self.sc["NoRoutSteps"]))))  # dyn.py:179-180
+                                                                 int(self.sc["NoRoutSteps"])))           # dyn.py:179-180
                 else:
-                    check(L.lf_routing_substeps_fused(self.river._h, C.byref(self.rout), C.c_int(int(self.sc["NoRoutSteps"])),
-                                                      C.c_int64(0)))                                    # dyn.py:179-180
+                    check(L.lf_routing_substeps_fused(self.river._h, C.byref(self.rout), int(self.sc["NoRoutSteps"]), 0))
         finally:
             if side:
-                check(L.lf_side_stream_end(C.c_int(dev)))
+                check(L.lf_side_stream_end(dev))
 
     def step_profile(self, forcing, time_since_start=None, ordered=False):
         """step() with every stage timed on its own (synchronising; no overlap between the stages) -> {stage: ms}"""
-        L, dev = lib(), self.device
-        b = self.steps_done % 2
-        if self._prefetched[b] is not forcing:
-            self._upload(b, forcing, ordered)
-        self._prefetched[b] = None
-        check(L.lf_compute_acquire(C.c_int(dev), C.c_int(b)))
-        self._use_set(b)
         ms = {}
-        try:
-            self._enqueue(time_since_start, ms)
-        finally:
-            check(L.lf_compute_release(C.c_int(dev), C.c_int(b)))
+        self._step(forcing, time_since_start, ordered, ms)
         return ms
 
     def stage_bytes(self):
@@ -720,8 +707,7 @@ class HotPathDevice:
             a.free()
         for r in (self.r_other, self.r_forest, self.r_direct, self.river):
             r.close()
-        _lib_sync = lib().lf_device_synchronize
-        check(_lib_sync(C.c_int(self.device)))       # no upload may still be reading the page-locked buffers
+        check(lib().lf_device_synchronize(self.device))       # no upload may still be reading the page-locked buffers
         for bufs in self.__dict__.pop("_pinned", []):
             for b in bufs.values():
                 b.free()

@@ -35,7 +35,7 @@ class Graph:
             r = np.ascontiguousarray(ldd_raster, dtype=np.uint8)
             H, W = r.shape
             m = None if land_mask is None else u8(land_mask)
-            check(lib().lf_graph_create_raster(ptr(r), ptr(m), C.c_int(H), C.c_int(W), C.byref(self._h)))
+            check(lib().lf_graph_create_raster(ptr(r), ptr(m), H, W, C.byref(self._h)))
         else:
             land_mask = np.asarray(land_mask)
             H, W = land_mask.shape
@@ -47,7 +47,7 @@ class Graph:
             vd = None if virtual_down is None else np.ascontiguousarray(virtual_down, dtype=np.int64)
             if vd is not None and vd.size != codes.size:
                 raise ValueError("virtual_down needs one entry per land pixel")
-            check(lib().lf_graph_create_ex(ptr(codes), ptr(m), C.c_int(H), C.c_int(W), ptr(vd), C.byref(self._h)))
+            check(lib().lf_graph_create_ex(ptr(codes), ptr(m), H, W, ptr(vd), C.byref(self._h)))
         self.shape = (H, W)
         self.num_pixels = int(lib().lf_graph_num_pixels(self._h))
         self.num_levels = int(lib().lf_graph_num_levels(self._h))
@@ -114,8 +114,8 @@ class kinematicWave:
             dx, dxs = f64(space_delta), 0.0
         a2 = None if alpha_floodplains is None else f64(np.broadcast_to(alpha_floodplains, (N,)))
         self._h = C.c_void_p()
-        check(lib().lf_router_create(self.graph._h, ptr(alpha), C.c_double(beta), ptr(dx), C.c_double(dxs),
-                                     C.c_double(time_delta), ptr(a2), C.c_int(device), C.byref(self._h)))
+        check(lib().lf_router_create(self.graph._h, ptr(alpha), beta, ptr(dx), dxs, time_delta, ptr(a2), device,
+                                     C.byref(self._h)))
         self._lookups = None
         self._orders = None
 
@@ -165,7 +165,7 @@ class kinematicWave:
         q = f64(np.broadcast_to(specific_lateral_inflow, (self.num_pixels,)))
         if self.num_pixels == 0:
             return
-        check(lib().lf_router_route_host(self._h, ptr(discharge), ptr(q), C.c_int(sec)))
+        check(lib().lf_router_route_host(self._h, ptr(discharge), ptr(q), sec))
         if self.flagnancheck and not self.kinematic_wave_warning_printed:
             if not np.all(np.isfinite(discharge)):
                 self._warn()
@@ -173,11 +173,10 @@ class kinematicWave:
     def route_device(self, discharge_dev, lateral_dev, section="main_channel"):
         """Device-resident form: DeviceArray vectors in pixel order; asynchronous."""
         sec = self._section(section)
-        check(lib().lf_router_route_device(self._h, discharge_dev.ptr, lateral_dev.ptr, C.c_int(sec)))
+        check(lib().lf_router_route_device(self._h, discharge_dev.ptr, lateral_dev.ptr, sec))
         if self.flagnancheck and not self.kinematic_wave_warning_printed:
             n = C.c_int64(0)
-            check(lib().lf_count_nonfinite(C.c_int(self.device), discharge_dev.ptr, C.c_int64(self.num_pixels),
-                                           C.byref(n)))
+            check(lib().lf_count_nonfinite(self.device, discharge_dev.ptr, self.num_pixels, C.byref(n)))
             if n.value:
                 self._warn()
 
@@ -197,7 +196,7 @@ class kinematicWave:
     def route_ordered(self, discharge_ord_dev, lateral_ord_dev, section="main_channel"):
         """Engine-order resident form: both DeviceArrays are in sweep order, discharge is updated in place."""
         sec = self._section(section)
-        check(lib().lf_router_route_ordered(self._h, discharge_ord_dev.ptr, lateral_ord_dev.ptr, C.c_int(sec)))
+        check(lib().lf_router_route_ordered(self._h, discharge_ord_dev.ptr, lateral_ord_dev.ptr, sec))
 
     @staticmethod
     def route_together(routers, discharge_devs, lateral_devs, section="main_channel", engine_order=False):
@@ -209,7 +208,7 @@ class kinematicWave:
         hs = (C.c_void_p * n)(*[r._h for r in routers])
         qs = (C.c_void_p * n)(*[q.ptr for q in discharge_devs])
         ls = (C.c_void_p * n)(*[x.ptr for x in lateral_devs])
-        check(lib().lf_router_route_device_multi(C.c_int(n), hs, qs, ls, C.c_int(sec), C.c_int(1 if engine_order else 0)))
+        check(lib().lf_router_route_device_multi(n, hs, qs, ls, sec, 1 if engine_order else 0))
 
     def _warn(self):
         self.kinematic_wave_warning_printed = True
@@ -249,11 +248,11 @@ class kinematicWave:
                     lane_use=(s[4] / (64.0 * s[3]) if s[3] else 0.0))
 
     def profile(self, on):
-        check(lib().lf_router_profile_enable(self._h, C.c_int(1 if on else 0)))
+        check(lib().lf_router_profile_enable(self._h, 1 if on else 0))
 
     def profile_read(self, reset=True):
         o = (C.c_double * 9)()
-        check(lib().lf_router_profile_read(self._h, o, C.c_int(1 if reset else 0)))
+        check(lib().lf_router_profile_read(self._h, o, 1 if reset else 0))
         names = ("prep", "wide_level", "narrow_run")
         return {names[i]: dict(launches=o[3 * i], ms=o[3 * i + 1], cells=o[3 * i + 2]) for i in range(3)}
 

@@ -213,7 +213,7 @@ def upstream_raster(ldd_raster, w_raster, device=0):
     H, W = ldd_raster.shape
     d_l, d_w = DeviceArray.from_host(ldd_raster, device), DeviceArray.from_host(w_raster, device)
     d_o = DeviceArray((H, W), np.float64, device)
-    check(lib().lf_upstream_sum_raster_device(C.c_int(device), d_l.ptr, d_w.ptr, d_o.ptr, C.c_int(H), C.c_int(W)))
+    check(lib().lf_upstream_sum_raster_device(device, d_l.ptr, d_w.ptr, d_o.ptr, H, W))
     out = d_o.download()
     for d in (d_l, d_w, d_o):
         d.free()
@@ -238,7 +238,7 @@ def _raster_op(ldd_raster, keep_raster, device):
     H, W = ldd_raster.shape
     out = np.empty((H, W), np.uint8)
     keep = None if keep_raster is None else np.ascontiguousarray(keep_raster, np.uint8)
-    check(lib().lf_ldd_raster_host(C.c_int(device), ptr(ldd_raster), ptr(keep), ptr(out), C.c_int(H), C.c_int(W)))
+    check(lib().lf_ldd_raster_host(device, ptr(ldd_raster), ptr(keep), ptr(out), H, W))
     return out
 
 
@@ -314,7 +314,7 @@ class LddDevice:
             chunk = f64(np.stack(ws[i:i + 4])) if self.N else np.zeros((len(ws[i:i + 4]), 0))
             res = np.empty_like(chunk)
             if self.N:
-                check(lib().lf_catchment_totals_multi_host(self.kw._h, C.c_int(chunk.shape[0]), ptr(chunk), ptr(res)))
+                check(lib().lf_catchment_totals_multi_host(self.kw._h, chunk.shape[0], ptr(chunk), ptr(res)))
             out.extend(res[k] for k in range(chunk.shape[0]))
         return out
 

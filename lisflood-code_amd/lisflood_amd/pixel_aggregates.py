@@ -51,7 +51,7 @@ def dynamic(var, device=0):
     for k, d in dev.items():
         setattr(a, k, d.ptr.value)
     a.InvDtDay, a.TimeSinceStart, a.N = float(v.InvDtDay), float(v.TimeSinceStart), N
-    check(lib().lf_pixel_aggregates_device(C.c_int(device), C.byref(a)))
+    check(lib().lf_pixel_aggregates_device(device, C.byref(a)))
     for k in _STATE + _OUT:
         setattr(v, k, dev[k].download())
     th = dev["Theta"].download()

@@ -633,7 +633,7 @@ class routing(HydroModule):
                 setattr(a, k, st["dev"][k].ptr.value)
         a.step = int(s)
         if launch:
-            check(lib().lf_inloop_structures(C.c_int(self.device), C.byref(a)))
+            check(lib().lf_inloop_structures(self.device, C.byref(a)))
 
     def _structures_download(self, s):
         v, st = self.var, self._st
@@ -687,7 +687,7 @@ class routing(HydroModule):
         self._structures_substep(0, launch=False)      # site state + the dense terms of the sideflow, once
         self._args.split = 1 if self._split() else 0
         check(lib().lf_routing_substeps_fused_structures(self.river_router._h, C.byref(self._args),
-                                                         C.byref(self._inloop), C.c_int(nsteps)))
+                                                         C.byref(self._inloop), nsteps))
         if not self._resident:
             self._download_state()
         self._structures_download(nsteps - 1)
@@ -718,7 +718,7 @@ class routing(HydroModule):
             self._dev["SideflowChanM3"].upload(f64(self._up(self.sideflow_m3())))
         self._args.split = 1 if self._split() else 0
         if self.engine_order:       # one level sweep updating both routers of a cell (one sub-step of the wavefront)
-            check(lib().lf_routing_substeps_fused(self.river_router._h, C.byref(self._args), C.c_int(1), C.c_int64(0)))
+            check(lib().lf_routing_substeps_fused(self.river_router._h, C.byref(self._args), 1, 0))
         else:
             check(lib().lf_routing_substep(self.river_router._h, C.byref(self._args)))
         if not self._resident:
@@ -746,7 +746,7 @@ def _fused(self, sideflows):
         raise ValueError("need one sideflow vector, or NoRoutSteps of them")
     sv = SubstepVectors(substep_host_vectors(v, N, perm), Nk, v.Beta, v.InvDtRouting, v.DtSec, self._split(), True,
                         self.device, sideflow=sideflows[:, perm])
-    check(lib().lf_routing_substeps_fused(r._h, C.byref(sv.args), C.c_int(nsteps), C.c_int64(stride)))
+    check(lib().lf_routing_substeps_fused(r._h, C.byref(sv.args), nsteps, stride))
     for k in result_names(self._split()):
         out = np.zeros(N)                # pixels outside a compact domain keep their zero state
         out[perm] = sv.download(k)[:Nk]

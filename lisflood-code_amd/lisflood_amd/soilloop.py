@@ -65,7 +65,7 @@ def interception_water_balance(Interception, TaInterception, LeafDrainage, CumIn
                        "TaInterceptionMax"), keep):
         setattr(a, k, arr.ctypes.data)
     a.drainageK, a.V, a.N = float(drainageK), V, N
-    check(lib().lf_interception_host(C.c_int(device), C.byref(a)))
+    check(lib().lf_interception_host(device, C.byref(a)))
 
 
 def potentialTranspiration(TranspirMax, TaInterception):
@@ -105,7 +105,7 @@ def soilColumnsWaterBalance(*args, device=0):
     a.DtDay, a.AvWaterThreshold = float(d["DtDay"]), float(d["AvWaterThreshold"])
     a.CourantCrit, a.DrainedFraction = float(d["CourantCrit"]), float(d["DrainedFraction"])
     a.V, a.L, a.N = V, L, N
-    check(lib().lf_soil_columns_host(C.c_int(device), C.byref(a)))
+    check(lib().lf_soil_columns_host(device, C.byref(a)))
 
 
 def derived_parameters_hold(d):
@@ -158,13 +158,13 @@ class SoilColumnsDevice:
 
     def step(self):
         fn = lib().lf_soil_columns_device_derived if self.derived else lib().lf_soil_columns_device
-        check(fn(C.c_int(self.device), C.byref(self.args)))
+        check(fn(self.device, C.byref(self.args)))
 
     def substep_histogram(self, nbins=128):
         """hist[k] = columns of the last step that needed k Courant sub-steps, k >= 2 (columns with one sub-step are not
         listed; the engine keeps trip counts up to 127, the last bin holds the rest) -- lf_soil_substep_histogram"""
         hist = (C.c_int64 * nbins)()
-        check(lib().lf_soil_substep_histogram(C.c_int(self.device), hist, C.c_int(nbins)))
+        check(lib().lf_soil_substep_histogram(self.device, hist, nbins))
         return np.array(hist[:], dtype=np.int64)
 
     def get(self, name):
@@ -267,7 +267,7 @@ class soilloop(HydroModule):
                 a.WFilla, a.WFillb = fill[0].ptr.value, fill[1].ptr.value
                 a.WPF3a = self._cache.put_static("canopy.WPF3a", f64(_values(v.WPF3a))).ptr.value
                 a.WPF3b = self._cache.put_static("canopy.WPF3b", f64(_values(v.WPF3b))).ptr.value
-        check(lib().lf_canopy_device(C.c_int(self.device), C.byref(a)))
+        check(lib().lf_canopy_device(self.device, C.byref(a)))
         for k in _CANOPY_IO:
             dev[k].download(host[k])
         if stress is not None:
@@ -283,7 +283,7 @@ class soilloop(HydroModule):
         lt = self._cache.put("soil.LAITerm", f64(_values(v.LAITerm)))
         V = _values(v.LAITerm).shape[0]
         out = self._cache.get("soil.ESMax", (V, N))
-        check(lib().lf_scale_rows_device(C.c_int(self.device), es.ptr, lt.ptr, out.ptr, C.c_int64(V), C.c_int64(N)))
+        check(lib().lf_scale_rows_device(self.device, es.ptr, lt.ptr, out.ptr, V, N))
         # soilColumnsWaterBalance (soilloop.py:645-665) on cached device buffers: the static parameter maps ([L,N] soil
         # hydraulic parameters and the five [N] constants) are uploaded once, the state and forcing every call -- other
         # modules may have changed them on `var` --, the 22 written arrays come back in place
@@ -311,7 +311,7 @@ class soilloop(HydroModule):
         a.DtDay, a.AvWaterThreshold = float(v.DtDay), float(v.AvWaterThreshold)
         a.CourantCrit, a.DrainedFraction = float(v.CourantCrit), float(v.DrainedFraction)
         a.V, a.L, a.N = V, g("WS1a").shape[0], N
-        check(lib().lf_soil_columns_device(C.c_int(self.device), C.byref(a)))
+        check(lib().lf_soil_columns_device(self.device, C.byref(a)))
         for k, host in written.items():
             cache.buf["soil." + k].download(host)
         if self.options.get("simulatePF"):
@@ -341,7 +341,7 @@ class soilloop(HydroModule):
         a.index_landuse_all = idx.ctypes.data
         a.HeadMax = float(v.HeadMax)
         a.V, a.L, a.N = V, _values(v.WS1a).shape[0], N
-        check(lib().lf_soil_pf_device(C.c_int(self.device), C.byref(a)))
+        check(lib().lf_soil_pf_device(self.device, C.byref(a)))
         for k in outs:
             self._cache.buf["pf." + k].download(outs[k])
 

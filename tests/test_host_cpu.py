@@ -4,6 +4,8 @@ lookups/orders on the golden vectors, and compute entry points fail loudly witho
 import ctypes as C
 import os
 import re
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -21,6 +23,104 @@ def declared_symbols():
     text = open(HEADER).read()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     return sorted(set(re.findall(r"\b(lf_[a-z0-9_]+)\s*\(", text)))
+
+
+PARAM_KIND = {"int": "i", "unsigned int": "u", "int64_t": "q", "size_t": "z", "double": "d"}
+RETURN_KIND = {"int": "i", "int64_t": "q", "void": "v", "const char *": "s"}
+
+
+def declared_prototypes():
+    """name -> (return kind, parameter kinds) of every function the header declares, in the letters of _lib._SIGNATURES:
+    a parameter with a * or a [ is a pointer (p), every other one is named by its type"""
+    text = open(HEADER).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    text = re.sub(r"\{[^{}]*\}", "", text)                       # struct bodies
+    protos = {}
+    for ret, name, params in re.findall(r"\b(const char \*|int64_t|int|void)\s*\b(lf_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", text):
+        kinds = ""
+        for prm in ([] if params.strip() == "void" else params.split(",")):
+            prm = " ".join(prm.split())
+            kinds += "p" if "*" in prm or "[" in prm else PARAM_KIND[prm.rsplit(" ", 1)[0]]
+        assert name not in protos, name
+        protos[name] = (RETURN_KIND[ret], kinds)
+    return protos
+
+
+def table_prototypes():
+    protos = {}
+    for sig, names in _lib._SIGNATURES.items():
+        args, _, ret = sig.partition(">")
+        for name in names.split():
+            assert "lf_" + name not in protos, name
+            protos["lf_" + name] = (ret or "i", args)
+    return protos
+
+
+def test_signature_table_is_the_header():
+    """_lib._SIGNATURES against include/lisflood_amd.h, function by function and in both directions; the prototype parser
+    must have read every name the plain symbol scan finds, so a prototype it cannot read fails here instead of going
+    unchecked"""
+    header, table = declared_prototypes(), table_prototypes()
+    assert sorted(header) == declared_symbols()
+    assert sorted(set(header) - set(table)) == [], "only in the header"
+    assert sorted(set(table) - set(header)) == [], "only in the table"
+    for name in sorted(header):
+        assert table[name] == header[name], name
+    assert {k for _ret, args in header.values() for k in args} == set("piuqzd")
+    assert {ret for ret, _args in header.values()} == set("iqvs")
+    L = _lib.lib()
+    for name, (ret, args) in header.items():
+        f = getattr(L, name)
+        assert f.restype is _lib._KIND[ret] and list(f.argtypes) == [_lib._KIND[k] for k in args], name
+
+
+def test_symbol_missing_from_the_library_is_named(monkeypatch):
+    monkeypatch.setattr(_lib, "_SIGNATURES", dict(_lib._SIGNATURES, pq="no_such_entry_point"))
+    monkeypatch.setattr(_lib, "_lib", None)
+    with pytest.raises(_lib.LisfloodAmdError, match="lf_no_such_entry_point"):
+        _lib.lib()
+
+
+def test_wrong_argument_kinds_are_refused_before_the_call():
+    g = Graph(ldd_raster=syn.make_ldd("river", 24, 20, 4))
+    L = _lib.lib()
+    o = (C.c_int64 * 6)()
+    assert L.lf_graph_block_plan_stats(g._h, 16, 2**20, 64, o) == 0
+    with pytest.raises(C.ArgumentError):
+        L.lf_graph_get_links(g._h, 1.0)                                  # a float for a pointer
+    with pytest.raises(C.ArgumentError):
+        L.lf_graph_block_plan_stats(g._h, 16.0, 2**20, 64, o)            # a float for an int
+    with pytest.raises(C.ArgumentError):
+        L.lf_graph_block_plan_stats(g._h, 16, C.c_int(2**20), 64, o)     # a C int for an int64_t
+    with pytest.raises(C.ArgumentError):
+        L.lf_graph_num_pixels(np.int64(g._h.value))                      # a numpy integer for a pointer
+    g.close()
+
+
+def test_int64_argument_arrives_whole():
+    """no level of the 300 x 260 river graph (78 000 cells) reaches 2**20 cells, so wide = 2**40 plans it as wide = 2**20
+    does -- if all 64 bits of the plain Python int arrive (as a 32-bit int 2**40 is 0: every level would be a wide one)"""
+    g = Graph(ldd_raster=syn.make_ldd("river", 300, 260, 4))
+
+    def stats(wide):
+        o = (C.c_int64 * 6)()
+        _lib.check(_lib.lib().lf_graph_block_plan_stats(g._h, 16, wide, 64, o))
+        return list(o)
+    assert stats(2**40) == stats(2**20)
+    assert stats(2**20)[1] > 0 and stats(0) != stats(2**20)
+    g.close()
+
+
+def test_int64_return_types_do_not_wait_for_a_dist_graph():
+    code = ("import sys; sys.path.insert(0, %r)\n"
+            "import ctypes\n"
+            "from lisflood_amd import _lib, dist\n"
+            "L = _lib.lib()\n"
+            "assert L.lf_dist_router_last_launches.restype is ctypes.c_int64\n"
+            "assert L.lf_router_num_pixels.restype is ctypes.c_int64\n"
+            "print('RESTYPES_OK')\n" % os.path.join(ROOT, "lisflood-code_amd"))
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "RESTYPES_OK" in r.stdout, r.stdout[-1500:] + r.stderr[-1500:]
 
 
 def test_library_exports_every_declared_symbol():

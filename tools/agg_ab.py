@@ -24,7 +24,7 @@ for s in range(2):
     hp.step(f, s + 1, ordered=True)
 _lib.synchronize()
 L = lib()
-dev = C.c_int(hp.device)
+dev = hp.device
 nb = hp.stage_bytes()["pixel_aggregates"]
 for x in ("0", "1", "0", "1", "0", "1"):
     os.environ["LF_AGG_ALL"] = x

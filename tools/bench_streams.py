@@ -16,12 +16,12 @@ dst = _lib.DeviceArray(n).zero()
 ptrs = (C.c_void_p * 8)(*[s.ptr.value for s in srcs])
 for k in range(1, 9):
     for rep in range(3):
-        _lib.check(L.lf_calibration_streams(C.c_int(0), C.c_int(k), ptrs, dst.ptr, C.c_int64(n)))
+        _lib.check(L.lf_calibration_streams(0, k, ptrs, dst.ptr, n))
     _lib.synchronize()
     _lib.timer_start()
     reps = 20
     for rep in range(reps):
-        _lib.check(L.lf_calibration_streams(C.c_int(0), C.c_int(k), ptrs, dst.ptr, C.c_int64(n)))
+        _lib.check(L.lf_calibration_streams(0, k, ptrs, dst.ptr, n))
     ms = _lib.timer_stop() / reps
     print("%d read + 1 write streams of %d doubles: %.1f us  %.2f TB/s" % (k, n, ms * 1e3, (k + 1) * 8 * n / (ms * 1e-3) / 1e12),
           flush=True)
