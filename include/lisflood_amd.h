@@ -199,6 +199,16 @@ int lf_router_from_engine_order(lf_router *r, const double *src_ord_dev, double 
 /* (The first such call of a router with per-pixel channel lengths builds, per section, a 16-byte (alpha*dx/dt, dx) record per
  * cell on the device for its wide levels -- 16 N bytes that stay with the router; LF_LEVEL_STATICS=0 keeps the two vectors.) */
 int lf_router_route_ordered(lf_router *r, double *discharge_ord_dev, const double *lateral_ord_dev, int section);
+/* `members` (>= 1) state vectors of ONE router swept together: member m's discharge (in/out) is
+ * discharge_ord_dev + m * stride, its lateral inflow lateral_ord_dev + m * stride, both in sweep order,
+ * stride >= N in elements.  One launch per wide level / narrow run / level block for all members; each
+ * member's result is bit-identical to lf_router_route_ordered on that member alone.  Elements between N
+ * and stride are neither read nor written.  (General exponent: the router's `constant` grows to members * N.) */
+int lf_router_route_ordered_members(lf_router *r, double *discharge_ord_dev, const double *lateral_ord_dev,
+                                    int members, int64_t stride, int section);
+/* host form: discharge_host[members][N] in PIXEL order updated in place, lateral_host[members][N] */
+int lf_router_route_members_host(lf_router *r, double *discharge_host, const double *lateral_host,
+                                 int members, int section);
 /* nancheck (kinematic_wave_parallel.py:180-184): number of non-finite entries of a device vector. */
 int lf_count_nonfinite(int device, const double *x_dev, int64_t n, int64_t *count);
 /* launch statistics of the last route call: [0] kernel launches, [1] wide-level launches,

@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <string>
 #include <map>
+#include <utility>
 #include <vector>
 
 #include "../../include/lisflood_amd.h"
@@ -113,6 +114,20 @@ struct lf_dbuf { // owning device buffer
             p = nullptr;
             return lf_set_error(LF_E_HIP, "hipMalloc(%zu bytes) failed: %s", count * sizeof(T), hipGetErrorString(e));
         }
+        return LF_OK;
+    }
+    // A buffer of `count` elements in place of this one (contents not kept), for buffers that grow on demand: the new one
+    // is taken first, so when it does not fit this one is still whole -- p and n as they were -- and the caller can refuse
+    // its call and serve the next one.
+    int grow(size_t count)
+    {
+        lf_dbuf<T> next;
+        if (int rc = next.alloc(count)) {
+            (void)hipGetLastError(); // (the refused hipMalloc is reported here, not by the next call's launch check)
+            return rc;
+        }
+        std::swap(p, next.p);
+        std::swap(n, next.n);
         return LF_OK;
     }
     // `stream`: the stream the kernels that read the buffer run on.  The library's compute stream is non-blocking, i.e. it

@@ -176,6 +176,7 @@ __global__ void __launch_bounds__(kBlock) k_count_nonfinite(long long n, const d
 struct lf_router : lf_router_core {
     int64_t NL = 0;
     lf_dbuf<double> qord, io_q, io_lat, tmp_ord;
+    lf_dbuf<double> members_pix, members_ord; // lf_router_route_members_host: [2][members][N] discharge, lateral inflow
     lf_dbuf<unsigned long long> counter;
     lf_dbuf<uint8_t> linked; // zero-length structure links (lf_graph_create_ex); null without them
     lf_dbuf<int> level_nlinked; // ... and how many of them are parked at the end of every level (k_fused_cones_split)
@@ -381,14 +382,126 @@ int enqueue_route(int count, lf_router **rs, double **q_dev, const double **lat_
     return LF_OK;
 }
 
-int route_device(lf_router *r, double *q_dev, const double *lat_dev, int section, bool ordered = false)
+// the section exists and the graph has no structure links: what every plain router call asks of r
+int check_plain_call(const lf_router *r, int section)
 {
     LF_TRY(check_section(*r, section));
     if (r->linked.p)
         return lf_set_error(LF_E_INVALID, "a router on a graph with structure links (lf_graph_create_ex) runs only the "
                             "fused sub-step path (lf_routing_substeps_fused*)");
+    return LF_OK;
+}
+
+int route_device(lf_router *r, double *q_dev, const double *lat_dev, int section, bool ordered = false)
+{
+    LF_TRY(check_plain_call(r, section));
     LF_HIP(hipSetDevice(r->device));
     LF_TRY(enqueue_route(1, &r, &q_dev, &lat_dev, section, ordered));
+    LF_HIP(hipGetLastError());
+    if (r->profile) LF_TRY(r->prof_collect());
+    return LF_OK;
+}
+
+// ---- an ensemble on one router (lf_sweep.h: member_rows) ----------------------------------------------------------------
+// Members per lane of k_level_members, chosen by measurement on the shallow 10 000^2 graph: 4
+// members per lane sweep 4 and 8 members in 0.77 of the time of as many single calls, 2 per lane in 0.86, 1 per lane in
+// 0.98; two members are one short group either way (0.87).  LF_MEMBERS_MB = 1, 2 or 4, read at every call, is the A/B
+// switch of that measurement (tools/bench_route_members.py --mb).
+constexpr int kMembersPerLane = 4;
+int members_per_lane()
+{
+    if (const char *e = std::getenv("LF_MEMBERS_MB")) {
+        const int v = std::atoi(e);
+        if (v == 1 || v == 2 || v == 4) return v;
+    }
+    return kMembersPerLane;
+}
+constexpr int kMaxGridY = 65535; // blockIdx.y picks the member (cones) or the member group (wide levels)
+
+template <bool FUSED, int STATICS>
+void launch_level_members(int mb, unsigned blocks, int members, hipStream_t s, int first, int cells, const sweep_args &A,
+                          const member_rows &R)
+{
+    const dim3 grid(blocks, (unsigned)((members + mb - 1) / mb)), block(kLevelBlock);
+    if (mb == 1)
+        hipLaunchKernelGGL((k_level_members<FUSED, true, STATICS, 1>), grid, block, 0, s, first, cells, A, R);
+    else if (mb == 2)
+        hipLaunchKernelGGL((k_level_members<FUSED, true, STATICS, 2>), grid, block, 0, s, first, cells, A, R);
+    else
+        hipLaunchKernelGGL((k_level_members<FUSED, true, STATICS, 4>), grid, block, 0, s, first, cells, A, R);
+}
+
+// `members` rows of q_dev / lat_dev (sweep order, `stride` elements apart) swept on r's schedule: the plan, the
+// LF_ROUTE_CONES switch and the profile hooks of enqueue_route, every launch once for all members (more than kMaxGridY
+// of them: in slices).  The chain / supply cone kernel stays a single router's: here the members fill the machine.
+int enqueue_route_members(lf_router *r, double *q_dev, const double *lat_dev, int members, int64_t stride, int section)
+{
+    hipStream_t s = r->ctx->stream;
+    const int n = (int)r->N;
+    if (!r->fused && r->constant.n < (size_t)members * (size_t)n) {
+        LF_HIP(hipStreamSynchronize(s)); // (earlier calls read the buffer that goes)
+        LF_TRY(r->constant.grow((size_t)members * (size_t)n)); // (refused: r keeps the buffer it had, for fewer members)
+    }
+    const int mb = members_per_lane();
+    launch_counts c;
+    for (int m0 = 0; m0 < members; m0 += kMaxGridY) {
+        const int mm = std::min(members - m0, kMaxGridY);
+        sweep_args A = sweep_args_of(*r, section, q_dev + (int64_t)m0 * stride, nullptr, lat_dev + (int64_t)m0 * stride);
+        if (!r->fused) A.constant = r->constant.p + (int64_t)m0 * n;
+        const member_rows R{(long long)stride, (long long)n, mm};
+        if (!r->fused) {
+            LF_TRY(r->prof_begin(0, (int64_t)n * mm));
+            hipLaunchKernelGGL(k_prep_members, dim3(blocks_for(n), mm), dim3(kBlock), 0, s, n, A, R, (double *)A.constant);
+            LF_TRY(r->prof_end());
+            ++c.launches;
+        }
+        auto cones = [&](dim3 grid, const cone_plan_args &C, int64_t cells) {
+            LF_TRY(r->prof_begin(2, cells * mm));
+            grid.y = (unsigned)mm;
+            pick_flags(r->fused, r->rplan.cw == 64, [&](auto f, auto one_wavefront) {
+                constexpr int CW = one_wavefront ? 64 : kBlock;
+                hipLaunchKernelGGL((k_sweep_cones_members<f, true, CW>), grid, dim3(CW), 0, s, C, A, R);
+            });
+            return r->prof_end();
+        };
+        auto level = [&](int first, int cells) {
+            LF_TRY(r->prof_begin(1, (int64_t)cells * mm));
+            const unsigned blocks = (unsigned)level_blocks_for(cells);
+            sweep_args B = A;
+            if (r->fused) B.adx = level_statics(r, A);
+            if (B.adx)
+                launch_level_members<true, 1>(mb, blocks, mm, s, first, cells, B, R);
+            else if (r->fused)
+                launch_level_members<true, 0>(mb, blocks, mm, s, first, cells, B, R);
+            else
+                launch_level_members<false, 0>(mb, blocks, mm, s, first, cells, B, R);
+            return r->prof_end();
+        };
+        auto narrow = [&](int k0, int k1) {
+            LF_TRY(r->prof_begin(2, (r->h_level_start[k1] - r->h_level_start[k0]) * mm));
+            if (r->fused)
+                hipLaunchKernelGGL((k_levels_narrow_members<true, true>), dim3(mm), dim3(kNarrowBlock), 0, s, k0, k1, r->level_start.p, A, R);
+            else
+                hipLaunchKernelGGL((k_levels_narrow_members<false, true>), dim3(mm), dim3(kNarrowBlock), 0, s, k0, k1, r->level_start.p, A, R);
+            return r->prof_end();
+        };
+        LF_TRY(route_schedule(*r, 0, r->rplan.nblocks(), r->schedule, !r->rplan.empty(), c, cones, level, narrow));
+    }
+    r->last_stats[0] = c.launches;
+    r->last_stats[1] = c.wide;
+    r->last_stats[2] = c.narrow;
+    r->last_stats[3] = r->NL;
+    return LF_OK;
+}
+
+// (the arguments are checked by the caller: lf_router_route_ordered_members)
+int route_members(lf_router *r, double *q_dev, const double *lat_dev, int members, int64_t stride, int section)
+{
+    if (members == 1) return route_device(r, q_dev, lat_dev, section, true);
+    LF_TRY(check_plain_call(r, section));
+    if (r->N == 0) return LF_OK;
+    LF_HIP(hipSetDevice(r->device));
+    LF_TRY(enqueue_route_members(r, q_dev, lat_dev, members, stride, section));
     LF_HIP(hipGetLastError());
     if (r->profile) LF_TRY(r->prof_collect());
     return LF_OK;
@@ -610,6 +723,50 @@ int lf_router_route_ordered(lf_router *r, double *discharge_ord_dev, const doubl
 {
     if (!r || !discharge_ord_dev || !lateral_ord_dev) return lf_set_error(LF_E_INVALID, "null argument");
     return route_device(r, discharge_ord_dev, lateral_ord_dev, section, true);
+}
+
+// An ensemble on one router: `members` discharge / lateral-inflow rows that share r's static vectors and schedule, one
+// launch per wide level, narrow run or level block for all of them (enqueue_route_members).  The arguments are checked
+// before r or a device is touched as far as they can be.
+int lf_router_route_ordered_members(lf_router *r, double *discharge_ord_dev, const double *lateral_ord_dev, int members,
+                                    int64_t stride, int section)
+{
+    if (members < 1) return lf_set_error(LF_E_INVALID, "members must be at least 1 (got %d)", members);
+    if (stride < 0) return lf_set_error(LF_E_INVALID, "stride %lld is less than the router's number of cells", (long long)stride);
+    if (!r || !discharge_ord_dev || !lateral_ord_dev) return lf_set_error(LF_E_INVALID, "null argument");
+    if (stride < r->N)
+        return lf_set_error(LF_E_INVALID, "stride %lld is less than the router's number of cells (%lld)", (long long)stride,
+                            (long long)r->N);
+    return route_members(r, discharge_ord_dev, lateral_ord_dev, members, stride, section);
+}
+
+// ... from host arrays in pixel order: up, every row into sweep order, the member call, back (staging kept with r)
+int lf_router_route_members_host(lf_router *r, double *discharge_host, const double *lateral_host, int members, int section)
+{
+    if (members < 1) return lf_set_error(LF_E_INVALID, "members must be at least 1 (got %d)", members);
+    if (!r || !discharge_host || !lateral_host) return lf_set_error(LF_E_INVALID, "null argument");
+    LF_TRY(check_plain_call(r, section));
+    if (r->N == 0) return LF_OK;
+    LF_HIP(hipSetDevice(r->device));
+    hipStream_t s = r->ctx->stream;
+    const size_t n = (size_t)r->N, total = n * (size_t)members, bytes = sizeof(double) * total;
+    if (r->members_pix.n < 2 * total || r->members_ord.n < 2 * total) { // (each is whole whether or not the other grew)
+        LF_HIP(hipStreamSynchronize(s));
+        if (r->members_pix.n < 2 * total) LF_TRY(r->members_pix.grow(2 * total));
+        if (r->members_ord.n < 2 * total) LF_TRY(r->members_ord.grow(2 * total));
+    }
+    double *q_pix = r->members_pix.p, *lat_pix = q_pix + total, *q_ord = r->members_ord.p, *lat_ord = q_ord + total;
+    LF_HIP(hipMemcpyAsync(q_pix, discharge_host, bytes, hipMemcpyHostToDevice, s));
+    LF_HIP(hipMemcpyAsync(lat_pix, lateral_host, bytes, hipMemcpyHostToDevice, s));
+    for (size_t m = 0; m < (size_t)members; ++m) {
+        LF_TRY(core_to_engine_order(*r, q_pix + m * n, q_ord + m * n));
+        LF_TRY(core_to_engine_order(*r, lat_pix + m * n, lat_ord + m * n));
+    }
+    LF_TRY(route_members(r, q_ord, lat_ord, members, (int64_t)n, section));
+    for (size_t m = 0; m < (size_t)members; ++m) LF_TRY(core_from_engine_order(*r, q_ord + m * n, q_pix + m * n));
+    LF_HIP(hipMemcpyAsync(discharge_host, q_pix, bytes, hipMemcpyDeviceToHost, s));
+    LF_HIP(hipStreamSynchronize(s));
+    return LF_OK;
 }
 
 // dst[i] = src[index[i]] for i < n (device vectors; index is int32): the permutation between two domains, e.g. a

@@ -142,21 +142,12 @@ struct lf_rec24 {
 //   INDEXED: upstream positions come from the index list ups_idx[ups_ptr[p] .. ups_ptr[p+1]) instead of being the
 //     contiguous positions themselves (row-block partitions: upstream cells may sit in other phases or in the
 //     ghost slots filled by the halo exchange).
-template <bool FUSED, bool ORDERED, bool INDEXED = false, int STATICS = 0>
-__device__ __forceinline__ void sweep_cell_range(int p, int u0, int u1, const sweep_args &A)
+// What a cell reads of the router's static vectors -- the same for every member of an ensemble swept on one router: a, dx
+// (STATICS = 3, the partition's record with the upstream range in it: sweep_cell_range)
+template <bool FUSED, int STATICS>
+__device__ __forceinline__ void sweep_cell_statics(int p, const sweep_args &A, double &ap, double &dxp)
 {
-    static_assert(STATICS == 0 || (FUSED && ORDERED && INDEXED == (STATICS == 3)), "the records are the ordered beta = 3/5 router's");
-    const int pix = ORDERED ? p : A.perm[p];
-    double ap, dxp;
-    int rec_base = 0;
-    if (STATICS == 3) {
-        const lf_rec24 R = A.rec24[p];
-        ap = R.a;
-        dxp = R.dx;
-        u0 = (int)(R.up & 0x0fffffffu);
-        u1 = u0 + (int)(R.up >> 28);
-        rec_base = R.base;
-    } else if (STATICS == 1) {
+    if (STATICS == 1) {
         const double2 sd = A.adx[p];
         ap = sd.x;
         dxp = sd.y;
@@ -164,6 +155,11 @@ __device__ __forceinline__ void sweep_cell_range(int p, int u0, int u1, const sw
         ap = A.a[p];
         dxp = (FUSED && A.dx) ? A.dx[p] : A.dx_scalar;
     }
+}
+// ... and everything else of the cell: the state vectors of A (one member's), the solve, the store
+template <bool FUSED, bool ORDERED, bool INDEXED = false, int STATICS = 0>
+__device__ __forceinline__ void sweep_cell_state(int p, int pix, double ap, double dxp, int u0, int u1, int rec_base, const sweep_args &A)
+{
     // the cell's own two values first: requested with the statics above, before anything waits for the upstream range
     double lat_q = 0.0, qold = 0.0;
     if (FUSED) {
@@ -235,6 +231,25 @@ __device__ __forceinline__ void sweep_cell_range(int p, int u0, int u1, const sw
     }
     A.qord[p] = q;
     if (!ORDERED) A.q_pix[pix] = q;
+}
+template <bool FUSED, bool ORDERED, bool INDEXED = false, int STATICS = 0>
+__device__ __forceinline__ void sweep_cell_range(int p, int u0, int u1, const sweep_args &A)
+{
+    static_assert(STATICS == 0 || (FUSED && ORDERED && INDEXED == (STATICS == 3)), "the records are the ordered beta = 3/5 router's");
+    const int pix = ORDERED ? p : A.perm[p];
+    double ap, dxp;
+    int rec_base = 0;
+    if (STATICS == 3) {
+        const lf_rec24 R = A.rec24[p];
+        ap = R.a;
+        dxp = R.dx;
+        u0 = (int)(R.up & 0x0fffffffu);
+        u1 = u0 + (int)(R.up >> 28);
+        rec_base = R.base;
+    } else {
+        sweep_cell_statics<FUSED, STATICS>(p, A, ap, dxp);
+    }
+    sweep_cell_state<FUSED, ORDERED, INDEXED, STATICS>(p, pix, ap, dxp, u0, u1, rec_base, A);
 }
 template <bool FUSED, bool ORDERED, bool INDEXED = false, int STATICS = 0>
 __device__ __forceinline__ void sweep_cell(int p, const sweep_args &A)
@@ -354,12 +369,14 @@ __device__ __forceinline__ void cone_sync() // between the levels of a cone: wor
 }
 
 // CW: cells per level of a cone = threads of the workgroup (64: one wavefront, no barrier between the levels)
-template <bool FUSED, bool ORDERED, int NR, int CW = kBlock>
-__global__ void __launch_bounds__(CW) k_sweep_cones(cone_plan_args C, sweep_args_multi M)
+// (the kernel's body: cone `cone` of the block for the NR routers of M -- k_sweep_cones_members runs it on one member's
+// state vectors)
+template <bool FUSED, bool ORDERED, int NR, int CW>
+__device__ __forceinline__ void sweep_cone(unsigned cone, const cone_plan_args &C, const sweep_args_multi &M)
 {
     __shared__ double x[NR][2][CW];
     const int tid = threadIdx.x, nl = C.nl;
-    const int *c0 = C.cone + (size_t)blockIdx.x * nl, *c1 = c0 + nl;
+    const int *c0 = C.cone + (size_t)cone * nl, *c1 = c0 + nl;
     struct cell { // the operands of one cell as loaded: no arithmetic before the level that solves it (a product here
                   // would make the loads wait where they are issued)
         int u0, u1, pix;
@@ -488,6 +505,11 @@ __global__ void __launch_bounds__(CW) k_sweep_cones(cone_plan_args C, sweep_args
         l2 = l5;
     }
     flush();
+}
+template <bool FUSED, bool ORDERED, int NR, int CW = kBlock>
+__global__ void __launch_bounds__(CW) k_sweep_cones(cone_plan_args C, sweep_args_multi M)
+{
+    sweep_cone<FUSED, ORDERED, NR, CW>(blockIdx.x, C, M);
 }
 
 // The cone sweep with the work split between TWO wavefronts of a 128-thread workgroup (round 4).  One level of a cone is
@@ -960,6 +982,81 @@ __global__ void __launch_bounds__(kNarrowBlock) k_levels_narrow(int k0, int k1, 
         __threadfence_block();
         __syncthreads();
     }
+}
+
+// ---- an ensemble on ONE router (lf_router_route_ordered_members) ---------------------------------------------------------
+// `members` state vectors that share the router's static vectors and so its whole launch schedule: member m's discharge
+// and lateral inflow are rows m of two [members][stride] arrays in sweep order.  Every launch of the schedule covers all
+// members; the argument block is one sweep_args (row 0) and this, whatever the count.  Per cell and member the code is
+// sweep_cell_state / sweep_cone on the member's rows: bit-identical to the member swept alone.
+struct member_rows {
+    long long stride;  // elements between the rows of the state vectors (>= N)
+    long long cstride; // ... and of `constant` (general exponent: N)
+    int members;
+};
+__device__ __forceinline__ sweep_args member_view(sweep_args A, const member_rows &R, int m)
+{
+    A.qord += (long long)m * R.stride;
+    A.lat += (long long)m * R.stride;
+    if (A.constant) A.constant += (long long)m * R.cstride;
+    return A;
+}
+
+// k_prep for all members: blockIdx.y = member, vectors in sweep order
+__global__ void __launch_bounds__(kBlock) k_prep_members(int n, sweep_args A, member_rows R, double *__restrict__ constant)
+{
+    const int p = blockIdx.x * kBlock + threadIdx.x;
+    if (p >= n) return;
+    const long long row = (long long)blockIdx.y * R.stride;
+    const double lateral = A.lat[row + p] * (A.dx ? A.dx[p] : A.dx_scalar); // (k_prep's expression, sweep order)
+    constant[(long long)blockIdx.y * R.cstride + p] = A.a[p] * pow(A.qord[row + p], A.beta) + lateral;
+}
+
+// One wide level for all members: a lane owns one cell for a group of MB members (blockIdx.y = group; the last one may be
+// short).  The cell's static operands -- the (a, dx) record or a and dx, and the ups_ptr pair -- are loaded once and stay
+// in registers; per member the requests then go out in sweep_cell_state's order.  (Sharing them through L2 instead would
+// depend on which XCD a workgroup lands on.)  The members one after the other, each behind its own uniform branch (in a
+// loop the compiler hoists the solve's constants out of it and runs out of registers).
+// One member per lane is k_level's code at k_level's 8 wavefronts per SIMD; with the statics held across two or four
+// members the kernel needs 77 VGPRs, and forced into 64 it spills: 6 wavefronts per SIMD (80 VGPRs), no scratch.
+#define LF_MEMBERS_ATTR(MB) __attribute__((amdgpu_waves_per_eu((MB) == 1 ? 8 : 6)))
+template <bool FUSED, bool ORDERED, int STATICS, int MB>
+__global__ void __launch_bounds__(kLevelBlock) LF_MEMBERS_ATTR(MB) k_level_members(int first, int count, sweep_args A, member_rows R)
+{
+    static_assert(ORDERED && (STATICS == 0 || (STATICS == 1 && FUSED)), "members lie in sweep order; records: (a, dx)");
+    const int i = blockIdx.x * kLevelBlock + threadIdx.x;
+    if (i >= count) return;
+    const int p = first + i;
+    const int u0 = A.ups_ptr[p], u1 = A.ups_ptr[p + 1];
+    double ap, dxp;
+    sweep_cell_statics<FUSED, STATICS>(p, A, ap, dxp);
+    const int m0 = (int)blockIdx.y * MB;
+#pragma unroll
+    for (int j = 0; j < MB; ++j)
+        if (m0 + j < R.members) sweep_cell_state<FUSED, ORDERED, false, STATICS>(p, p, ap, dxp, u0, u1, 0, member_view(A, R, m0 + j));
+}
+
+// A run of narrow levels: k_levels_narrow's walk, one workgroup per member (blockIdx.x)
+template <bool FUSED, bool ORDERED>
+__global__ void __launch_bounds__(kNarrowBlock) k_levels_narrow_members(int k0, int k1, const long long *__restrict__ level_start,
+                                                                        sweep_args A, member_rows R)
+{
+    const sweep_args B = member_view(A, R, (int)blockIdx.x);
+    for (int k = k0; k < k1; ++k) {
+        const int first = (int)level_start[k], last = (int)level_start[k + 1];
+        for (int p = first + (int)threadIdx.x; p < last; p += kNarrowBlock) sweep_cell<FUSED, ORDERED, false>(p, B);
+        __threadfence_block();
+        __syncthreads();
+    }
+}
+
+// A level block: k_sweep_cones' cone (one router), blockIdx.y = member
+template <bool FUSED, bool ORDERED, int CW>
+__global__ void __launch_bounds__(CW) k_sweep_cones_members(cone_plan_args C, sweep_args A, member_rows R)
+{
+    sweep_args_multi M;
+    M.r[0] = member_view(A, R, (int)blockIdx.y);
+    sweep_cone<FUSED, ORDERED, 1, CW>(blockIdx.x, C, M);
 }
 
 // ================================================================================================

@@ -71,9 +71,10 @@ _SIGNATURES = {
            "dist_graph_get_export_phases dist_graph_get_layout dist_router_to_engine_order "
            "dist_router_from_engine_order dist_graph_get_fused_tables",
     "pppi": "router_route_host router_route_device router_route_ordered routing_substeps_fused_structures",
-    "pppii": "dist_routing_substep dist_router_compute_phase",
+    "pppii": "dist_routing_substep dist_router_compute_phase router_route_members_host",
     "pppiii": "dist_router_compute_part dist_router_exchange",
     "pppiiqii": "dist_routing_model_steps_fused",
+    "pppiqi": "router_route_ordered_members",
     "pppiqii": "dist_routing_substeps_fused",
     "pppp": "graph_get_lookups graph_get_layout surface_step surface_step_ordered dist_graph_set_ghost_phases "
             "dist_graph_get_csr",

@@ -198,6 +198,66 @@ class kinematicWave:
         sec = self._section(section)
         check(lib().lf_router_route_ordered(self._h, discharge_ord_dev.ptr, lateral_ord_dev.ptr, sec))
 
+    # --- an ensemble on this router: members that share the LDD and the channel geometry --------------
+    def kinematicWaveRoutingEnsemble(self, discharge, specific_lateral_inflow, section="main_channel"):
+        """kinematicWaveRouting for M members in one sweep: `discharge` (fp64, C-contiguous, [M, N] in pixel order) is
+        updated in place, the lateral inflow is broadcastable to [M, N].  Every row ends up as its own
+        kinematicWaveRouting call would leave it, bit for bit."""
+        sec = self._section(section)
+        if not (isinstance(discharge, np.ndarray) and discharge.dtype == np.float64 and discharge.ndim == 2
+                and discharge.flags.c_contiguous and discharge.shape[0] >= 1 and discharge.shape[1] == self.num_pixels):
+            raise ValueError("discharge must be a C-contiguous float64 [members, %d] array (members >= 1)"
+                             % self.num_pixels)
+        q = f64(np.broadcast_to(specific_lateral_inflow, discharge.shape))
+        if self.num_pixels == 0:
+            return
+        check(lib().lf_router_route_members_host(self._h, ptr(discharge), ptr(q), discharge.shape[0], sec))
+        if self.flagnancheck and not self.kinematic_wave_warning_printed:
+            if not np.all(np.isfinite(discharge)):
+                self._warn()
+
+    def route_ordered_members(self, discharge_ord_dev, lateral_ord_dev, members, stride=None, section="main_channel"):
+        """Engine-order resident form of the ensemble: both DeviceArrays hold `members` rows in sweep order, `stride`
+        elements apart (default: N); the discharge rows are updated in place; asynchronous."""
+        sec = self._section(section)
+        stride = self.num_pixels if stride is None else int(stride)
+        members = self._member_rows(members, stride, discharge_ord_dev, lateral_ord_dev)
+        check(lib().lf_router_route_ordered_members(self._h, discharge_ord_dev.ptr, lateral_ord_dev.ptr, members,
+                                                    stride, sec))
+
+    def _member_rows(self, members, stride, *arrays):
+        """`members` as an int, once every DeviceArray is seen to hold that many rows of N doubles, `stride` elements
+        apart: a wrong count is a ValueError here, not an access past the end of a device vector.  (No member or a stride
+        below N is the library's to refuse, with its own message.)"""
+        members, N = int(members), self.num_pixels
+        need = 8 * ((members - 1) * stride + N)
+        for a in arrays if members >= 1 and stride >= N else ():
+            if a.dtype != np.float64 or a.nbytes < need:
+                raise ValueError("%d member rows of %d doubles, %d apart, need a float64 DeviceArray of %d bytes (got %s, "
+                                 "%d bytes)" % (members, N, stride, need, a.dtype, a.nbytes))
+        return members
+
+    def to_engine_order_members(self, src_pix_dev, members, dst_ord_dev=None):
+        """[members, N] pixel order -> engine order, row by row (not on the hot path)"""
+        N = self.num_pixels
+        members = self._member_rows(members, N, src_pix_dev, *(() if dst_ord_dev is None else (dst_ord_dev,)))
+        if dst_ord_dev is None:
+            dst_ord_dev = DeviceArray((members, N), np.float64, self.device)
+        for m in range(members if N else 0):
+            check(lib().lf_router_to_engine_order(self._h, src_pix_dev.ptr.value + 8 * m * N,
+                                                  dst_ord_dev.ptr.value + 8 * m * N))
+        return dst_ord_dev
+
+    def from_engine_order_members(self, src_ord_dev, members, dst_pix_dev=None):
+        N = self.num_pixels
+        members = self._member_rows(members, N, src_ord_dev, *(() if dst_pix_dev is None else (dst_pix_dev,)))
+        if dst_pix_dev is None:
+            dst_pix_dev = DeviceArray((members, N), np.float64, self.device)
+        for m in range(members if N else 0):
+            check(lib().lf_router_from_engine_order(self._h, src_ord_dev.ptr.value + 8 * m * N,
+                                                    dst_pix_dev.ptr.value + 8 * m * N))
+        return dst_pix_dev
+
     @staticmethod
     def route_together(routers, discharge_devs, lateral_devs, section="main_channel", engine_order=False):
         """Several routers built on the same graph (the direct / other / forest overland routers of
