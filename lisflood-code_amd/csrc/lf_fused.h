@@ -171,7 +171,7 @@ __device__ __forceinline__ double upstream_sum8_pairs(const double *q, int u0, i
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         double2 t = make_double2(0.0, 0.0);
-        if (2 * j < kmax && u0 + 2 * j < u1) t = *(const double2 *)(q + u0 + 2 * j); // (8-byte aligned)
+        if (2 * j < kmax && u0 + 2 * j < u1) t = lf_load_pair(q + u0 + 2 * j);
         v[2 * j] = t.x;
         v[2 * j + 1] = (u0 + 2 * j + 1 < u1) ? t.y : 0.0;
     }
@@ -197,14 +197,14 @@ __device__ __forceinline__ void upstream_sum8_pairs2(const double *q1, const dou
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         double2 t = make_double2(0.0, 0.0);
-        if (2 * j < kmax && u0 + 2 * j < u1) t = *(const double2 *)(q1 + u0 + 2 * j);
+        if (2 * j < kmax && u0 + 2 * j < u1) t = lf_load_pair(q1 + u0 + 2 * j);
         v1[2 * j] = t.x;
         v1[2 * j + 1] = t.y;
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         double2 t = make_double2(0.0, 0.0);
-        if (two && 2 * j < kmax && u0 + 2 * j < u1) t = *(const double2 *)(q2 + u0 + 2 * j);
+        if (two && 2 * j < kmax && u0 + 2 * j < u1) t = lf_load_pair(q2 + u0 + 2 * j);
         v2[2 * j] = t.x;
         v2[2 * j + 1] = t.y;
     }

@@ -195,6 +195,11 @@ struct lf_router : lf_router_core {
     // (the fused plan of lf_router_core, fplan, is build_level_blocks' and carries lvl2blk for the sites of the structures
     // variant; rplan feeds k_sweep_cones)
     lf_dbuf<double2> adx1, adx2; // the (a, dx) records of k_level<.., STATICS = 1> per section (level_statics)
+    // the upstream ranges of k_level<.., STATICS = 2>, the graph's and so both sections' (level_counts): a count byte per
+    // cell, and ups_ptr at every 64th cell of every level -- level k's entries from wave_off[k] on
+    lf_dbuf<unsigned char> upcnt;
+    lf_dbuf<int> wave_start, wave_off_dev;
+    std::vector<int> wave_off;
     int64_t last_stats[4] = {0, 0, 0, 0};
     // profiling
     bool profile = false;
@@ -270,12 +275,46 @@ const double2 *level_statics(lf_router *r, const sweep_args &A)
     return buf.p;
 }
 
+// The count bytes and wavefront starts of r's graph for the wide levels that read the records, built on first use -> true;
+// LF_LEVEL_COUNTS=0 or no memory for them (1 byte per cell, 4 bytes per 64 cells of a level; a refusal is the records'
+// refusal: the separate streams stay for good) -> false
+bool level_counts(lf_router *r)
+{
+    if (!level_counts_enabled() || r->statics_refused) return false;
+    if (r->wave_start.p) return true;
+    const size_t nl = r->h_level_start.size() - 1;
+    r->wave_off.assign(nl + 1, 0);
+    for (size_t k = 0; k < nl; ++k)
+        r->wave_off[k + 1] = r->wave_off[k] + (int)((r->h_level_start[k + 1] - r->h_level_start[k] + 63) / 64);
+    if (!level_records_alloc(*r, r->upcnt)) return false;
+    lf_dbuf<int> table;
+    if (!level_records_alloc(*r, table, true, (size_t)r->wave_off[nl]) || r->wave_off_dev.upload(r->wave_off.data(), nl + 1, r->ctx->stream) != LF_OK) {
+        r->statics_refused = true;
+        (void)hipGetLastError();
+        r->upcnt.release();
+        return false;
+    }
+    hipLaunchKernelGGL(k_static_counts, dim3((unsigned)((r->N + kLevelBlock - 1) / kLevelBlock)), dim3(kLevelBlock), 0, r->ctx->stream,
+                       (long long)r->N, (const int *)r->ups_ptr.p, r->upcnt.p);
+    hipLaunchKernelGGL(k_wave_starts, dim3((unsigned)std::min<size_t>(nl, 4096), 64), dim3(kLevelBlock), 0, r->ctx->stream, (long long)nl,
+                       (const long long *)r->level_start.p, (const int *)r->wave_off_dev.p, (const int *)r->ups_ptr.p, table.p);
+    std::swap(r->wave_start.p, table.p);
+    std::swap(r->wave_start.n, table.n);
+    return true;
+}
+
 // one wide level of an ORDERED beta = 3/5 call
 void launch_level_ordered_fused(lf_router *r, hipStream_t s, int first, int cells, sweep_args A)
 {
     const dim3 grid(level_blocks_for(cells)), block(kLevelBlock);
     A.adx = level_statics(r, A);
-    if (A.adx)
+    if (A.adx && level_counts(r)) {
+        // the level that starts at `first` (the last of them: the ones before it are empty)
+        const size_t k = (size_t)(std::upper_bound(r->h_level_start.begin(), r->h_level_start.end() - 1, (int64_t)first) - r->h_level_start.begin()) - 1;
+        A.upcnt = r->upcnt.p;
+        A.wave_start = r->wave_start.p + r->wave_off[k];
+        hipLaunchKernelGGL((k_level<true, true, false, 2>), grid, block, 0, s, first, cells, A);
+    } else if (A.adx)
         hipLaunchKernelGGL((k_level<true, true, false, 1>), grid, block, 0, s, first, cells, A);
     else
         hipLaunchKernelGGL((k_level<true, true>), grid, block, 0, s, first, cells, A);

@@ -125,6 +125,11 @@ struct sweep_args {
     // STATICS = 3 (INDEXED: the row-block partition's level kernel, which reads four static streams -- a, dx, ups_ptr,
     // ups_base): (a, dx, first list entry | count << 28, ups_base), 24 bytes
     const struct lf_rec24 *__restrict__ rec24;
+    // STATICS = 2 (wide levels of an ordered beta = 3/5 call): the (a, dx) records of STATICS = 1, and the upstream range
+    // from one count byte per cell instead of two ups_ptr entries -- upcnt[p] = ups_ptr[p + 1] - ups_ptr[p], and ups_ptr at
+    // the first cell of every group of 64 cells of the level being swept (wave_start points at the level's first group)
+    const unsigned char *__restrict__ upcnt;
+    const int *__restrict__ wave_start;
 };
 struct lf_rec24 {
     double a, dx;
@@ -147,7 +152,7 @@ struct lf_rec24 {
 template <bool FUSED, int STATICS>
 __device__ __forceinline__ void sweep_cell_statics(int p, const sweep_args &A, double &ap, double &dxp)
 {
-    if (STATICS == 1) {
+    if (STATICS == 1 || STATICS == 2) {
         const double2 sd = A.adx[p];
         ap = sd.x;
         dxp = sd.y;
@@ -155,6 +160,13 @@ __device__ __forceinline__ void sweep_cell_statics(int p, const sweep_args &A, d
         ap = A.a[p];
         dxp = (FUSED && A.dx) ? A.dx[p] : A.dx_scalar;
     }
+}
+// two consecutive discharges as one 16-byte load from an address that is only 8-byte aligned (double2 itself asks for 16)
+__device__ __forceinline__ double2 lf_load_pair(const double *p)
+{
+    double2 t;
+    __builtin_memcpy(&t, p, sizeof t);
+    return t;
 }
 // ... and everything else of the cell: the state vectors of A (one member's), the solve, the store
 template <bool FUSED, bool ORDERED, bool INDEXED = false, int STATICS = 0>
@@ -188,7 +200,7 @@ __device__ __forceinline__ void sweep_cell_state(int p, int pix, double ap, doub
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             double2 t = make_double2(0.0, 0.0);
-            if (2 * j < A.kmax && u0 + 2 * j < u1) t = *(const double2 *)(A.qord + u0 + 2 * j); // (8-byte aligned)
+            if (2 * j < A.kmax && u0 + 2 * j < u1) t = lf_load_pair(A.qord + u0 + 2 * j);
             v[2 * j] = t.x;
             v[2 * j + 1] = t.y;
         }
@@ -269,6 +281,28 @@ __device__ __forceinline__ int ld_table(const int *p, int i)
     return ((const_int_ptr)(unsigned long long)p)[i];
 }
 
+// STATICS = 2: the cell at position p, number i of its level.  The upstream runs of consecutive cells are consecutive
+// (ups_ptr is their running sum), so a cell's run starts at the start of its wavefront's first run plus the counts of the
+// lanes below it: one byte per cell and one scalar load per wavefront instead of two 4-byte loads per lane.  A count is at
+// most 8: the prefix is the number of lanes below with bit b of the count set, weighted 1, 2, 4, 8 -- four ballots and
+// mbcnt, no data moves between lanes, and a lane that has left (beyond the level's end) is in no ballot.
+template <bool FUSED, bool ORDERED>
+__device__ __forceinline__ void sweep_cell_counted(int p, int i, const sweep_args &A)
+{
+    const unsigned cnt = A.upcnt[p];
+    double ap, dxp;
+    sweep_cell_statics<FUSED, 2>(p, A, ap, dxp);
+    const int start = ld_table(A.wave_start, __builtin_amdgcn_readfirstlane(i >> 6));
+    unsigned below[4];
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+        const unsigned long long m = __builtin_amdgcn_ballot_w64((cnt >> b) & 1u);
+        below[b] = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+    }
+    const int u0 = start + (int)(below[0] + 2u * below[1] + 4u * below[2] + 8u * below[3]);
+    sweep_cell_state<FUSED, ORDERED, false, 2>(p, p, ap, dxp, u0, u0 + (int)cnt, 0, A);
+}
+
 // one wide level: one cell per lane
 #ifndef LF_LEVEL_WAVES
 #define LF_LEVEL_WAVES 8 /* <= 80 SGPRs / 64 VGPRs: 8 wavefronts per SIMD instead of the 7 that 96 SGPRs allow (+2.3 %) */
@@ -288,7 +322,31 @@ __global__ void __launch_bounds__(kLevelBlock) LF_LEVEL_ATTR k_level(int first, 
 {
     const int i = blockIdx.x * kLevelBlock + threadIdx.x;
     if (i >= count) return;
-    sweep_cell<FUSED, ORDERED, INDEXED, STATICS>(first + i, A);
+    if constexpr (STATICS == 2) {
+        static_assert(FUSED && ORDERED && !INDEXED && kLevelBlock % 64 == 0, "a wavefront is one group of 64 cells of the level");
+        sweep_cell_counted<FUSED, ORDERED>(first + i, i, A);
+    } else {
+        sweep_cell<FUSED, ORDERED, INDEXED, STATICS>(first + i, A);
+    }
+}
+
+// the count bytes of k_level<.., STATICS = 2> (once per router)
+__global__ void __launch_bounds__(kLevelBlock) k_static_counts(long long n, const int *__restrict__ ups_ptr, unsigned char *__restrict__ upcnt)
+{
+    const long long i = (long long)blockIdx.x * kLevelBlock + threadIdx.x;
+    if (i < n) upcnt[i] = (unsigned char)(ups_ptr[i + 1] - ups_ptr[i]);
+}
+// ... and its table of wavefront starts: for every level k, from entry wave_off[k] on, ups_ptr at every 64th cell of the
+// level counted from its first one (blockIdx.x strides the levels, blockIdx.y and the threads the groups of a level)
+__global__ void __launch_bounds__(kLevelBlock) k_wave_starts(long long nl, const long long *__restrict__ level_start,
+                                                             const int *__restrict__ wave_off, const int *__restrict__ ups_ptr,
+                                                             int *__restrict__ wave_start)
+{
+    for (long long k = blockIdx.x; k < nl; k += gridDim.x) {
+        const long long first = level_start[k], groups = (level_start[k + 1] - first + 63) / 64;
+        for (long long w = (long long)blockIdx.y * kLevelBlock + threadIdx.x; w < groups; w += (long long)gridDim.y * kLevelBlock)
+            wave_start[wave_off[k] + w] = ups_ptr[first + 64 * w];
+    }
 }
 
 // the 24-byte records of k_level<.., INDEXED, STATICS = 3> (row-block partition; once per router and section)
@@ -1176,6 +1234,14 @@ inline bool dist_overlap_enabled()
     return !(e && e[0] == '0');
 }
 
+// LF_LEVEL_COUNTS=0: the wide levels that read the records take the upstream range from ups_ptr, not from the count
+// bytes (A/B switch, read at every call)
+inline bool level_counts_enabled()
+{
+    const char *e = std::getenv("LF_LEVEL_COUNTS");
+    return !(e && e[0] == '0');
+}
+
 // Do the wide levels of r's ordered calls read one record per cell (lf_router_core::statics_refused)?  Not with a scalar
 // dx (the sweep then has one static load anyway), off the beta = 3/5 path, after a refusal or with LF_LEVEL_STATICS=0.
 inline bool level_records_wanted(const lf_router_core &r)
@@ -1183,12 +1249,12 @@ inline bool level_records_wanted(const lf_router_core &r)
     return r.fused && r.dx_per_pixel && !r.statics_refused && r.N > 0 && level_statics_enabled();
 }
 
-// The records of one section on their first use: `buf` for r's N cells, which the caller then fills -> true; no memory
-// for them (or !fits, the caller's own limit) -> refused for good, the HIP error cleared
+// The records of one section on their first use: `buf` for r's N cells (or `count` elements), which the caller then
+// fills -> true; no memory for them (or !fits, the caller's own limit) -> refused for good, the HIP error cleared
 template <class T>
-bool level_records_alloc(lf_router_core &r, lf_dbuf<T> &buf, bool fits = true)
+bool level_records_alloc(lf_router_core &r, lf_dbuf<T> &buf, bool fits = true, size_t count = 0)
 {
-    if (fits && buf.alloc((size_t)r.N) == LF_OK) return true;
+    if (fits && buf.alloc(count ? count : (size_t)r.N) == LF_OK) return true;
     r.statics_refused = true;
     (void)hipGetLastError();
     return false;
@@ -1286,6 +1352,8 @@ inline sweep_args sweep_args_of(const lf_router_core &r, int section, double *qo
     A.qold_src = nullptr;
     A.adx = nullptr;
     A.rec24 = nullptr;
+    A.upcnt = nullptr;
+    A.wave_start = nullptr;
     return A;
 }
 

@@ -1,5 +1,5 @@
 """Same-box A/B of the headline call between two builds of the library: python tools/bench_headline_ab.py [size] [steps]
-(run once per LISFLOOD_AMD_LIBRARY setting; prints ms per call and the wide-level kernel mean)"""
+(run once per LISFLOOD_AMD_LIBRARY setting; prints ms per call, the wide-level kernel mean and the CRC of the final discharge)"""
 import os
 import sys
 
@@ -16,6 +16,6 @@ for rep in range(3):
     w = r["prof"]["wide_level"]
     us = w["ms"] * 1e3 / max(w["launches"], 1)
     cells = w["cells"] / max(w["launches"], 1)
-    print("%s: %.4f ms per call  %.1f Gcell-steps/s  wide level mean %.1f us -> frac %.4f" % (
+    print("%s: %.4f ms per call  %.1f Gcell-steps/s  wide level mean %.1f us -> frac %.4f  crc %08x" % (
         os.path.basename(os.environ.get("LISFLOOD_AMD_LIBRARY", "default")), r["ms_per_step"],
-        kw.num_pixels / r["ms_per_step"] / 1e6, us, 48.0 * cells / (us * 1e-6) / 8e12), flush=True)
+        kw.num_pixels / r["ms_per_step"] / 1e6, us, 48.0 * cells / (us * 1e-6) / 8e12, r["checksum"]), flush=True)
