@@ -1,5 +1,5 @@
 // lf_structures.h -- lakes and reservoirs of the routing loop, one lane per site; shared by the sub-step-by-sub-step
-// path (lf_modules.hip: k_inloop_sites) and the fused sub-step wavefront (lf_router.hip: k_sites_wave).
+// path (lf_modules.hip: k_inloop_sites) and the fused sub-step wavefront (lf_fused.h: k_sites_wave, k_sites_blocks).
 #pragma once
 #include "lf_common.h"
 

@@ -273,10 +273,15 @@ class _InloopArgs(C.Structure):  # lfo_inloop_args (lf_oracle.c)
 
 class InloopStructures:
     """lakes / reservoir / inflow / transmission .dynamic_inloop + the SideflowChanM3 assembly (routing.py:441-478)
-    on host arrays of a `var` namespace with the reference's attribute names (all four options on)."""
+    on host arrays of a `var` namespace with the reference's attribute names.  `options`: the reference's switches
+    simulateLakes / simulateReservoirs / inflow / TransLoss / openwaterevapo / wateruse / simulatePolders; None = the
+    first four on.  A module that is off has no sites (or a NULL QInM3Old / UpTrans) and its term is left out of the
+    sideflow; an optional sideflow vector is read from `var` when its option is on."""
 
-    def __init__(self, v):
+    def __init__(self, v, options=None):
         self.v = v
+        o = self.options = (dict(simulateLakes=True, simulateReservoirs=True, inflow=True, TransLoss=True)
+                            if options is None else dict(options))
         N = self.N = np.asarray(v.ChanQ).size
         ds = np.asarray(v.downstruct).astype(np.int64)
         order = np.argsort(ds, kind="stable")
@@ -290,8 +295,8 @@ class InloopStructures:
                 ptr[i + 1] = ptr[i] + u.size
             idx = np.concatenate(idx).astype(np.int32) if idx else np.zeros(0, np.int32)
             return ptr, (idx if idx.size else np.zeros(1, np.int32))
-        self.lake_cell = np.asarray(v.LakeIndex).astype(np.int32)
-        self.res_cell = np.asarray(v.ReservoirIndex).astype(np.int32)
+        self.lake_cell = np.asarray(v.LakeIndex if o.get("simulateLakes") else [], dtype=np.int64).astype(np.int32)
+        self.res_cell = np.asarray(v.ReservoirIndex if o.get("simulateReservoirs") else [], dtype=np.int64).astype(np.int32)
         self.lake_csr, self.res_csr = csr(self.lake_cell), csr(self.res_cell)
         nl, nr = self.lake_cell.size, self.res_cell.size
         for k in ("LakeInflowCC",):
@@ -302,39 +307,65 @@ class InloopStructures:
             setattr(v, k, np.zeros(N))
 
     def dynamic_inloop(self, step):
-        v = self.v
+        v, o = self.v, self.options
+        nl, nr = self.lake_cell.size, self.res_cell.size
         if step == 0:      # lakes.py:212-213, reservoir.py:195-196
-            v.LakeStorageM3CC = _f(np.asarray(v.LakeStorageM3)[self.lake_cell]).copy()
-            v.ReservoirStorageM3CC = _f(np.asarray(v.ReservoirStorageM3)[self.res_cell]).copy()
+            if nl:
+                v.LakeStorageM3CC = _f(np.asarray(v.LakeStorageM3)[self.lake_cell]).copy()
+            if nr:
+                v.ReservoirStorageM3CC = _f(np.asarray(v.ReservoirStorageM3)[self.res_cell]).copy()
         a, keep = _InloopArgs(), []
 
         def put(name, arr):
             keep.append(arr)
             setattr(a, name, arr.ctypes.data)
         put("ChanQ", _f(v.ChanQ))
-        a.n_lakes, a.n_res = self.lake_cell.size, self.res_cell.size
-        put("lake_cell", self.lake_cell); put("lake_ups_ptr", self.lake_csr[0]); put("lake_ups_idx", self.lake_csr[1])
-        put("res_cell", self.res_cell); put("res_ups_ptr", self.res_csr[0]); put("res_ups_idx", self.res_csr[1])
-        for k in ("LakeFactor", "LakeFactorSqr", "LakeAreaCC", "TotalReservoirStorageM3CC", "MinReservoirOutflowCC",
-                  "NormalReservoirOutflowCC", "NonDamagingReservoirOutflowCC", "ConservativeStorageLimitCC",
-                  "NormalStorageLimitCC", "FloodStorageLimitCC", "Normal_FloodStorageLimitCC", "DeltaO", "DeltaLN",
-                  "DeltaNFL", "QInM3Old", "QDelta", "ToChanM3RunoffDt"):
-            put(k, _f(np.broadcast_to(getattr(v, k), (self.N,) if k in ("QInM3Old", "QDelta", "ToChanM3RunoffDt") else np.shape(getattr(v, k)))))
-        put("UpTrans", _u8(v.UpTrans))
-        for k in ("LakeStorageM3CC", "LakeInflowOldCC", "LakeOutflowCC", "LakeStorageM3BalanceCC", "LakeLevelCC",
-                  "LakeInflowCC", "QLakeOutM3Dt", "ReservoirStorageM3CC", "ReservoirFillCC", "ReservoirInflowCC",
-                  "QResOutM3Dt", "QInDt", "QinADDEDM3", "TransLossM3Dt", "TransCum", "SideflowChanM3"):
+        put("ToChanM3RunoffDt", _f(np.broadcast_to(v.ToChanM3RunoffDt, (self.N,))))
+        a.n_lakes, a.n_res = nl, nr
+        if nl:
+            put("lake_cell", self.lake_cell); put("lake_ups_ptr", self.lake_csr[0]); put("lake_ups_idx", self.lake_csr[1])
+            for k in ("LakeFactor", "LakeFactorSqr", "LakeAreaCC"):
+                put(k, _f(np.broadcast_to(getattr(v, k), (nl,))))
+        if nr:
+            put("res_cell", self.res_cell); put("res_ups_ptr", self.res_csr[0]); put("res_ups_idx", self.res_csr[1])
+            for k in ("TotalReservoirStorageM3CC", "MinReservoirOutflowCC", "NormalReservoirOutflowCC",
+                      "NonDamagingReservoirOutflowCC", "ConservativeStorageLimitCC", "NormalStorageLimitCC",
+                      "FloodStorageLimitCC", "Normal_FloodStorageLimitCC", "DeltaO", "DeltaLN", "DeltaNFL"):
+                put(k, _f(np.broadcast_to(getattr(v, k), (nr,))))
+        written = ["SideflowChanM3"]
+        if nl:
+            written += ["LakeStorageM3CC", "LakeInflowOldCC", "LakeOutflowCC", "LakeStorageM3BalanceCC", "LakeLevelCC",
+                        "LakeInflowCC", "QLakeOutM3Dt"]
+        if nr:
+            written += ["ReservoirStorageM3CC", "ReservoirFillCC", "ReservoirInflowCC", "QResOutM3Dt"]
+        if o.get("inflow"):
+            put("QInM3Old", _f(np.broadcast_to(v.QInM3Old, (self.N,)))); put("QDelta", _f(np.broadcast_to(v.QDelta, (self.N,))))
+            written += ["QInDt", "QinADDEDM3"]
+        if o.get("TransLoss"):
+            put("UpTrans", _u8(v.UpTrans))
+            written += ["TransLossM3Dt", "TransCum"]
+        if o.get("openwaterevapo"):
+            put("EvaAddM3Dt", _f(np.broadcast_to(v.EvaAddM3Dt, (self.N,))))
+        if o.get("wateruse"):      # routing.py:466-468
+            v.WUseAddM3Dt = _f(v.withdrawal_CH_actual_M3_routStep) - _f(v.returnflow_GwAbs2Channel_M3_routStep)
+            put("WUseAddM3Dt", _f(np.broadcast_to(v.WUseAddM3Dt, (self.N,))))
+        if o.get("simulatePolders"):
+            put("ChannelToPolderM3Dt", _f(np.broadcast_to(v.ChannelToPolderM3Dt, (self.N,))))
+        for k in written:
             x = getattr(v, k)
             assert x.dtype == np.float64 and x.flags.c_contiguous, k
             put(k, x)
-        a.TransPower1, a.TransPower2, a.TransSub = float(v.TransPower1), float(v.TransPower2), float(v.TransSub)
+        if o.get("TransLoss"):
+            a.TransPower1, a.TransPower2, a.TransSub = float(v.TransPower1), float(v.TransPower2), float(v.TransSub)
         a.DtRouting, a.InvNoRoutSteps, a.N, a.step = float(v.DtRouting), float(v.InvNoRoutSteps), self.N, int(step)
         lib().lfo_inloop_structures(C.byref(a))
         if step == int(v.NoRoutSteps) - 1:      # lakes.py:283-292, reservoir.py:311-315: back to the dense state maps
-            v.LakeStorageM3 = np.zeros(self.N)
-            v.LakeStorageM3[self.lake_cell] = v.LakeStorageM3CC
-            v.ReservoirStorageM3 = np.zeros(self.N)
-            v.ReservoirStorageM3[self.res_cell] = v.ReservoirStorageM3CC
+            if nl:
+                v.LakeStorageM3 = np.zeros(self.N)
+                v.LakeStorageM3[self.lake_cell] = v.LakeStorageM3CC
+            if nr:
+                v.ReservoirStorageM3 = np.zeros(self.N)
+                v.ReservoirStorageM3[self.res_cell] = v.ReservoirStorageM3CC
 
 
 _PIX_V_IN = ("SoilFraction TaInterception Ta ESAct PrefFlow Infiltration SeepTopToSubA SeepTopToSubB SeepSubToGW Theta1a "
