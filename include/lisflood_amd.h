@@ -149,6 +149,18 @@ int lf_graph_create_ex(const double *ldd_codes, const uint8_t *land_mask, int H,
 /* linked[N], by engine position: 1 = the cell is such a zero-length link (it sits at the end of its level, outside
  * every upstream range) */
 int lf_graph_get_links(const lf_graph *g, uint8_t *linked);
+/* The site plan of the time-major form of lf_routing_substeps_fused_structures, host arrays only (no device): n cells
+ * in nlevels levels (level_start[nlevels + 1], as lf_graph_get_layout gives it) and the six site lists of lf_inloop_args
+ * in engine positions.  Out: feed_slot[n] -- entry e of lake_ups_idx has slot e, entry e of res_ups_idx slot
+ * lake_ups_ptr[n_lakes] + e, feed_slot is the inverse map (-1: the cell feeds no site); level_site[level_site_ptr[k] ..
+ * level_site_ptr[k + 1]) -- the sites (lakes 0 .. n_lakes - 1, then the reservoirs) whose cell is on level k, ascending
+ * (level_site_ptr[nlevels + 1], level_site[n_lakes + n_res]); *applies = 0 when a site cell feeds another site, two sites
+ * share a cell, a cell feeds two sites or a feeder is not on its site's level: the call then runs the skewed wavefront,
+ * and the arrays are not complete.  A cell or a pointer out of range is LF_E_INVALID. */
+int lf_site_plan(int64_t n, int nlevels, const int64_t *level_start, int64_t n_lakes, const int32_t *lake_cell,
+                 const int32_t *lake_ups_ptr, const int32_t *lake_ups_idx, int64_t n_res, const int32_t *res_cell,
+                 const int32_t *res_ups_ptr, const int32_t *res_ups_idx, int32_t *applies, int32_t *feed_slot,
+                 int32_t *level_site_ptr, int32_t *level_site);
 /* raster form for large domains: H*W uint8 codes; land_mask may be NULL (= all land). */
 int lf_graph_create_raster(const uint8_t *ldd_raster, const uint8_t *land_mask, int H, int W, lf_graph **out);
 void lf_graph_destroy(lf_graph *g);
@@ -214,6 +226,10 @@ int lf_count_nonfinite(int device, const double *x_dev, int64_t n, int64_t *coun
 /* launch statistics of the last route call: [0] kernel launches, [1] wide-level launches,
  * [2] narrow-run launches, [3] levels */
 int lf_router_last_launches(const lf_router *r, int64_t stats[4]);
+/* the schedule the last lf_routing_substeps_fused* / lf_routing_model_steps_fused call of this router took: 0 none yet,
+ * 1 time-major (one launch per level through all sub-steps, plus one per level that holds a lake or reservoir), 2 the
+ * skewed wavefront over level blocks, 3 the skewed wavefront over levels; -1: null router */
+int lf_router_last_fused_form(const lf_router *r);
 /* shape of the block plan of single router calls: [0] blocks, [1] blocks of more than one level (swept cone by cone),
  * and over those: [2] cones, [3] cone levels (one wavefront-level each: 64 lanes), [4] cells, [5] most cones in one launch.
  * [4] / (64 * [3]) = lane use of the cone sweep. */
@@ -496,7 +512,14 @@ int lf_inloop_structures(int device, const lf_inloop_args *a);
  * engine positions, `in->step` is ignored), and a router whose graph was built by lf_graph_create_ex with the
  * uncut links of the structures (every cell feeding a site on the site's level; checked once per set of device
  * site lists, whose contents must not change afterwards).  Bit-identical to the
- * sub-step-by-sub-step sequence lf_inloop_structures + lf_routing_substep. */
+ * sub-step-by-sub-step sequence lf_inloop_structures + lf_routing_substep.
+ * On graphs of few wide levels (the rule of lf_routing_substeps_fused; LF_FUSED_TIME_MAJOR=0 / 1: never / whenever it
+ * applies) the call takes the TIME-MAJOR form instead: level after level, every cell through all its sub-steps with its
+ * state -- and the inflow hydrograph, transmission loss and sideflow terms -- in registers.  The cells feeding a site write
+ * their ChanQ of every sub-step to a small [nsteps + 1][feeders] buffer; the site cells of a level run in a launch of
+ * their own behind the level's (one lane per site: the site's update, then the cell's sub-step, sub-step after sub-step).
+ * It needs the site plan to apply (lf_site_plan: no chained sites, no shared cells) and room for the [nsteps][N]
+ * history; otherwise the skewed wavefront runs.  Same bits either way; lf_router_last_fused_form tells which ran. */
 int lf_routing_substeps_fused_structures(lf_router *r, const lf_substep_args *a, const lf_inloop_args *in, int nsteps);
 /* drops the cached validation of the site lists (call after rebuilding lake_cell / lake_ups_idx / res_cell /
  * res_ups_idx, even if the new lists live at the old addresses) */

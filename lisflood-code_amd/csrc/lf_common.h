@@ -197,3 +197,83 @@ inline bool lf_history_ensure(lf_dbuf<double> &h1, lf_dbuf<double> &h2, size_t &
     }
     return ok;
 }
+
+// Site plan of the time-major fused form with lakes and reservoirs in the loop (lf_fused.h: k_fused_level_steps<.., STRUCT>),
+// a pure function of the level table and the six site lists (engine positions):
+//  * feed slots: entry e of lake_ups_idx has slot e, entry e of res_ups_idx slot lake_ups_ptr[n_lakes] + e; slot_of[N] is the
+//    inverse map (cell position -> slot, -1: the cell feeds no site);
+//  * the sites of every level: level_site[level_ptr[k] .. level_ptr[k + 1]) are the sites (lakes 0 .. n_lakes - 1, then the
+//    reservoirs) whose cell is on level k, ascending;
+//  * applies: no site cell feeds another site (chained sites), no two sites share a cell, no cell feeds two sites and every
+//    feeder is on its site's level -- otherwise the skewed wavefront runs.  The arrays are complete only if it applies.
+// A cell, a pointer or a level table out of range is an error (LF_E_INVALID), not a plan that does not apply.
+struct lf_site_plan_t {
+    bool applies = false;
+    int64_t nfeed = 0;
+    std::vector<int32_t> slot_of, level_ptr, level_site, site_level;
+};
+inline int lf_site_plan_build(int64_t n, int64_t nlevels, const int64_t *level_start, int64_t n_lakes, const int32_t *lake_cell,
+                              const int32_t *lake_ups_ptr, const int32_t *lake_ups_idx, int64_t n_res, const int32_t *res_cell,
+                              const int32_t *res_ups_ptr, const int32_t *res_ups_idx, lf_site_plan_t &P)
+{
+    if (n < 0 || n >= ((int64_t)1 << 31) || nlevels < 0 || !level_start || n_lakes < 0 || n_res < 0 ||
+        n_lakes + n_res >= ((int64_t)1 << 31))
+        return lf_set_error(LF_E_INVALID, "site plan: bad argument");
+    if (level_start[0] != 0 || level_start[nlevels] != n) return lf_set_error(LF_E_INVALID, "site plan: the levels do not cover the cells");
+    for (int64_t k = 0; k < nlevels; ++k)
+        if (level_start[k] > level_start[k + 1]) return lf_set_error(LF_E_INVALID, "site plan: level table not ascending");
+    if ((n_lakes > 0 && (!lake_cell || !lake_ups_ptr)) || (n_res > 0 && (!res_cell || !res_ups_ptr)))
+        return lf_set_error(LF_E_INVALID, "site plan: site lists missing");
+    const int64_t nsites = n_lakes + n_res;
+    const int64_t lake_entries = n_lakes > 0 ? lake_ups_ptr[n_lakes] : 0, res_entries = n_res > 0 ? res_ups_ptr[n_res] : 0;
+    auto check_list = [&](int64_t cnt, const int32_t *cell, const int32_t *ptr, const int32_t *idx, const char *what) -> int {
+        if (cnt == 0) return LF_OK;
+        if (ptr[0] != 0) return lf_set_error(LF_E_INVALID, "site plan: %s_ups_ptr does not start at 0", what);
+        for (int64_t i = 0; i < cnt; ++i) {
+            if (cell[i] < 0 || cell[i] >= n) return lf_set_error(LF_E_INVALID, "site plan: %s cell out of range", what);
+            if (ptr[i + 1] < ptr[i]) return lf_set_error(LF_E_INVALID, "site plan: %s_ups_ptr not ascending", what);
+        }
+        if (ptr[cnt] > 0 && !idx) return lf_set_error(LF_E_INVALID, "site plan: %s_ups_idx missing", what);
+        for (int32_t e = 0; e < ptr[cnt]; ++e)
+            if (idx[e] < 0 || idx[e] >= n) return lf_set_error(LF_E_INVALID, "site plan: a cell draining into a %s is out of range", what);
+        return LF_OK;
+    };
+    LF_TRY(check_list(n_lakes, lake_cell, lake_ups_ptr, lake_ups_idx, "lake"));
+    LF_TRY(check_list(n_res, res_cell, res_ups_ptr, res_ups_idx, "reservoir"));
+    if (lake_entries + res_entries >= ((int64_t)1 << 31)) return lf_set_error(LF_E_INVALID, "site plan: too many feeders");
+    auto level_of = [&](int64_t pos) { return (int32_t)(std::upper_bound(level_start, level_start + nlevels + 1, pos) - level_start) - 1; };
+    P.applies = true;
+    P.nfeed = lake_entries + res_entries;
+    P.slot_of.assign((size_t)n, -1);
+    P.site_level.assign((size_t)nsites, 0);
+    P.level_ptr.assign((size_t)nlevels + 1, 0);
+    P.level_site.assign((size_t)nsites, 0);
+    std::vector<uint8_t> is_site((size_t)n, 0);
+    auto cell_of = [&](int64_t i) { return i < n_lakes ? lake_cell[i] : res_cell[i - n_lakes]; };
+    for (int64_t i = 0; i < nsites; ++i) {
+        const int32_t c = cell_of(i);
+        if (is_site[c]) P.applies = false; // two sites share a cell
+        is_site[c] = 1;
+        P.site_level[i] = level_of(c);
+        ++P.level_ptr[P.site_level[i] + 1];
+    }
+    for (int64_t k = 0; k < nlevels; ++k) P.level_ptr[k + 1] += P.level_ptr[k];
+    {
+        std::vector<int32_t> next(P.level_ptr.begin(), P.level_ptr.end() - 1);
+        for (int64_t i = 0; i < nsites; ++i) P.level_site[next[P.site_level[i]]++] = (int32_t)i;
+    }
+    auto feeders = [&](int64_t cnt, const int32_t *ptr, const int32_t *idx, int64_t site0, int64_t slot0) {
+        for (int64_t i = 0; i < cnt; ++i)
+            for (int32_t e = ptr[i]; e < ptr[i + 1]; ++e) {
+                const int32_t c = idx[e];
+                if (P.slot_of[c] >= 0) // a cell feeds two sites (or is listed twice)
+                    P.applies = false;
+                else
+                    P.slot_of[c] = (int32_t)(slot0 + e);
+                if (is_site[c] || level_of(c) != P.site_level[site0 + i]) P.applies = false; // chained sites; not on the site's level
+            }
+    };
+    feeders(n_lakes, lake_ups_ptr, lake_ups_idx, 0, 0);
+    feeders(n_res, res_ups_ptr, res_ups_idx, n_lakes, lake_entries);
+    return LF_OK;
+}

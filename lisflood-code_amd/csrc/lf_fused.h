@@ -46,6 +46,12 @@ struct fused_args {
     const uint8_t *__restrict__ inert;  // cells whose sub-step is the identity while their state is all +0.0
     lf_inloop_args I;                   // STRUCT: lakes / reservoirs / inflow / transmission loss / sideflow assembly
     const int *__restrict__ site_level; // STRUCT: level of every lake, then every reservoir cell
+    // time-major form with structures (k_fused_level_steps<.., STRUCT>; lf_common.h: lf_site_plan; `linked` then holds 1
+    // for a link and 2 for a site cell): slot of a link in the [nsteps + 1][tm_nfeed] buffer of the feeders' ChanQ (row 0:
+    // before the call, row s + 1: after sub-step s), and the sites of level k: tm_site[tm_site_ptr[k] .. tm_site_ptr[k + 1])
+    const int *__restrict__ tm_slot, *__restrict__ tm_site_ptr, *__restrict__ tm_site;
+    double *tm_feed;
+    int tm_nfeed;
     // 1-D grid packed by sub-step: blocks [blk_start[s], blk_start[s+1]) work on (level t - s, sub-step s), so no
     // block is launched for the part of a narrow level that a 2-D grid sized by the widest level would cover
     // (packed = 0: 2-D grid, blockIdx.y = sub-step; used when nsteps > kMaxPackedSteps)
@@ -887,22 +893,42 @@ __device__ __forceinline__ void cone_compute(const fused_args &F, const cone_cel
 #ifndef LF_TM_WAVES
 #define LF_TM_WAVES 4
 #endif
+// The structures variant carries ~12 more doubles per lane through the loop: at 4 waves (128 registers) the cell lanes spill
+// 50 of them (184 B of scratch, split routing, beta = 3/5), at 3 waves (168 registers) 4 (40 B) -- LF_TM_WAVES_STRUCT.  The
+// site lanes are a few hundred per launch at most, so their cap is 2 (no spill).
+#ifndef LF_TM_WAVES_STRUCT
+#define LF_TM_WAVES_STRUCT 3
+#endif
 #if LF_TM_WAVES > 0
-#define LF_TM_ATTR __attribute__((amdgpu_waves_per_eu(LF_TM_WAVES)))
+#define LF_TM_ATTR __attribute__((amdgpu_waves_per_eu(STRUCT == 2 ? 2 : STRUCT == 1 ? LF_TM_WAVES_STRUCT : LF_TM_WAVES)))
 #else
 #define LF_TM_ATTR
 #endif
 // DIST (row-block partition, a phase's levels): upstream cells are a consecutive local run (hist), or come from the list --
 // same-phase positions (hist) and slab slots (earlier phases, other ranks: the slabs hold every sub-step) --, and a cell
 // whose router outputs cross a phase or rank boundary also writes them to its slab slot, as k_fused_substeps<DIST> does.
-template <bool SPLIT, bool ALL35, bool DIST = false>
+//
+// STRUCT (lakes, reservoirs, inflow hydrographs and transmission loss in the loop, lf_routing_substeps_fused_structures):
+// the sideflow of every sub-step is assembled as fused_cell<STRUCT> does, operation for operation, with QInDt, QinADDEDM3,
+// the transmission loss, TransCum and the ChanQ of the previous sub-step carried in registers.  Inside a level only the
+// site cells depend on other cells of the level -- on the cells that feed the site, one sub-step back -- so
+//  STRUCT = 1, one lane per cell of level k: a site cell returns at once; a link that feeds a site writes its ChanQ of every
+//              sub-step to the feed buffer (fused_args::tm_feed);
+//  STRUCT = 2, one lane per SITE of level k, launched behind the level's own launch: sub-step after sub-step the site's
+//              inflow from the feed buffer (ascending list order, as lf_site_inflow), the site's update (lf_site_body), then
+//              the sub-step of the site's cell with the outflow volume in its sideflow.
+template <bool SPLIT, bool ALL35, bool DIST = false, int STRUCT = 0>
 __global__ void __launch_bounds__(kBlock) LF_TM_ATTR k_fused_level_steps(fused_args F, int k)
 {
+    static_assert(!(DIST && STRUCT != 0), "the row-block partition runs no structures");
     const lf_substep_args &A = F.S;
-    const long long first = F.level_start[k];
+    // (STRUCT = 2: lane i works on the i-th site of level k, the cell is that site's)
+    const long long first = STRUCT == 2 ? (long long)F.tm_site_ptr[k] : F.level_start[k];
     const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= F.level_start[k + 1] - first) return;
-    const long long p = first + i, n = F.n;
+    if (i >= (STRUCT == 2 ? (long long)F.tm_site_ptr[k + 1] : F.level_start[k + 1]) - first) return;
+    const long long site = STRUCT == 2 ? (long long)F.tm_site[first + i] : 0;
+    const long long p = STRUCT == 2 ? (long long)(site < F.I.n_lakes ? F.I.lake_cell[site] : F.I.res_cell[site - F.I.n_lakes]) : first + i,
+                    n = F.n;
     const int nsteps = F.nsteps;
     const int u0 = F.ups_ptr[p], u1 = F.ups_ptr[p + 1], kmax = F.kmax;
     int base = u0;
@@ -937,7 +963,15 @@ __global__ void __launch_bounds__(kBlock) LF_TM_ATTR k_fused_level_steps(fused_a
     const double dxp = (dflags & 2u) ? len : (F.dx ? F.dx[p] : F.dx_scalar);
     const double inv_len = rc ? 1.0 / len : A.InvChanLength[p];
     const bool is_chan = A.IsChannelKinematic[p] != 0;
-    const bool cut = F.linked && F.linked[p];
+    bool cut;
+    int feed = -1; // STRUCT = 1: this cell's row entry in the feed buffer
+    if constexpr (STRUCT != 0) {
+        const unsigned fl = F.linked ? F.linked[p] : 0u;
+        if (STRUCT == 1 && (fl & 2u)) return; // a site cell: run by the site lanes behind this launch
+        cut = (fl & 1u) != 0u;
+        if (STRUCT == 1 && cut && F.tm_slot) feed = F.tm_slot[p];
+    } else
+        cut = F.linked && F.linked[p];
     const double alpha1 = A.ChannelAlpha[p];
     const double inv_alpha1 = rc ? 1.0 / alpha1 : A.InvChannelAlpha[p], ap1 = rc ? alpha1 * dxp / F.dt : F.a1[p];
     double qold = A.ChanQKin[p], sum = 0.0;
@@ -956,7 +990,7 @@ __global__ void __launch_bounds__(kBlock) LF_TM_ATTR k_fused_level_steps(fused_a
     }
     const double pix_area = A.PixelArea[p];
     int s0 = 0;
-    if (F.inert && F.inert[p]) { // see k_inert_flags: a sub-step leaves such a cell as it is while its state is all +0.0,
+    if (STRUCT == 0 && F.inert && F.inert[p]) { // see k_inert_flags: a sub-step leaves such a cell as it is while its state is all +0.0,
                                  // so only the last one (which also writes the velocities) is run, as fused_cell does
         bool zero = plus_zero(qold) && plus_zero(A.ChanM3Kin[p]) && plus_zero(A.ChanQ[p]);
         if (SPLIT && zero)
@@ -970,7 +1004,32 @@ __global__ void __launch_bounds__(kBlock) LF_TM_ATTR k_fused_level_steps(fused_a
         }
     }
     double v = 0, q = 0, chanq = 0, s1 = 0, v2 = 0, q2 = 0;
-    double side_m3 = fused_side(F, s0)[p];
+    double side_m3 = STRUCT != 0 ? 0.0 : fused_side(F, s0)[p];
+    // STRUCT: the terms of the sideflow assembly (routing.py:462-478) and what the loop carries from sub-step to sub-step
+    double to_chan = 0, eva = 0, wuse = 0, qin_old = 0, qdelta = 0, qin = 0, qin_added = 0.0, loss = 0, trans_cum = 0, lakeout = 0,
+           resout = 0, polder = 0;
+    bool uptrans = false;
+    int res_slot0 = 0; // STRUCT = 2: first feed slot of the reservoirs' lists
+    if constexpr (STRUCT != 0) {
+        const lf_inloop_args &I = F.I;
+        to_chan = I.ToChanM3RunoffDt[p];
+        if (I.EvaAddM3Dt) eva = I.EvaAddM3Dt[p];
+        if (I.WUseAddM3Dt) wuse = I.WUseAddM3Dt[p];
+        if (I.QInM3Old) {
+            qin_old = I.QInM3Old[p];
+            qdelta = I.QDelta[p];
+        }
+        if (I.UpTrans) {
+            uptrans = I.UpTrans[p] != 0;
+            trans_cum = I.TransCum[p];
+        }
+        if (I.QLakeOutM3Dt) lakeout = I.QLakeOutM3Dt[p];
+        if (I.QResOutM3Dt) resout = I.QResOutM3Dt[p];
+        if (I.ChannelToPolderM3Dt) polder = I.ChannelToPolderM3Dt[p];
+        chanq = A.ChanQ[p]; // ChanQ before the first sub-step: transmission loss, the sites' inflow
+        if (STRUCT == 1 && feed >= 0) F.tm_feed[feed] = chanq;
+        if (STRUCT == 2 && I.n_lakes > 0) res_slot0 = I.lake_ups_ptr[I.n_lakes];
+    }
     sum = fused_sum(F, s0)[p];
     // position of the sub-step inside its model step, counted along (s starts per lane -- inert cells run only the last
     // sub-step -- so `s % msteps` would be a vector-register division, ~25 instructions, twice per sub-step)
@@ -984,7 +1043,42 @@ __global__ void __launch_bounds__(kBlock) LF_TM_ATTR k_fused_level_steps(fused_a
             ups2 = SPLIT ? ups_of(F.hist2, F.root2, s) : 0.0;
         }
         const bool first_of_step = sm == 0;
-        if ((F.side_stride != 0 || first_of_step) && s > s0) side_m3 = fused_side(F, s)[p];
+        if constexpr (STRUCT == 0) {
+            if ((F.side_stride != 0 || first_of_step) && s > s0) side_m3 = fused_side(F, s)[p];
+        } else { // inflow.py:142-144, transmission.py:76-87, sideflow assembly routing.py:462-478 -- as fused_cell<STRUCT>
+            const lf_inloop_args &I = F.I;
+            if constexpr (STRUCT == 2) { // the site first: its feeders' ChanQ after sub-step s - 1, ascending list order
+                const double *row = F.tm_feed + (long long)s * F.tm_nfeed;
+                double inflow = 0.0;
+                if (site < I.n_lakes) {
+                    for (int e = I.lake_ups_ptr[site]; e < I.lake_ups_ptr[site + 1]; ++e) inflow += row[e];
+                } else {
+                    const long long r = site - I.n_lakes;
+                    for (int e = I.res_ups_ptr[r]; e < I.res_ups_ptr[r + 1]; ++e) inflow += row[res_slot0 + e];
+                }
+                lf_site_body(I, site, inflow);
+                if (I.QLakeOutM3Dt) lakeout = I.QLakeOutM3Dt[p];
+                if (I.QResOutM3Dt) resout = I.QResOutM3Dt[p];
+            }
+            side_m3 = to_chan;
+            if (I.EvaAddM3Dt) side_m3 -= eva;
+            if (I.WUseAddM3Dt) side_m3 -= wuse;
+            if (I.QInM3Old) {
+                qin = (qin_old + (s + 1) * qdelta) * I.InvNoRoutSteps;
+                qin_added = qin_added + qin; // (sub-step 0: 0.0 + qin)
+                side_m3 += qin;
+            }
+            if (I.UpTrans) {
+                const double qc = chanq;
+                const double tout = uptrans ? lf_pow_scalar_exponent(lf_pow_scalar_exponent(qc, I.TransPower2) - I.TransSub, I.TransPower1) : qc;
+                loss = (qc - tout) * I.DtRouting;
+                trans_cum = trans_cum + loss;
+                side_m3 -= loss;
+            }
+            if (I.QLakeOutM3Dt) side_m3 += lakeout;
+            if (I.QResOutM3Dt) side_m3 += resout;
+            if (I.ChannelToPolderM3Dt) side_m3 -= polder;
+        }
         if (first_of_step && s > s0) sum = fused_sum(F, s)[p]; // the next model step's sum (zeroed by the caller)
         // ---- sideflow (routing.py:512, 524 / 549-567) ----
         const double side = is_chan ? side_m3 * inv_len * A.InvDtRouting : 0.0;
@@ -1050,6 +1144,8 @@ __global__ void __launch_bounds__(kBlock) LF_TM_ATTR k_fused_level_steps(fused_a
             F.root1[slot * F.root_ss + (long long)s * F.root_st] = qr;
             if (SPLIT) F.root2[slot * F.root_ss + (long long)s * F.root_st] = q2r;
         }
+        if constexpr (STRUCT == 1)
+            if (feed >= 0) F.tm_feed[(long long)(s + 1) * F.tm_nfeed + feed] = chanq; // read by the site at sub-step s + 1
         // the state of the next sub-step
         m3 = v;
         qold = q;
@@ -1063,6 +1159,18 @@ __global__ void __launch_bounds__(kBlock) LF_TM_ATTR k_fused_level_steps(fused_a
         }
     }
     // ---- what the sub-step-by-sub-step sequence leaves behind ----
+    if constexpr (STRUCT != 0) {
+        const lf_inloop_args &I = F.I;
+        if (I.QInM3Old) {
+            I.QInDt[p] = qin;
+            I.QinADDEDM3[p] = qin_added;
+        }
+        if (I.UpTrans) {
+            I.TransLossM3Dt[p] = loss;
+            I.TransCum[p] = trans_cum;
+        }
+        I.SideflowChanM3[p] = side_m3;
+    }
     A.ChanM3Kin[p] = v;
     A.ChanQKin[p] = q;
     A.ChanQ[p] = chanq;
@@ -1774,26 +1882,23 @@ inline int fused_check_derived(lf_router_core &r, const lf_substep_args &a, hipS
 // r.fplan --
 // for F.nsteps sub-steps; fills F's wave fields and adds its launches to `launches`.  Of the three schedules the first that
 // applies runs:
-//   time-major   (time_major: the caller's precondition) one k_fused_level_steps launch per level;
+//   time-major   (time_major: the caller's precondition) one k_fused_level_steps launch per level; with structures in the
+//                loop (tm: the site plan's device tables) also one per level that holds a site, behind the level's own;
 //   level blocks (nblocks >= 0, F.nsteps <= kMaxPackedSteps) per wave time t: cones(ncones) launches the multi-level
 //                blocks through a cone kernel on a packed grid of ncones workgroups, levels(grid) the single levels
 //                through k_fused_substeps (F.use_lvl);
 //   levels       per wave time t: levels(grid), level t - s for sub-step s.
 // sites(blocks, lo, hi) runs first at every wave time t, with the window [lo, hi] of the level blocks (blocks = true) or
-// levels in flight, counted from b0 / level0.
-template <bool DIST, class Cones, class Levels, class Sites>
-int fused_wavefront(lf_router_core &r, fused_args &F, int level0, int nlevels, int b0, int nblocks, bool time_major, hipStream_t s,
-                    int64_t &launches, Cones &&cones, Levels &&levels, Sites &&sites)
+// levels in flight, counted from b0 / level0.  r.last_fused_form tells which of the three ran.
+// Whether the wavefront over levels [level0, level0 + nlevels) takes the time-major form, its caller's precondition given:
+// few, wide levels -- level after level, every level through all its sub-steps (k_fused_level_steps).
+// LF_FUSED_TIME_MAJOR=0 / 1: never / whenever it applies (A/B switch, read per call); LF_FUSED_TIME_MAJOR_LEVELS: the level
+// count up to which it is the default -- each launch carries a dependent chain of nsteps solves (~10 us), so NL launches of
+// that kind must stay small beside what the saved traffic (~3.8 kB per cell and model step) is worth.  The same rule with
+// structures in the loop (measured, DESIGN.md section 4.2: 3000^2 shallow 16.0 -> 5.9 ms, hot-path channel network 6.5 -> 4.1).
+// Takes the [nsteps][N] history (no room inside its budget, remembered in fused_hist_refused: the skewed wavefront).
+inline bool fused_time_major_ready(lf_router_core &r, int level0, int nlevels, int nsteps, bool split)
 {
-    const int nsteps = F.nsteps;
-    const bool split = F.S.split != 0, all35 = r.fused && F.S.Beta == 0.6; // otherwise: run-time flags and OCML pow
-    auto width = [&](int k) { return r.h_level_start[k + 1] - r.h_level_start[k]; };
-    F.level0 = level0;
-    F.nlevels = nlevels;
-    // ---- few, wide levels: level after level, every level through all its sub-steps (k_fused_level_steps) ----------------
-    // LF_FUSED_TIME_MAJOR=0 / 1: never / whenever it applies (A/B switch); LF_FUSED_TIME_MAJOR_LEVELS: the level count up to
-    // which it is the default -- each launch carries a dependent chain of nsteps solves (~10 us), so NL launches of that
-    // kind must stay small beside what the saved traffic (~3.8 kB per cell and model step) is worth
     static const int tm_levels = [] {
         const char *e = std::getenv("LF_FUSED_TIME_MAJOR_LEVELS");
         return e ? std::atoi(e) : 192;
@@ -1801,19 +1906,66 @@ int fused_wavefront(lf_router_core &r, fused_args &F, int level0, int nlevels, i
     const char *e = std::getenv("LF_FUSED_TIME_MAJOR");
     const int64_t cells = r.h_level_start[level0 + nlevels] - r.h_level_start[level0];
     const bool want = e ? e[0] != '0' : (nlevels <= tm_levels && cells >= 20000 * (int64_t)nlevels);
-    // (no room for the history inside its budget, remembered in fused_hist_refused: the skewed wavefront below)
-    if (time_major && want && nsteps > 1 &&
-        lf_history_ensure(r.fused_hist1, r.fused_hist2, r.fused_hist_refused, (size_t)nsteps * (size_t)r.N, split)) {
+    return want && nsteps > 1 &&
+           lf_history_ensure(r.fused_hist1, r.fused_hist2, r.fused_hist_refused, (size_t)nsteps * (size_t)r.N, split);
+}
+
+struct fused_tm_sites { // the site plan (lf_common.h: lf_site_plan_t) on the device, kept with the router
+    const uint8_t *flags;            // [N] 1: link, 2: site cell (null: no site)
+    const int *slot, *site_ptr, *site; // fused_args::tm_slot / tm_site_ptr / tm_site
+    const std::vector<int32_t> *level_ptr; // host copy of site_ptr (null: no site)
+    int64_t nfeed;
+    lf_dbuf<double> *feed;           // [nsteps + 1][nfeed], grown on demand
+};
+template <bool DIST, class Cones, class Levels, class Sites>
+int fused_wavefront(lf_router_core &r, fused_args &F, int level0, int nlevels, int b0, int nblocks, bool time_major, hipStream_t s,
+                    int64_t &launches, Cones &&cones, Levels &&levels, Sites &&sites, const fused_tm_sites *tm = nullptr)
+{
+    const int nsteps = F.nsteps;
+    const bool split = F.S.split != 0, all35 = r.fused && F.S.Beta == 0.6; // otherwise: run-time flags and OCML pow
+    auto width = [&](int k) { return r.h_level_start[k + 1] - r.h_level_start[k]; };
+    F.level0 = level0;
+    F.nlevels = nlevels;
+    // ---- few, wide levels: level after level, every level through all its sub-steps (k_fused_level_steps) ----------------
+    if (time_major && fused_time_major_ready(r, level0, nlevels, nsteps, split)) {
         F.hist1 = r.fused_hist1.p;
         F.hist2 = r.fused_hist2.p;
+        if (tm) {
+            const size_t need = (size_t)(nsteps + 1) * (size_t)tm->nfeed;
+            if (tm->feed->n < need) LF_TRY(tm->feed->grow(need));
+            F.tm_feed = tm->feed->p;
+            F.tm_nfeed = (int)tm->nfeed;
+            F.tm_slot = tm->slot;
+            F.tm_site_ptr = tm->site_ptr;
+            F.tm_site = tm->site;
+        }
+        const uint8_t *const linked = F.linked;
+        if (tm && tm->flags) F.linked = tm->flags;
         for (int k = level0; k < level0 + nlevels; ++k) {
             const int64_t w = width(k);
             if (w <= 0) continue;
             pick_flags(split, all35, [&](auto sp, auto a35) {
+                if constexpr (!DIST) {
+                    if (tm) {
+                        hipLaunchKernelGGL((k_fused_level_steps<sp, a35, false, 1>), dim3(blocks_for(w)), dim3(kBlock), 0, s, F, k);
+                        return;
+                    }
+                }
                 hipLaunchKernelGGL((k_fused_level_steps<sp, a35, DIST>), dim3(blocks_for(w)), dim3(kBlock), 0, s, F, k);
             });
             ++launches;
+            if constexpr (!DIST) {
+                const int64_t ns = tm && tm->level_ptr ? (*tm->level_ptr)[k + 1] - (*tm->level_ptr)[k] : 0;
+                if (ns > 0) { // the site cells of the level, each with its lake or reservoir
+                    pick_flags(split, all35, [&](auto sp, auto a35) {
+                        hipLaunchKernelGGL((k_fused_level_steps<sp, a35, false, 2>), dim3(blocks_for(ns)), dim3(kBlock), 0, s, F, k);
+                    });
+                    ++launches;
+                }
+            }
         }
+        F.linked = linked;
+        r.last_fused_form = 1;
         LF_HIP(hipGetLastError());
         return LF_OK;
     }
@@ -1870,6 +2022,7 @@ int fused_wavefront(lf_router_core &r, fused_args &F, int level0, int nlevels, i
                 ++launches;
             }
         }
+        r.last_fused_form = 2;
         LF_HIP(hipGetLastError());
         return LF_OK;
     }
@@ -1893,6 +2046,7 @@ int fused_wavefront(lf_router_core &r, fused_args &F, int level0, int nlevels, i
         levels(level_grid(pack, acc, widest));
         ++launches;
     }
+    r.last_fused_form = 3;
     LF_HIP(hipGetLastError());
     return LF_OK;
 }

@@ -379,4 +379,21 @@ int lf_graph_get_links(const lf_graph *g, uint8_t *linked)
     return LF_OK;
 }
 
+/* the site plan of the time-major fused form with structures (lf_common.h: lf_site_plan_build), host arrays in and out */
+int lf_site_plan(int64_t n, int nlevels, const int64_t *level_start, int64_t n_lakes, const int32_t *lake_cell,
+                 const int32_t *lake_ups_ptr, const int32_t *lake_ups_idx, int64_t n_res, const int32_t *res_cell,
+                 const int32_t *res_ups_ptr, const int32_t *res_ups_idx, int32_t *applies, int32_t *feed_slot,
+                 int32_t *level_site_ptr, int32_t *level_site)
+{
+    if (!applies || !feed_slot || !level_site_ptr || !level_site) return lf_set_error(LF_E_INVALID, "null argument");
+    lf_site_plan_t P;
+    LF_TRY(lf_site_plan_build(n, nlevels, level_start, n_lakes, lake_cell, lake_ups_ptr, lake_ups_idx, n_res, res_cell,
+                              res_ups_ptr, res_ups_idx, P));
+    *applies = P.applies ? 1 : 0;
+    std::copy(P.slot_of.begin(), P.slot_of.end(), feed_slot);
+    std::copy(P.level_ptr.begin(), P.level_ptr.end(), level_site_ptr);
+    std::copy(P.level_site.begin(), P.level_site.end(), level_site);
+    return LF_OK;
+}
+
 } // extern "C"

@@ -190,6 +190,13 @@ struct lf_router : lf_router_core {
     std::vector<int> site_level_sorted;
     const void *site_key[4] = {nullptr, nullptr, nullptr, nullptr}; // the site lists those levels were checked for
     int64_t site_cnt[2] = {-1, -1};
+    // ... and their plan for the time-major form (lf_common.h: lf_site_plan_t), built with those levels
+    bool tm_applies = false;
+    int64_t tm_nfeed = 0;
+    std::vector<int32_t> tm_level_ptr;            // sites per level (host copy of tm_site_ptr)
+    lf_dbuf<uint8_t> tm_flags;                    // [N] 1: link, 2: site cell
+    lf_dbuf<int32_t> tm_slot, tm_site_ptr, tm_site; // fused_args::tm_slot / tm_site_ptr / tm_site
+    lf_dbuf<double> tm_feed;                      // [nsteps + 1][tm_nfeed] ChanQ of the cells feeding a site
     std::vector<level_segment> schedule; // launches of a call without level blocks (level_segments)
     uint64_t graph_serial = 0; // lf_graph::serial of the graph the router was built on: same object <=> same plan
     // (the fused plan of lf_router_core, fplan, is build_level_blocks' and carries lvl2blk for the sites of the structures
@@ -875,6 +882,8 @@ int lf_count_nonfinite(int device, const double *x_dev, int64_t n, int64_t *coun
 int lf_router_device(const lf_router *r) { return r ? r->device : -1; }
 int64_t lf_router_num_pixels(const lf_router *r) { return r ? r->N : -1; }
 
+int lf_router_last_fused_form(const lf_router *r) { return r ? r->last_fused_form : -1; }
+
 int lf_router_last_launches(const lf_router *r, int64_t stats[4])
 {
     if (!r || !stats) return lf_set_error(LF_E_INVALID, "null argument");
@@ -898,6 +907,7 @@ int lf_router_reset_site_cache(lf_router *r)
     r->site_cnt[0] = r->site_cnt[1] = -1;
     for (const void *&k : r->site_key) k = nullptr;
     r->site_level_sorted.clear();
+    r->tm_applies = false;
     return LF_OK;
 }
 
@@ -1274,14 +1284,20 @@ int fused_impl(lf_router *r, const lf_substep_args *a, int nsteps, int64_t sidef
                              r->h_level_start.begin()) - 1;
             };
             std::vector<int> lv(nsites);
+            std::vector<int32_t> h_cell[2], h_ptr[2], h_idx[2]; // host copies of the lists: lakes, reservoirs
             auto check_sites = [&](int64_t cnt, const int32_t *cell_dev, const int32_t *ptr_dev, const int32_t *idx_dev,
-                                   int64_t off, const char *what) -> int {
+                                   int64_t off, int li, const char *what) -> int {
                 if (cnt == 0) return LF_OK;
                 if (!cell_dev || !ptr_dev || !idx_dev) return lf_set_error(LF_E_INVALID, "%s site lists missing", what);
-                std::vector<int32_t> cell(cnt), ptr(cnt + 1);
+                std::vector<int32_t> &cell = h_cell[li], &ptr = h_ptr[li], &idx = h_idx[li];
+                cell.resize(cnt);
+                ptr.resize(cnt + 1);
                 LF_HIP(hipMemcpy(cell.data(), cell_dev, sizeof(int32_t) * cnt, hipMemcpyDeviceToHost));
                 LF_HIP(hipMemcpy(ptr.data(), ptr_dev, sizeof(int32_t) * (cnt + 1), hipMemcpyDeviceToHost));
-                std::vector<int32_t> idx(std::max<int32_t>(ptr[cnt], 1));
+                if (ptr[0] != 0 || ptr[cnt] < 0) return lf_set_error(LF_E_INVALID, "%s_ups_ptr out of range", what);
+                for (int64_t i = 0; i < cnt; ++i)
+                    if (ptr[i + 1] < ptr[i]) return lf_set_error(LF_E_INVALID, "%s_ups_ptr not ascending", what);
+                idx.resize(std::max<int32_t>(ptr[cnt], 1));
                 if (ptr[cnt] > 0)
                     LF_HIP(hipMemcpy(idx.data(), idx_dev, sizeof(int32_t) * ptr[cnt], hipMemcpyDeviceToHost));
                 for (int64_t i = 0; i < cnt; ++i) {
@@ -1294,8 +1310,33 @@ int fused_impl(lf_router *r, const lf_substep_args *a, int nsteps, int64_t sidef
                 }
                 return LF_OK;
             };
-            LF_TRY(check_sites(I.n_lakes, I.lake_cell, I.lake_ups_ptr, I.lake_ups_idx, 0, "lake"));
-            LF_TRY(check_sites(I.n_res, I.res_cell, I.res_ups_ptr, I.res_ups_idx, I.n_lakes, "reservoir"));
+            LF_TRY(check_sites(I.n_lakes, I.lake_cell, I.lake_ups_ptr, I.lake_ups_idx, 0, 0, "lake"));
+            LF_TRY(check_sites(I.n_res, I.res_cell, I.res_ups_ptr, I.res_ups_idx, I.n_lakes, 1, "reservoir"));
+            // ---- the plan of the time-major form: feed slots, the sites of every level, whether it applies ----
+            r->tm_applies = false;
+            {
+                lf_site_plan_t P;
+                LF_TRY(lf_site_plan_build(n, r->NL, r->h_level_start.data(), I.n_lakes, h_cell[0].data(), h_ptr[0].data(),
+                                          h_idx[0].data(), I.n_res, h_cell[1].data(), h_ptr[1].data(), h_idx[1].data(), P));
+                std::vector<uint8_t> flags((size_t)n, 0);
+                if (r->linked.p) {
+                    LF_HIP(hipMemcpyAsync(flags.data(), r->linked.p, (size_t)n, hipMemcpyDeviceToHost, s));
+                    LF_HIP(hipStreamSynchronize(s));
+                }
+                for (int64_t p = 0; p < n && P.applies; ++p) // a feeder that is no link of the graph would never be written
+                    if (P.slot_of[p] >= 0 && !flags[p]) P.applies = false;
+                if (P.applies) {
+                    for (int li = 0; li < 2; ++li)
+                        for (int32_t c : h_cell[li]) flags[c] |= 2;
+                    LF_TRY(r->tm_flags.upload(flags.data(), flags.size(), s));
+                    LF_TRY(r->tm_slot.upload(P.slot_of.data(), P.slot_of.size(), s));
+                    LF_TRY(r->tm_site_ptr.upload(P.level_ptr.data(), P.level_ptr.size(), s));
+                    LF_TRY(r->tm_site.upload(P.level_site.data(), P.level_site.size(), s));
+                    r->tm_level_ptr = P.level_ptr;
+                    r->tm_nfeed = P.nfeed;
+                    r->tm_applies = true;
+                }
+            }
             LF_TRY(r->site_level.upload(lv.data(), (size_t)nsites, r->ctx->stream));
             F.site_level = r->site_level.p;
             lv_sorted = lv;
@@ -1317,7 +1358,17 @@ int fused_impl(lf_router *r, const lf_substep_args *a, int nsteps, int64_t sidef
             ++launches;
         }
     }
-    if (nsteps > 1 && fused_recompute()) {
+    // time-major: without structures on a graph without links; with them when the site plan applies (no site: nothing to plan)
+    fused_tm_sites tms = {nullptr, nullptr, nullptr, nullptr, nullptr, 0, &r->tm_feed};
+    bool time_major = !in && !F.linked;
+    if (in && (nsites == 0 || r->tm_applies)) {
+        time_major = true;
+        if (nsites > 0) tms = {r->tm_flags.p, r->tm_slot.p, r->tm_site_ptr.p, r->tm_site.p, &r->tm_level_ptr, r->tm_nfeed, &r->tm_feed};
+    }
+    // (the time-major form reads a cell's statics once per model step: recomputing the five derived ones would save 40 B per
+    // cell where the check that allows it reads 72 -- with structures it streams them as given, one launch less)
+    const bool tm_struct = in && time_major && fused_time_major_ready(*r, 0, (int)r->NL, nsteps, a->split != 0);
+    if (nsteps > 1 && fused_recompute() && !tm_struct) {
         LF_TRY(fused_check_derived(*r, *a, s));
         F.recompute = r->derived_ok.p;
         ++launches;
@@ -1377,7 +1428,7 @@ int fused_impl(lf_router *r, const lf_substep_args *a, int nsteps, int64_t sidef
         ++launches;
     };
     const int NB = r->fplan.empty() ? -1 : r->fplan.nblocks();
-    LF_TRY(fused_wavefront<false>(*r, F, 0, (int)r->NL, 0, NB, !in && !F.linked, s, launches, cones, levels, sites));
+    LF_TRY(fused_wavefront<false>(*r, F, 0, (int)r->NL, 0, NB, time_major, s, launches, cones, levels, sites, in ? &tms : nullptr));
     r->last_stats[0] = launches;
     r->last_stats[1] = launches;
     r->last_stats[2] = 0;

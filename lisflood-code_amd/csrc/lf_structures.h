@@ -1,5 +1,6 @@
 // lf_structures.h -- lakes and reservoirs of the routing loop, one lane per site; shared by the sub-step-by-sub-step
-// path (lf_modules.hip: k_inloop_sites) and the fused sub-step wavefront (lf_fused.h: k_sites_wave, k_sites_blocks).
+// path (lf_modules.hip: k_inloop_sites) and the fused sub-step wavefront (lf_fused.h: k_sites_wave, k_sites_blocks and the
+// site lanes of k_fused_level_steps).
 #pragma once
 #include "lf_common.h"
 
@@ -10,11 +11,23 @@ __device__ __forceinline__ double lf_npmax(double a, double b) { return (a != a)
 // lakes.dynamic_inloop (lakes.py:215-258) for lake i (i < n_lakes) or reservoir.dynamic_inloop (reservoir.py:190-296)
 // for reservoir i - n_lakes: inflow = np.bincount(downstruct, weights=ChanQ)[site] in ascending source id, then the
 // site's storage / outflow update; the outflow volume goes to the dense QLakeOutM3Dt / QResOutM3Dt at the site cell.
-__device__ __forceinline__ void lf_site_update(const lf_inloop_args &A, long long i)
+// The gather (lf_site_inflow) and the update (lf_site_body) are apart because the time-major fused form
+// (lf_fused.h: k_fused_level_steps<.., 2>) takes the inflow from its feed buffer instead of ChanQ.
+__device__ __forceinline__ double lf_site_inflow(const lf_inloop_args &A, long long i)
+{
+    double inflow = 0.0; // np.bincount(downstruct, weights=ChanQ)[LakeIndex / ReservoirIndex]: ascending source id
+    if (i < A.n_lakes) {
+        for (int e = A.lake_ups_ptr[i]; e < A.lake_ups_ptr[i + 1]; ++e) inflow += A.ChanQ[A.lake_ups_idx[e]];
+    } else if (i - A.n_lakes < A.n_res) {
+        const long long r = i - A.n_lakes;
+        for (int e = A.res_ups_ptr[r]; e < A.res_ups_ptr[r + 1]; ++e) inflow += A.ChanQ[A.res_ups_idx[e]];
+    }
+    return inflow;
+}
+
+__device__ __forceinline__ void lf_site_body(const lf_inloop_args &A, long long i, const double inflow)
 {
     if (i < A.n_lakes) {
-        double inflow = 0.0; // np.bincount(downstruct, weights=ChanQ)[LakeIndex]: ascending source id
-        for (int e = A.lake_ups_ptr[i]; e < A.lake_ups_ptr[i + 1]; ++e) inflow += A.ChanQ[A.lake_ups_idx[e]];
         A.LakeInflowCC[i] = inflow;
         const double lake_in = (inflow + A.LakeInflowOldCC[i]) * 0.5;
         A.LakeInflowOldCC[i] = inflow;
@@ -33,8 +46,6 @@ __device__ __forceinline__ void lf_site_update(const lf_inloop_args &A, long lon
     const long long r = i - A.n_lakes;
     if (r >= 0 && r < A.n_res) {
         const double inv_day = 1 / 86400.0; // 1 / float(86400)
-        double inflow = 0.0;
-        for (int e = A.res_ups_ptr[r]; e < A.res_ups_ptr[r + 1]; ++e) inflow += A.ChanQ[A.res_ups_idx[e]];
         A.ReservoirInflowCC[r] = inflow;
         const double tot = A.TotalReservoirStorageM3CC[r];
         double st = A.ReservoirStorageM3CC[r] + inflow * A.DtRouting;
@@ -66,3 +77,5 @@ __device__ __forceinline__ void lf_site_update(const lf_inloop_args &A, long lon
         A.QResOutM3Dt[A.res_cell[r]] = out_m3;
     }
 }
+
+__device__ __forceinline__ void lf_site_update(const lf_inloop_args &A, long long i) { lf_site_body(A, i, lf_site_inflow(A, i)); }

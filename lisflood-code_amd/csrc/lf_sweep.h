@@ -1138,6 +1138,7 @@ struct lf_router_core {
     lf_dbuf<double> fused_qr1, fused_qr2;     // fused sub-steps: router outputs by sub-step parity (fused_args::qr1 / qr2)
     lf_dbuf<double> fused_hist1, fused_hist2; // [nsteps][N] router outputs of every sub-step (k_fused_level_steps)
     size_t fused_hist_refused = SIZE_MAX;     // smallest history size that did not fit its budget (lf_history_ensure)
+    int last_fused_form = 0; // schedule of the last fused_wavefront: 1 time-major, 2 level blocks, 3 levels (0: none yet)
     std::vector<int64_t> h_level_start;
     // level blocks and cones (lf_blocks.h) of the fused sub-step wavefront; empty: the level-by-level wavefront
     lf_block_plan fplan;

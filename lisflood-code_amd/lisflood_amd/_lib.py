@@ -43,7 +43,7 @@ _SIGNATURES = {
     "iqppp": "gather_device",
     "iup": "xcd_contiguous_order",
     "izp": "device_alloc host_alloc",
-    "p": "struct_sizes device_count graph_max_upstream router_device router_reset_site_cache "
+    "p": "struct_sizes device_count graph_max_upstream router_device router_reset_site_cache router_last_fused_form "
          "dist_graph_local_num_phases dist_graph_num_phases comm_unique_id comm_close",
     "pi": "router_profile_enable dist_graph_finalize",
     "piiip": "comm_create",
@@ -82,6 +82,7 @@ _SIGNATURES = {
     "ppppiiii": "dist_router_route_many",
     "ppppppp": "dist_graph_get_fused_plan",
     "pppppppp": "dist_graph_get_route_plan",
+    "qipqpppqppppppp": "site_plan",
     "p>q": "graph_num_pixels graph_num_levels router_num_pixels dist_graph_num_pixels dist_graph_state_size "
            "dist_graph_num_launch_units dist_graph_num_noncontiguous dist_router_state_size "
            "dist_router_last_launches",

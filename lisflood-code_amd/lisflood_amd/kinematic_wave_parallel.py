@@ -300,6 +300,17 @@ class kinematicWave:
         check(lib().lf_router_last_launches(self._h, s))
         return dict(launches=s[0], wide=s[1], narrow=s[2], levels=s[3])
 
+    FUSED_FORMS = {0: None, 1: "time-major", 2: "level blocks", 3: "levels"}
+
+    def last_fused_form(self):
+        """Which schedule the last fused sub-step call on this router took (lf_router_last_fused_form): "time-major"
+        (level after level, every level through all its sub-steps), "level blocks" or "levels" (the skewed wavefront over
+        level blocks / over single levels); None before the first such call."""
+        form = int(lib().lf_router_last_fused_form(self._h))
+        if form < 0:
+            raise RuntimeError("router is closed")
+        return self.FUSED_FORMS[form]
+
     def route_plan_stats(self):
         """shape of the block plan of single router calls; lane_use = cells per 64-lane cone level"""
         s = (C.c_int64 * 6)()

@@ -663,8 +663,12 @@ class routing(HydroModule):
         skewed wavefront over (level, sub-step) on the device -- NL + NoRoutSteps - 1 launches instead of
         NoRoutSteps x (1..2) x NL.  `sideflows`: SideflowChanM3 of the step -- one [N] vector (the model's case
         when nothing in the loop changes it) or [NoRoutSteps, N]; default: assembled from `var` as in dynamic().
-        Bit-identical to calling dynamic(0..NoRoutSteps-1).  In-loop modules (lakes, reservoirs...) cannot run
-        inside the wavefront; use dynamic() when they are active."""
+        Bit-identical to calling dynamic(0..NoRoutSteps-1).  Host in-loop modules cannot run inside the call; after
+        attach_structures() the lakes, reservoirs, inflow hydrographs and transmission loss run inside it on the device
+        (engine_order=True).  On graphs of few wide levels the library takes the time-major form instead of the skew
+        -- one launch per level through all sub-steps, the state in registers --, with structures too when no site
+        cell feeds another site and no two sites share a cell (LF_FUSED_TIME_MAJOR=0 / 1: never / whenever it
+        applies); river_router.last_fused_form() tells which schedule ran.  Same bits either way."""
         if self.river_router is None:
             raise RuntimeError("routing.initialSecond()/attach_router() must be called first")
         if self.inloop_modules:
