@@ -423,12 +423,17 @@ void lfo_soil_stats(int64_t out[4]) { memcpy(out, g_soil_stats, sizeof(g_soil_st
 /* histogram of floor(log2(nsub)) over the columns of the last call (workload characterisation for the bench) */
 static int64_t g_soil_hist[32];
 void lfo_soil_substep_hist(int64_t out[32]) { memcpy(out, g_soil_hist, sizeof(g_soil_hist)); }
+/* out[k] = columns of the last call that took k sub-steps, k = 1 included; the last bin holds k >= 127 (the layout of the
+ * engine's lf_soil_substep_histogram, which leaves k = 1 out) */
+static int64_t g_soil_trips[128];
+void lfo_soil_trip_hist(int64_t out[128]) { memcpy(out, g_soil_trips, sizeof(g_soil_trips)); }
 
 void lfo_soil_columns(const lfo_soil_args *A)
 {
     int64_t st_cols = 0, st_multi = 0, st_sum = 0, st_max = 0;
     const int64_t N = A->N;
     memset(g_soil_hist, 0, sizeof(g_soil_hist));
+    memset(g_soil_trips, 0, sizeof(g_soil_trips));
     int64_t count_paddy = 0;
     for (int64_t veg = 0; veg < A->V; ++veg) {
         const uint8_t *inactive = NULL;
@@ -509,6 +514,8 @@ void lfo_soil_columns(const lfo_soil_args *A)
                 int c = 0;
                 for (int64_t t = nsub; t > 1 && c < 31; t >>= 1) ++c;
                 g_soil_hist[c] += 1;
+#pragma omp atomic
+                g_soil_trips[nsub < 127 ? nsub : 127] += 1;
             }
             /* sub-step loop, :266-312 */
             double wt1a = w1a, wt1b = w1b, wt2 = w2;

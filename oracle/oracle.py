@@ -205,6 +205,14 @@ def soil_columns(d):
     lib().lfo_soil_columns(C.byref(a))
 
 
+def soil_trip_hist():
+    """hist[k] = columns of the last soil_columns call that took k Courant sub-steps, k = 1 included; the last bin holds
+    k >= 127 (the layout of lf_soil_substep_histogram, which leaves k = 1 out)"""
+    out = np.zeros(128, np.int64)
+    lib().lfo_soil_trip_hist(_ptr(out))
+    return out
+
+
 def upstream_sum(downstruct, w):
     out = np.empty(w.size)
     lib().lfo_upstream_sum(_ptr(np.ascontiguousarray(downstruct, dtype=np.int32)), _ptr(_f(w)), C.c_int64(w.size),
