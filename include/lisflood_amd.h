@@ -292,6 +292,21 @@ int lf_routing_substeps_fused(lf_router *r, const lf_substep_args *a, int nsteps
  * first, then their channel routing in one call.  Bit-identical to the step-by-step calls. */
 int lf_routing_model_steps_fused(lf_router *r, const lf_substep_args *a, int steps_per_model_step, int n_model_steps,
                                  int64_t sideflow_model_stride);
+/* An ensemble through the sub-step loop: `members` (>= 1) state rows on ONE router.  `a` is one argument block: its static
+ * pointers are [N] and shared by all members, its state, output and sideflow pointers are the rows of member 0; member m's
+ * state and output rows sit m * member_stride elements further (member_stride >= N; elements between N and the stride are
+ * neither read nor written), its sideflow m * sideflow_member_stride elements further (0: every member reads member 0's;
+ * otherwise >= N with sideflow_stride = 0, >= nsteps * N with sideflow_stride = N).  Needs engine_order = 1 and a graph
+ * without structure links.  Where the time-major form applies (few wide levels; LF_FUSED_TIME_MAJOR=0 / 1: never / whenever
+ * possible) the members are a second grid dimension of its level kernel: one launch per level for a whole slice of members
+ * (as many as the history of their router outputs has room for; LF_FUSED_MEMBERS_SLICE caps it).  Otherwise the members run
+ * one after the other through the single call's schedule.  Either way every member's result is bit-identical to
+ * lf_routing_substeps_fused on that member alone; lf_router_last_fused_form / lf_router_last_launches tell what ran. */
+int lf_routing_substeps_fused_members(lf_router *r, const lf_substep_args *a, int nsteps, int64_t sideflow_stride,
+                                      int members, int64_t member_stride, int64_t sideflow_member_stride);
+/* members per slice of the time-major member form: the largest s <= min(members, 65535, cap if cap > 0) with
+ * s * nsteps * n * 8 * (split ? 2 : 1) <= budget_bytes; 0 when not even one member fits (host only) */
+int64_t lf_fused_members_slice(int members, int64_t n, int nsteps, int split, int64_t budget_bytes, int cap);
 
 /* ---------------------------------------------------------------------------------------------
  * LDD one-hop upstream reduction == np.bincount(downstruct, weights)[:N] (routing.py:159-164,

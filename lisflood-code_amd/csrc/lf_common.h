@@ -160,6 +160,23 @@ struct lf_dbuf { // owning device buffer
 // two buffers already hold) -- and a refused size is remembered, so a router that does not fit never pays a multi-GB
 // hipMalloc / failed hipMalloc / synchronising hipFree per call.  -> true: both buffers hold `count` doubles (h2 only
 // if `two`).
+// The budget itself (bytes; counting what the two buffers already hold) -> false: the device did not tell.
+inline bool lf_history_budget(const lf_dbuf<double> &h1, const lf_dbuf<double> &h2, size_t &budget)
+{
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
+    const size_t held = (h1.p ? h1.n : 0) * sizeof(double) + (h2.p ? h2.n : 0) * sizeof(double);
+    budget = (free_b + held) / 2;
+    static const long long cap = [] {
+        const char *e = std::getenv("LF_FUSED_TIME_MAJOR_MAX_BYTES");
+        return e ? std::atoll(e) : -1ll;
+    }();
+    if (cap >= 0) budget = std::min((size_t)cap, free_b + held);
+    return true;
+}
 inline bool lf_history_ensure(lf_dbuf<double> &h1, lf_dbuf<double> &h2, size_t &refused_bytes, size_t count, bool two)
 {
     const bool ok1 = h1.p && h1.n >= count, ok2 = !two || (h2.p && h2.n >= count);
@@ -167,20 +184,9 @@ inline bool lf_history_ensure(lf_dbuf<double> &h1, lf_dbuf<double> &h2, size_t &
     const size_t total = count * sizeof(double) * (two ? 2 : 1);
     if (total >= refused_bytes) return false;
     size_t budget = 0;
-    {
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) {
-            (void)hipGetLastError();
-            refused_bytes = total;
-            return false;
-        }
-        const size_t held = (h1.p ? h1.n : 0) * sizeof(double) + (h2.p ? h2.n : 0) * sizeof(double);
-        budget = (free_b + held) / 2;
-        static const long long cap = [] {
-            const char *e = std::getenv("LF_FUSED_TIME_MAJOR_MAX_BYTES");
-            return e ? std::atoll(e) : -1ll;
-        }();
-        if (cap >= 0) budget = std::min((size_t)cap, free_b + held);
+    if (!lf_history_budget(h1, h2, budget)) {
+        refused_bytes = total;
+        return false;
     }
     if (total > budget) {
         refused_bytes = total;

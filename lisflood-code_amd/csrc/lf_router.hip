@@ -1231,8 +1231,10 @@ extern "C" int lf_routing_substep(lf_router *r, const lf_substep_args *a)
 
 namespace {
 
+// flags_ready: the statics' flag passes (k_inert_flags, k_check_derived) are not run -- an earlier call of the same ensemble call,
+// with the same static vectors, left them with the router (fused_members_impl)
 int fused_impl(lf_router *r, const lf_substep_args *a, int nsteps, int64_t sideflow_stride, const lf_inloop_args *in,
-               int msteps = 0, int64_t side_mstride = 0)
+               int msteps = 0, int64_t side_mstride = 0, bool flags_ready = false)
 {
     if (!r || !a || nsteps < 1) return lf_set_error(LF_E_INVALID, "bad argument");
     if (!a->engine_order) return lf_set_error(LF_E_INVALID, "the fused sub-step wavefront needs engine-order vectors");
@@ -1352,10 +1354,12 @@ int fused_impl(lf_router *r, const lf_substep_args *a, int nsteps, int64_t sidef
         const char *e = std::getenv("LF_NO_INERT_SKIP"); // A/B switch
         if (!in && r->n_isolated > 0 && nsteps > 1 && !(e && e[0] == '1')) {
             if (!r->inert.p) LF_TRY(r->inert.alloc(n));
-            hipLaunchKernelGGL(k_inert_flags, dim3(blocks_for(n)), dim3(kBlock), 0, s, (long long)n, *a, r->isolated.p,
-                               r->a1.p, r->a2.p, F.dx, r->inert.p);
+            if (!flags_ready) {
+                hipLaunchKernelGGL(k_inert_flags, dim3(blocks_for(n)), dim3(kBlock), 0, s, (long long)n, *a, r->isolated.p,
+                                   r->a1.p, r->a2.p, F.dx, r->inert.p);
+                ++launches;
+            }
             F.inert = r->inert.p;
-            ++launches;
         }
     }
     // time-major: without structures on a graph without links; with them when the site plan applies (no site: nothing to plan)
@@ -1369,9 +1373,11 @@ int fused_impl(lf_router *r, const lf_substep_args *a, int nsteps, int64_t sidef
     // cell where the check that allows it reads 72 -- with structures it streams them as given, one launch less)
     const bool tm_struct = in && time_major && fused_time_major_ready(*r, 0, (int)r->NL, nsteps, a->split != 0);
     if (nsteps > 1 && fused_recompute() && !tm_struct) {
-        LF_TRY(fused_check_derived(*r, *a, s));
+        if (!flags_ready) {
+            LF_TRY(fused_check_derived(*r, *a, s));
+            ++launches;
+        }
         F.recompute = r->derived_ok.p;
-        ++launches;
     }
     const bool all35 = r->fused && a->Beta == 0.6; // otherwise: run-time flags and inlined OCML pow, as fused_cell
     auto cones = [&](int64_t ncones) {
@@ -1458,6 +1464,154 @@ extern "C" int lf_routing_substeps_fused_structures(lf_router *r, const lf_subst
 {
     if (!in) return lf_set_error(LF_E_INVALID, "null argument");
     return fused_impl(r, a, nsteps, 0, in);
+}
+
+// ================================================================================================
+// An ensemble through the sub-step loop: `members` state rows on ONE router, sharing its statics and its launch schedule.
+// Where the time-major form applies the members are a second grid dimension of its level kernel
+// (k_fused_level_steps_members), slice by slice: a slice is as many members as the history [slice][nsteps][N] has room
+// for inside its budget.  Otherwise the members run one after the other through the single-member schedule -- correct and
+// bit-identical, with no gain but the flag passes, which run once.
+// ================================================================================================
+extern "C" int64_t lf_fused_members_slice(int members, int64_t n, int nsteps, int split, int64_t budget_bytes, int cap)
+{
+    if (members < 1 || n < 0 || nsteps < 1 || budget_bytes < 0) return 0;
+    int64_t s = std::min<int64_t>(members, 65535); // blockIdx.y
+    if (cap > 0) s = std::min<int64_t>(s, cap);
+    const __int128 per = (__int128)nsteps * n * 8 * (split ? 2 : 1); // bytes of one member's history
+    if (per > 0) s = (int64_t)std::min<__int128>(s, (__int128)budget_bytes / per);
+    return s;
+}
+
+namespace {
+
+// `a` with every per-member row moved m members on
+lf_substep_args member_args(const lf_substep_args &a, int64_t m, int64_t member_stride, int64_t side_member_stride)
+{
+    lf_substep_args b = a;
+    auto move = [&](double *&x) {
+        if (x) x += m * member_stride;
+    };
+    b.SideflowChanM3 += m * side_member_stride;
+    move(b.ChanQKin);
+    move(b.ChanM3Kin);
+    move(b.Chan2QKin);
+    move(b.Chan2M3Kin);
+    move(b.CrossSection2Area);
+    move(b.Sideflow1Chan);
+    move(b.ChanQ);
+    move(b.sumDisDay);
+    move(b.FlowVelocity);
+    move(b.TravelDistance);
+    return b;
+}
+
+int fused_members_impl(lf_router *r, const lf_substep_args *a, int nsteps, int64_t sideflow_stride, int members,
+                       int64_t member_stride, int64_t side_member_stride)
+{
+    LF_HIP(hipSetDevice(r->device));
+    const int64_t n = r->N;
+    const int NL = (int)r->NL;
+    const bool split = a->split != 0;
+    // ---- does the member form of the time-major schedule apply, and on slices of how many members? -------------------
+    int64_t slice = 0;
+    {
+        // the single call's rule (fused_time_major_ready) with the lanes of a launch counted over the members
+        const bool want = fused_time_major_wanted(NL, (int64_t)members * n);
+        size_t budget = 0;
+        if (want && nsteps > 1 && lf_history_budget(r->fused_hist1, r->fused_hist2, budget)) {
+            const char *c = std::getenv("LF_FUSED_MEMBERS_SLICE"); // A/B switch, read per call
+            slice = lf_fused_members_slice(members, n, nsteps, split, (int64_t)std::min<size_t>(budget, INT64_MAX),
+                                           c ? std::atoi(c) : 0);
+            // (the size was cut to the budget first, so nothing is refused for its size -- and a history that still does not
+            // come is not remembered in r->fused_hist_refused, which belongs to the single call's own, smaller, request)
+            size_t refused = SIZE_MAX;
+            if (slice > 0 && !lf_history_ensure(r->fused_hist1, r->fused_hist2, refused, (size_t)slice * nsteps * (size_t)n, split))
+                slice = 0;
+        }
+    }
+    int64_t launches = 0;
+    if (slice == 0) { // member after member through the single-member schedule
+        for (int m = 0; m < members; ++m) {
+            const lf_substep_args b = member_args(*a, m, member_stride, side_member_stride);
+            LF_TRY(fused_impl(r, &b, nsteps, sideflow_stride, nullptr, 0, 0, m > 0));
+            launches += r->last_stats[0];
+        }
+    } else {
+        if (!r->fused_qr1.p) LF_TRY(r->fused_qr1.alloc(2 * n)); // (as fused_impl leaves a router: other forms find them)
+        if (split && !r->fused_qr2.p) LF_TRY(r->fused_qr2.alloc(2 * n));
+        fused_args F = fused_args_of(*r, *a, nsteps, nsteps, sideflow_stride, 0);
+        hipStream_t s = r->ctx->stream;
+        const char *e = std::getenv("LF_NO_INERT_SKIP");
+        if (r->n_isolated > 0 && !(e && e[0] == '1')) { // statics only: once for all members
+            if (!r->inert.p) LF_TRY(r->inert.alloc(n));
+            hipLaunchKernelGGL(k_inert_flags, dim3(blocks_for(n)), dim3(kBlock), 0, s, (long long)n, *a, r->isolated.p, r->a1.p,
+                               r->a2.p, F.dx, r->inert.p);
+            F.inert = r->inert.p;
+            ++launches;
+        }
+        if (fused_recompute()) {
+            LF_TRY(fused_check_derived(*r, *a, s));
+            F.recompute = r->derived_ok.p;
+            ++launches;
+        }
+        F.hist1 = r->fused_hist1.p;
+        F.hist2 = r->fused_hist2.p;
+        F.nlevels = NL;
+        const bool all35 = r->fused && a->Beta == 0.6;
+        for (int64_t m0 = 0; m0 < members; m0 += slice) {
+            const int64_t cnt = std::min<int64_t>(slice, members - m0);
+            F.S = member_args(*a, m0, member_stride, side_member_stride);
+            for (int k = 0; k < NL; ++k) {
+                const int64_t w = r->h_level_start[k + 1] - r->h_level_start[k];
+                if (w <= 0) continue;
+                pick_flags(split, all35, [&](auto sp, auto a35) {
+                    hipLaunchKernelGGL((k_fused_level_steps_members<sp, a35>), dim3(blocks_for(w), (unsigned)cnt), dim3(kBlock), 0, s,
+                                       F, k, (long long)member_stride, (long long)side_member_stride);
+                });
+                ++launches;
+            }
+        }
+        r->last_fused_form = 1;
+        LF_HIP(hipGetLastError());
+    }
+    r->last_stats[0] = launches;
+    r->last_stats[1] = launches;
+    r->last_stats[2] = 0;
+    r->last_stats[3] = r->NL;
+    return LF_OK;
+}
+
+} // namespace
+
+extern "C" int lf_routing_substeps_fused_members(lf_router *r, const lf_substep_args *a, int nsteps, int64_t sideflow_stride,
+                                                 int members, int64_t member_stride, int64_t sideflow_member_stride)
+{
+    if (members < 1) return lf_set_error(LF_E_INVALID, "members must be at least 1 (got %d)", members);
+    if (member_stride < 0)
+        return lf_set_error(LF_E_INVALID, "member_stride %lld is less than the router's number of cells", (long long)member_stride);
+    if (sideflow_member_stride < 0)
+        return lf_set_error(LF_E_INVALID, "sideflow_member_stride %lld is neither 0 nor a whole member's sideflow rows",
+                            (long long)sideflow_member_stride);
+    if (!r || !a) return lf_set_error(LF_E_INVALID, "null argument");
+    if (nsteps < 1) return lf_set_error(LF_E_INVALID, "bad argument");
+    if (member_stride < r->N)
+        return lf_set_error(LF_E_INVALID, "member_stride %lld is less than the router's number of cells (%lld)",
+                            (long long)member_stride, (long long)r->N);
+    if (!a->engine_order) return lf_set_error(LF_E_INVALID, "the fused sub-step wavefront needs engine-order vectors");
+    if (a->split && !r->has_floodplains)
+        return lf_set_error(LF_E_SECTION, "split routing requested but the router has no floodplain alpha");
+    if (sideflow_stride != 0 && sideflow_stride != r->N) return lf_set_error(LF_E_INVALID, "sideflow_stride must be 0 or N");
+    const int64_t side_rows = sideflow_stride == 0 ? r->N : (int64_t)nsteps * r->N;
+    if (sideflow_member_stride != 0 && sideflow_member_stride < side_rows)
+        return lf_set_error(LF_E_INVALID, "sideflow_member_stride %lld is neither 0 nor a whole member's sideflow rows (%lld)",
+                            (long long)sideflow_member_stride, (long long)side_rows);
+    if (r->linked.p)
+        return lf_set_error(LF_E_INVALID, "a router on a graph with structure links runs no ensemble through the sub-step loop "
+                                          "(lf_routing_substeps_fused_members)");
+    if (members == 1) return fused_impl(r, a, nsteps, sideflow_stride, nullptr);
+    if (r->N == 0) return LF_OK;
+    return fused_members_impl(r, a, nsteps, sideflow_stride, members, member_stride, sideflow_member_stride);
 }
 
 // ================================================================================================

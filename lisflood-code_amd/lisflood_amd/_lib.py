@@ -65,6 +65,7 @@ _SIGNATURES = {
     "ppipp": "dist_router_pack",
     "ppiq": "routing_substeps_fused",
     "ppiqi": "dist_fused_phase",
+    "ppiqiqq": "routing_substeps_fused_members",
     "ppp": "graph_get_orders router_to_engine_order router_from_engine_order upstream_sum_device "
            "upstream_sum_host accuflux_host accuflux_ordered_device downstream_device downstream_host "
            "catchments_device catchments catchment_totals_device catchment_totals_host "
@@ -87,6 +88,7 @@ _SIGNATURES = {
            "dist_graph_num_launch_units dist_graph_num_noncontiguous dist_router_state_size "
            "dist_router_last_launches",
     "pii>q": "dist_graph_round_recv_slot",
+    "iqiiqi>q": "fused_members_slice",
     ">s": "last_error",
     "p>v": "graph_destroy router_destroy dist_graph_destroy comm_destroy dist_router_destroy",
 }

@@ -237,6 +237,27 @@ class kinematicWave:
                                  "%d bytes)" % (members, N, stride, need, a.dtype, a.nbytes))
         return members
 
+    def routing_substeps_members(self, args, nsteps, members, member_stride=None, sideflow_stride=0,
+                                 sideflow_member_stride=None):
+        """nsteps routing sub-steps of `members` members in one call (lf_routing_substeps_fused_members): `args` is one
+        lf_substep_args block in engine order whose state, output and sideflow pointers are member 0's rows; member m's rows
+        sit m * member_stride elements further (default N), its sideflow m * sideflow_member_stride (default: the rows back to
+        back -- N with sideflow_stride 0, nsteps * N with sideflow_stride N; 0: every member reads member 0's).  Every member
+        ends up as lf_routing_substeps_fused on it alone would leave it; asynchronous.  (Strides the router cannot take are
+        the library's to refuse, with its own message.)"""
+        nsteps, members, N = int(nsteps), int(members), self.num_pixels
+        if members < 1:
+            raise ValueError("members must be at least 1 (got %d)" % members)
+        if nsteps < 1:
+            raise ValueError("nsteps must be at least 1 (got %d)" % nsteps)
+        if int(sideflow_stride) not in (0, N):
+            raise ValueError("sideflow_stride must be 0 or %d (got %d)" % (N, int(sideflow_stride)))
+        member_stride = N if member_stride is None else int(member_stride)
+        if sideflow_member_stride is None:
+            sideflow_member_stride = N if int(sideflow_stride) == 0 else nsteps * N
+        check(lib().lf_routing_substeps_fused_members(self._h, C.byref(args), nsteps, int(sideflow_stride), members,
+                                                      member_stride, int(sideflow_member_stride)))
+
     def to_engine_order_members(self, src_pix_dev, members, dst_ord_dev=None):
         """[members, N] pixel order -> engine order, row by row (not on the hot path)"""
         N = self.num_pixels

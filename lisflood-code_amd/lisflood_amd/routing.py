@@ -61,12 +61,14 @@ class SubstepVectors:
     either is made.  `host`: name -> vector of n_dev entries (substep_host_vectors); a name it does not hold is zeroed.
     state_size: length of the two router state vectors (ChanQKin, Chan2QKin) where ghost slots follow the n_dev cells;
     sideflow: host [rows, n_dev] (default: one zeroed row).  No buffer is shorter than one element.  `order`: the names the
-    constructor allocates, in that order (each caller keeps the buffer placement it had); allocate() makes the rest later."""
+    constructor allocates, in that order (each caller keeps the buffer placement it had); allocate() makes the rest later.
+    lengths: name -> entries of its vector where that is not n_dev (the [members][stride] rows of routingEnsemble)."""
 
     def __init__(self, host, n_dev, Beta, InvDtRouting, DtSec, split, engine_order, device=0, state_size=None,
-                 sideflow=None, order=_STATIC + _STATE + _OUT + ["scratch0", "scratch1", "SideflowChanM3"]):
+                 sideflow=None, order=_STATIC + _STATE + _OUT + ["scratch0", "scratch1", "SideflowChanM3"], lengths=None):
         self.device, self.dev, self._host = device, {}, dict(host)
         self._len = {k: n_dev for k, t in _SubstepArgs._fields_ if t is C.c_void_p}      # entries of a name's host vector
+        self._len.update(lengths or {})
         if sideflow is not None:
             self._host["SideflowChanM3"] = f64(sideflow).reshape(-1)
             self._len["SideflowChanM3"] = self._host["SideflowChanM3"].size
@@ -756,6 +758,98 @@ def _fused(self, sideflows):
         out[perm] = sv.download(k)[:Nk]
         setattr(v, k, out)
     sv.free()
+
+
+class routingEnsemble:
+    """An ensemble that lives on the device: `members` sets of routing state on ONE router, run through the sub-step loop of a
+    model step in one call (lf_routing_substeps_fused_members).  The members share the LDD, the channel geometry and every
+    static vector -- a forecast ensemble, a calibration batch over the forcing, an EnKF -- and differ in state and sideflow.
+
+    `var`: the namespace routing.dynamic reads (statics, Beta, InvDtRouting, DtSec, NoRoutSteps; pixel order); every member
+    starts from the state it holds (zeros where it holds none).  `router`: the kinematicWave of the domain (with
+    alpha_floodplains for split routing).  State and output rows are [members][member_stride] in engine order
+    (member_stride >= N, default N); set_state / state permute at the boundary.  Every member ends up as its own
+    routing.dynamic_fused call would leave it, bit for bit; where the library's time-major form applies
+    (last_fused_form() == "time-major") the whole ensemble costs the launches of one member per slice of members."""
+
+    def __init__(self, var, router, members, split_routing=False, member_stride=None, device=0):
+        members = int(members)
+        if members < 1:
+            raise ValueError("members must be at least 1 (got %d)" % members)
+        self.var, self.router, self.members, self.split, self.device = var, router, members, bool(split_routing), device
+        N = self.N = router.num_pixels
+        self.stride = N if member_stride is None else int(member_stride)
+        if self.stride < N:
+            raise ValueError("member_stride %d is less than the router's %d cells" % (self.stride, N))
+        self.nsteps = int(var.NoRoutSteps)
+        self.perm = router.graph.layout()[0].astype(np.int64)                          # position -> pixel
+        rows = (members - 1) * self.stride + N                                          # entries of a vector of member rows
+        host = substep_host_vectors(var, N, self.perm, _STATIC)
+        self.vectors = SubstepVectors(host, N, var.Beta, var.InvDtRouting, var.DtSec, self.split, True, device,
+                                      lengths={k: rows for k in _STATE + _OUT})
+        self._side = None
+        start = substep_host_vectors(var, N, None, _STATE)
+        for k in _STATE:
+            self.set_state(k, np.broadcast_to(start[k], (members, N)))
+
+    def _member_rows(self, name, host):
+        """host [members, N] float64 in pixel order, or ValueError"""
+        if name not in _STATE + _OUT:
+            raise ValueError("no state or output vector of the routing sub-step is called %r" % (name,))
+        if not (isinstance(host, np.ndarray) and host.dtype == np.float64 and host.shape == (self.members, self.N)):
+            raise ValueError("%s must be a float64 [%d, %d] array (members, pixels)" % (name, self.members, self.N))
+        return host
+
+    def set_state(self, name, host):
+        """member rows of a state vector from host[members, N] in pixel order (the padding between rows becomes 0)"""
+        host = self._member_rows(name, host)
+        rows = np.zeros((self.members, self.stride))
+        rows[:, :self.N] = host[:, self.perm]
+        self.vectors.upload(name, rows.reshape(-1)[:(self.members - 1) * self.stride + self.N])
+
+    def state(self, name):
+        """host[members, N] in pixel order of a state or output vector"""
+        if name not in _STATE + _OUT:
+            raise ValueError("no state or output vector of the routing sub-step is called %r" % (name,))
+        flat = np.zeros(self.members * self.stride)
+        flat[:(self.members - 1) * self.stride + self.N] = self.vectors.download(name)
+        out = np.empty((self.members, self.N))
+        out[:, self.perm] = flat.reshape(self.members, self.stride)[:, :self.N]
+        return out
+
+    def _sideflow_rows(self, sideflows):
+        """-> (host array as given, sideflow_stride, sideflow_member_stride) for [N], [M, N] or [M, NoRoutSteps, N]"""
+        M, S, N = self.members, self.nsteps, self.N
+        x = sideflows
+        if not (isinstance(x, np.ndarray) and x.dtype == np.float64 and x.shape in ((N,), (M, N), (M, S, N))):
+            raise ValueError("sideflows must be a float64 array shaped [%d], [%d, %d] or [%d, %d, %d] (pixels; members, pixels; "
+                             "members, sub-steps, pixels)" % (N, M, N, M, S, N))
+        return x, (N if x.ndim == 3 else 0), (0 if x.ndim == 1 else x.size // M)
+
+    def dynamic_fused(self, sideflows):
+        """One model step (NoRoutSteps sub-steps) of every member in one call.  `sideflows` (pixel order): [N] -- one vector for
+        all members and sub-steps --, [members, N] or [members, NoRoutSteps, N].  sumDisDay is zeroed first, as the model does
+        at the start of a model step (Lisflood_dynamic.py:177)."""
+        x, side_stride, side_member_stride = self._sideflow_rows(sideflows)
+        x = f64(x[..., self.perm])
+        if self._side is None or self._side.nbytes != x.nbytes:
+            if self._side is not None:
+                self._side.free()
+            self._side = DeviceArray(x.shape, np.float64, self.device)
+        self._side.upload(x)
+        self.vectors.dev["sumDisDay"].zero()
+        args = self.vectors.with_overrides(SideflowChanM3=self._side.ptr.value)
+        self.router.routing_substeps_members(args, self.nsteps, self.members, self.stride, side_stride, side_member_stride)
+
+    def last_fused_form(self):
+        """the schedule the last call took: "time-major" when the members went through the member kernel"""
+        return self.router.last_fused_form()
+
+    def free(self):
+        self.vectors.free()
+        if self._side is not None:
+            self._side.free()
+            self._side = None
 
 
 def var_from_fixture(g):
