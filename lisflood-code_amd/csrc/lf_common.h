@@ -211,12 +211,14 @@ inline bool lf_history_ensure(lf_dbuf<double> &h1, lf_dbuf<double> &h2, size_t &
 //  * the sites of every level: level_site[level_ptr[k] .. level_ptr[k + 1]) are the sites (lakes 0 .. n_lakes - 1, then the
 //    reservoirs) whose cell is on level k, ascending;
 //  * applies: no site cell feeds another site (chained sites), no two sites share a cell, no cell feeds two sites and every
-//    feeder is on its site's level -- otherwise the skewed wavefront runs.  The arrays are complete only if it applies.
+//    feeder is on its site's level -- otherwise the skewed wavefront runs.  The arrays are complete only if it applies;
+//  * whether or not it applies: site_level[i], the level of site i's cell, site_level_sorted, the same ascending, and
+//    off_level_site, the first site with a feeder off its own level (-1: none) -- no schedule runs that (fused_site_cache).
 // A cell, a pointer or a level table out of range is an error (LF_E_INVALID), not a plan that does not apply.
 struct lf_site_plan_t {
     bool applies = false;
-    int64_t nfeed = 0;
-    std::vector<int32_t> slot_of, level_ptr, level_site, site_level;
+    int64_t nfeed = 0, off_level_site = -1;
+    std::vector<int32_t> slot_of, level_ptr, level_site, site_level, site_level_sorted;
 };
 inline int lf_site_plan_build(int64_t n, int64_t nlevels, const int64_t *level_start, int64_t n_lakes, const int32_t *lake_cell,
                               const int32_t *lake_ups_ptr, const int32_t *lake_ups_idx, int64_t n_res, const int32_t *res_cell,
@@ -250,6 +252,7 @@ inline int lf_site_plan_build(int64_t n, int64_t nlevels, const int64_t *level_s
     auto level_of = [&](int64_t pos) { return (int32_t)(std::upper_bound(level_start, level_start + nlevels + 1, pos) - level_start) - 1; };
     P.applies = true;
     P.nfeed = lake_entries + res_entries;
+    P.off_level_site = -1;
     P.slot_of.assign((size_t)n, -1);
     P.site_level.assign((size_t)nsites, 0);
     P.level_ptr.assign((size_t)nlevels + 1, 0);
@@ -268,6 +271,8 @@ inline int lf_site_plan_build(int64_t n, int64_t nlevels, const int64_t *level_s
         std::vector<int32_t> next(P.level_ptr.begin(), P.level_ptr.end() - 1);
         for (int64_t i = 0; i < nsites; ++i) P.level_site[next[P.site_level[i]]++] = (int32_t)i;
     }
+    P.site_level_sorted = P.site_level;
+    std::sort(P.site_level_sorted.begin(), P.site_level_sorted.end());
     auto feeders = [&](int64_t cnt, const int32_t *ptr, const int32_t *idx, int64_t site0, int64_t slot0) {
         for (int64_t i = 0; i < cnt; ++i)
             for (int32_t e = ptr[i]; e < ptr[i + 1]; ++e) {
@@ -276,7 +281,9 @@ inline int lf_site_plan_build(int64_t n, int64_t nlevels, const int64_t *level_s
                     P.applies = false;
                 else
                     P.slot_of[c] = (int32_t)(slot0 + e);
-                if (is_site[c] || level_of(c) != P.site_level[site0 + i]) P.applies = false; // chained sites; not on the site's level
+                const bool off_level = level_of(c) != P.site_level[site0 + i];
+                if (is_site[c] || off_level) P.applies = false; // chained sites; not on the site's level
+                if (off_level && P.off_level_site < 0) P.off_level_site = site0 + i;
             }
     };
     feeders(n_lakes, lake_ups_ptr, lake_ups_idx, 0, 0);

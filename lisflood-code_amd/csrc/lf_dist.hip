@@ -1193,9 +1193,7 @@ namespace {
 int dist_fused_prepare(lf_dist_router *r, const lf_substep_args *a, int nsteps)
 {
     if (!r || !a || nsteps < 1) return lf_set_error(LF_E_INVALID, "bad argument");
-    if (!a->engine_order) return lf_set_error(LF_E_INVALID, "the partitioned sub-steps need engine-order vectors");
-    if (a->split && !r->has_floodplains)
-        return lf_set_error(LF_E_SECTION, "split routing requested but the router has no floodplain alpha");
+    LF_TRY(fused_check_call(*r, *a, 0, "partitioned sub-steps need")); // (the sideflow stride comes with the phases)
     LF_HIP(hipSetDevice(r->device));
     const size_t n = (size_t)std::max<int64_t>(r->N, 1);
     if (!r->fused_qr1.p) LF_TRY(r->fused_qr1.alloc(2 * n));
@@ -1223,7 +1221,7 @@ int dist_fused_phase(lf_dist_router *r, const lf_substep_args *a, int nsteps, in
                      int64_t side_mstride = 0)
 {
     if (phase < 0 || phase >= r->nphases) return lf_set_error(LF_E_INVALID, "phase %d out of range", phase);
-    if (sideflow_stride != 0 && sideflow_stride != r->N) return lf_set_error(LF_E_INVALID, "sideflow_stride must be 0 or N");
+    LF_TRY(fused_check_call(*r, *a, sideflow_stride, "partitioned sub-steps need"));
     if (nsteps != r->slab_steps && nsteps > r->slab_steps) return lf_set_error(LF_E_INVALID, "lf_dist_fused_prepare first");
     const int unit0 = r->phase_level[phase], nunits = r->phase_level[phase + 1] - unit0;
     if (nunits <= 0 || r->N == 0) return LF_OK;

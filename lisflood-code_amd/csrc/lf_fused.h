@@ -1604,6 +1604,16 @@ __global__ void __launch_bounds__(64 * (1 + KC)) k_fused_cones_split(fused_args 
 // lf_sweep.h).
 // ================================================================================================
 
+// What every fused call asks of its arguments, in the caller's own words for itself (`who_needs`: "... wavefront needs")
+inline int fused_check_call(const lf_router_core &r, const lf_substep_args &a, int64_t sideflow_stride, const char *who_needs)
+{
+    if (!a.engine_order) return lf_set_error(LF_E_INVALID, "the %s engine-order vectors", who_needs);
+    if (a.split && !r.has_floodplains)
+        return lf_set_error(LF_E_SECTION, "split routing requested but the router has no floodplain alpha");
+    if (sideflow_stride != 0 && sideflow_stride != r.N) return lf_set_error(LF_E_INVALID, "sideflow_stride must be 0 or N");
+    return LF_OK;
+}
+
 // fused_args of nsteps sub-steps (msteps per model step) from the router's statics; the wave fields are the schedule's,
 // the rest (structures, slabs, recompute flag, ...) stays zero for the caller
 inline fused_args fused_args_of(const lf_router_core &r, const lf_substep_args &a, int nsteps, int msteps, int64_t side_stride,
@@ -1651,12 +1661,41 @@ inline int fused_check_derived(lf_router_core &r, const lf_substep_args &a, hipS
     return LF_OK;
 }
 
+// The flag passes over the statics of a single-domain call of more than one sub-step, each a launch on s counted in
+// `launches`: F.inert (k_inert_flags over the router's isolated cells; never with structures in the loop;
+// LF_NO_INERT_SKIP=1: A/B switch) and F.recompute (fused_check_derived; not for tm_struct, the time-major form with
+// structures: it reads a cell's statics once per model step, so recomputing the five derived ones would save 40 B per cell
+// where the check that allows it reads 72).  flags_ready: an earlier call of the same ensemble call left both with the router.
+inline int fused_statics_flags(lf_router_core &r, fused_args &F, bool structures, bool tm_struct, bool flags_ready, hipStream_t s,
+                               int64_t &launches)
+{
+    if (F.nsteps <= 1) return LF_OK;
+    const char *e = std::getenv("LF_NO_INERT_SKIP");
+    if (!structures && r.n_isolated > 0 && !(e && e[0] == '1')) {
+        if (!r.inert.p) LF_TRY(r.inert.alloc(r.N));
+        if (!flags_ready) {
+            hipLaunchKernelGGL(k_inert_flags, dim3(blocks_for(r.N)), dim3(kBlock), 0, s, (long long)r.N, F.S, r.isolated.p, r.a1.p,
+                               r.a2.p, F.dx, r.inert.p);
+            ++launches;
+        }
+        F.inert = r.inert.p;
+    }
+    if (fused_recompute() && !tm_struct) {
+        if (!flags_ready) {
+            LF_TRY(fused_check_derived(r, F.S, s));
+            ++launches;
+        }
+        F.recompute = r.derived_ok.p;
+    }
+    return LF_OK;
+}
+
 // The wavefront over levels [level0, level0 + nlevels) -- and, if nblocks >= 0, their level blocks [b0, b0 + nblocks) of
 // r.fplan --
 // for F.nsteps sub-steps; fills F's wave fields and adds its launches to `launches`.  Of the three schedules the first that
 // applies runs:
 //   time-major   (time_major: the caller's precondition) one k_fused_level_steps launch per level; with structures in the
-//                loop (tm: the site plan's device tables) also one per level that holds a site, behind the level's own;
+//                loop (tm: their site cache) also one per level that holds a site, behind the level's own;
 //   level blocks (nblocks >= 0, F.nsteps <= kMaxPackedSteps) per wave time t: cones(ncones) launches the multi-level
 //                blocks through a cone kernel on a packed grid of ncones workgroups, levels(grid) the single levels
 //                through k_fused_substeps (F.use_lvl);
@@ -1688,16 +1727,9 @@ inline bool fused_time_major_ready(lf_router_core &r, int level0, int nlevels, i
            lf_history_ensure(r.fused_hist1, r.fused_hist2, r.fused_hist_refused, (size_t)nsteps * (size_t)r.N, split);
 }
 
-struct fused_tm_sites { // the site plan (lf_common.h: lf_site_plan_t) on the device, kept with the router
-    const uint8_t *flags;            // [N] 1: link, 2: site cell (null: no site)
-    const int *slot, *site_ptr, *site; // fused_args::tm_slot / tm_site_ptr / tm_site
-    const std::vector<int32_t> *level_ptr; // host copy of site_ptr (null: no site)
-    int64_t nfeed;
-    lf_dbuf<double> *feed;           // [nsteps + 1][nfeed], grown on demand
-};
 template <bool DIST, class Cones, class Levels, class Sites>
 int fused_wavefront(lf_router_core &r, fused_args &F, int level0, int nlevels, int b0, int nblocks, bool time_major, hipStream_t s,
-                    int64_t &launches, Cones &&cones, Levels &&levels, Sites &&sites, const fused_tm_sites *tm = nullptr)
+                    int64_t &launches, Cones &&cones, Levels &&levels, Sites &&sites, const fused_site_cache *tm = nullptr)
 {
     const int nsteps = F.nsteps;
     const bool split = F.S.split != 0, all35 = r.fused && F.S.Beta == 0.6; // otherwise: run-time flags and OCML pow
@@ -1710,15 +1742,15 @@ int fused_wavefront(lf_router_core &r, fused_args &F, int level0, int nlevels, i
         F.hist2 = r.fused_hist2.p;
         if (tm) {
             const size_t need = (size_t)(nsteps + 1) * (size_t)tm->nfeed;
-            if (tm->feed->n < need) LF_TRY(tm->feed->grow(need));
-            F.tm_feed = tm->feed->p;
+            if (tm->feed.n < need) LF_TRY(tm->feed.grow(need));
+            F.tm_feed = tm->feed.p;
             F.tm_nfeed = (int)tm->nfeed;
-            F.tm_slot = tm->slot;
-            F.tm_site_ptr = tm->site_ptr;
-            F.tm_site = tm->site;
+            F.tm_slot = tm->slot.p;
+            F.tm_site_ptr = tm->site_ptr.p;
+            F.tm_site = tm->site.p;
         }
         const uint8_t *const linked = F.linked;
-        if (tm && tm->flags) F.linked = tm->flags;
+        if (tm && tm->flags.p) F.linked = tm->flags.p;
         for (int k = level0; k < level0 + nlevels; ++k) {
             const int64_t w = width(k);
             if (w <= 0) continue;
@@ -1733,7 +1765,7 @@ int fused_wavefront(lf_router_core &r, fused_args &F, int level0, int nlevels, i
             });
             ++launches;
             if constexpr (!DIST) {
-                const int64_t ns = tm && tm->level_ptr ? (*tm->level_ptr)[k + 1] - (*tm->level_ptr)[k] : 0;
+                const int64_t ns = tm && !tm->level_ptr.empty() ? tm->level_ptr[k + 1] - tm->level_ptr[k] : 0;
                 if (ns > 0) { // the site cells of the level, each with its lake or reservoir
                     pick_flags(split, all35, [&](auto sp, auto a35) {
                         hipLaunchKernelGGL((k_fused_level_steps<sp, a35, false, 2>), dim3(blocks_for(ns)), dim3(kBlock), 0, s, F, k);

@@ -183,20 +183,6 @@ struct lf_router : lf_router_core {
     lf_dbuf<int32_t> parent; // [N] downstream position of every position, -1 = outlet (lf_ldd.hip builds it on demand)
     lf_dbuf<int32_t> root;   // [N] position of the outlet every position drains to (lf_ldd.hip, on demand: catchment totals)
     lf_dbuf<double> totals_scratch; // catchment totals: engine-order copies of the weights and their accuflux
-    lf_dbuf<uint8_t> isolated; // [N] by position: 1 = no upstream and no downstream cell (e.g. non-channel land pixels)
-    lf_dbuf<uint8_t> inert;    // [N] per fused call: isolated, not a channel, zero split-routing thresholds
-    int64_t n_isolated = 0;
-    lf_dbuf<int> site_level; // levels of the lake and reservoir cells of the last fused-with-structures call
-    std::vector<int> site_level_sorted;
-    const void *site_key[4] = {nullptr, nullptr, nullptr, nullptr}; // the site lists those levels were checked for
-    int64_t site_cnt[2] = {-1, -1};
-    // ... and their plan for the time-major form (lf_common.h: lf_site_plan_t), built with those levels
-    bool tm_applies = false;
-    int64_t tm_nfeed = 0;
-    std::vector<int32_t> tm_level_ptr;            // sites per level (host copy of tm_site_ptr)
-    lf_dbuf<uint8_t> tm_flags;                    // [N] 1: link, 2: site cell
-    lf_dbuf<int32_t> tm_slot, tm_site_ptr, tm_site; // fused_args::tm_slot / tm_site_ptr / tm_site
-    lf_dbuf<double> tm_feed;                      // [nsteps + 1][tm_nfeed] ChanQ of the cells feeding a site
     std::vector<level_segment> schedule; // launches of a call without level blocks (level_segments)
     uint64_t graph_serial = 0; // lf_graph::serial of the graph the router was built on: same object <=> same plan
     // (the fused plan of lf_router_core, fplan, is build_level_blocks' and carries lvl2blk for the sites of the structures
@@ -208,6 +194,7 @@ struct lf_router : lf_router_core {
     lf_dbuf<int> wave_start, wave_off_dev;
     std::vector<int> wave_off;
     int64_t last_stats[4] = {0, 0, 0, 0};
+    fused_site_cache sites; // the lake and reservoir lists of the last fused call with structures in the loop
     // profiling
     bool profile = false;
     std::vector<hipEvent_t> ev_pool;
@@ -899,15 +886,12 @@ int lf_router_route_plan_stats(const lf_router *r, int64_t out[6])
     return LF_OK;
 }
 
-// The fused-with-structures call validates the levels of the site lists once per set of device pointers; a caller
-// that rebuilds its site lists (possibly at the same addresses) drops that cache here.
+// The fused-with-structures call checks and plans the site lists once per set of device pointers (fused_site_cache); a
+// caller that rebuilds its site lists (possibly at the same addresses) drops that cache here.
 int lf_router_reset_site_cache(lf_router *r)
 {
     if (!r) return lf_set_error(LF_E_INVALID, "null argument");
-    r->site_cnt[0] = r->site_cnt[1] = -1;
-    for (const void *&k : r->site_key) k = nullptr;
-    r->site_level_sorted.clear();
-    r->tm_applies = false;
+    r->sites.reset();
     return LF_OK;
 }
 
@@ -1231,16 +1215,20 @@ extern "C" int lf_routing_substep(lf_router *r, const lf_substep_args *a)
 
 namespace {
 
-// flags_ready: the statics' flag passes (k_inert_flags, k_check_derived) are not run -- an earlier call of the same ensemble call,
-// with the same static vectors, left them with the router (fused_members_impl)
+void fused_set_stats(lf_router *r, int64_t launches) // what lf_router_last_launches tells of a fused call
+{
+    r->last_stats[0] = r->last_stats[1] = launches;
+    r->last_stats[2] = 0;
+    r->last_stats[3] = r->NL;
+}
+
+// A fused call on the single domain: check, sites, flags, pick the schedule, run.
+// flags_ready: see fused_statics_flags (fused_members_impl)
 int fused_impl(lf_router *r, const lf_substep_args *a, int nsteps, int64_t sideflow_stride, const lf_inloop_args *in,
                int msteps = 0, int64_t side_mstride = 0, bool flags_ready = false)
 {
     if (!r || !a || nsteps < 1) return lf_set_error(LF_E_INVALID, "bad argument");
-    if (!a->engine_order) return lf_set_error(LF_E_INVALID, "the fused sub-step wavefront needs engine-order vectors");
-    if (a->split && !r->has_floodplains)
-        return lf_set_error(LF_E_SECTION, "split routing requested but the router has no floodplain alpha");
-    if (sideflow_stride != 0 && sideflow_stride != r->N) return lf_set_error(LF_E_INVALID, "sideflow_stride must be 0 or N");
+    LF_TRY(fused_check_call(*r, *a, sideflow_stride, "fused sub-step wavefront needs"));
     if (msteps <= 0) msteps = nsteps; // one model step
     if (nsteps % msteps != 0) return lf_set_error(LF_E_INVALID, "the sub-step count must be a multiple of the sub-steps per model step");
     if (msteps != nsteps && (in || sideflow_stride != 0 || (side_mstride != 0 && side_mstride < r->N)))
@@ -1256,8 +1244,7 @@ int fused_impl(lf_router *r, const lf_substep_args *a, int nsteps, int64_t sidef
     F.level_nlinked = r->level_nlinked.p;
     F.fb_lvl2blk = r->fplan_dev.lvl2blk.p;
     hipStream_t s = r->ctx->stream;
-    // ---- structures: levels of the site cells; every cell feeding a site must sit on the site's own level ----------
-    std::vector<int> lv_sorted;
+    // ---- structures: the site lists, checked and planned once per set of lists (r->sites) ---------------------------------
     int64_t nsites = 0;
     if (in) {
         F.I = *in;
@@ -1274,111 +1261,16 @@ int fused_impl(lf_router *r, const lf_substep_args *a, int nsteps, int64_t sidef
             return lf_set_error(LF_E_INVALID, "lf_inloop_args: ToChanM3RunoffDt, SideflowChanM3 and N = num_pixels are needed");
         I.ChanQ = a->ChanQ;
         nsites = I.n_lakes + I.n_res;
-        const void *key[4] = {I.lake_cell, I.lake_ups_idx, I.res_cell, I.res_ups_idx};
-        const bool checked = nsites > 0 && r->site_level.p && r->site_cnt[0] == I.n_lakes && r->site_cnt[1] == I.n_res &&
-                             std::memcmp(key, r->site_key, sizeof(key)) == 0;
-        if (checked) { // same device lists as the last call: levels already validated and resident
-            F.site_level = r->site_level.p;
-            lv_sorted = r->site_level_sorted;
-        } else if (nsites > 0) {
-            auto level_of = [&](int pos) {
-                return (int)(std::upper_bound(r->h_level_start.begin(), r->h_level_start.end(), (int64_t)pos) -
-                             r->h_level_start.begin()) - 1;
-            };
-            std::vector<int> lv(nsites);
-            std::vector<int32_t> h_cell[2], h_ptr[2], h_idx[2]; // host copies of the lists: lakes, reservoirs
-            auto check_sites = [&](int64_t cnt, const int32_t *cell_dev, const int32_t *ptr_dev, const int32_t *idx_dev,
-                                   int64_t off, int li, const char *what) -> int {
-                if (cnt == 0) return LF_OK;
-                if (!cell_dev || !ptr_dev || !idx_dev) return lf_set_error(LF_E_INVALID, "%s site lists missing", what);
-                std::vector<int32_t> &cell = h_cell[li], &ptr = h_ptr[li], &idx = h_idx[li];
-                cell.resize(cnt);
-                ptr.resize(cnt + 1);
-                LF_HIP(hipMemcpy(cell.data(), cell_dev, sizeof(int32_t) * cnt, hipMemcpyDeviceToHost));
-                LF_HIP(hipMemcpy(ptr.data(), ptr_dev, sizeof(int32_t) * (cnt + 1), hipMemcpyDeviceToHost));
-                if (ptr[0] != 0 || ptr[cnt] < 0) return lf_set_error(LF_E_INVALID, "%s_ups_ptr out of range", what);
-                for (int64_t i = 0; i < cnt; ++i)
-                    if (ptr[i + 1] < ptr[i]) return lf_set_error(LF_E_INVALID, "%s_ups_ptr not ascending", what);
-                idx.resize(std::max<int32_t>(ptr[cnt], 1));
-                if (ptr[cnt] > 0)
-                    LF_HIP(hipMemcpy(idx.data(), idx_dev, sizeof(int32_t) * ptr[cnt], hipMemcpyDeviceToHost));
-                for (int64_t i = 0; i < cnt; ++i) {
-                    if (cell[i] < 0 || cell[i] >= n) return lf_set_error(LF_E_INVALID, "%s cell out of range", what);
-                    lv[off + i] = level_of(cell[i]);
-                    for (int32_t e = ptr[i]; e < ptr[i + 1]; ++e)
-                        if (idx[e] < 0 || idx[e] >= n || level_of(idx[e]) != lv[off + i])
-                            return lf_set_error(LF_E_INVALID, "%s %lld: a cell draining into it is not on its level -- build "
-                                                "the router's graph with lf_graph_create_ex(virtual_down)", what, (long long)i);
-                }
-                return LF_OK;
-            };
-            LF_TRY(check_sites(I.n_lakes, I.lake_cell, I.lake_ups_ptr, I.lake_ups_idx, 0, 0, "lake"));
-            LF_TRY(check_sites(I.n_res, I.res_cell, I.res_ups_ptr, I.res_ups_idx, I.n_lakes, 1, "reservoir"));
-            // ---- the plan of the time-major form: feed slots, the sites of every level, whether it applies ----
-            r->tm_applies = false;
-            {
-                lf_site_plan_t P;
-                LF_TRY(lf_site_plan_build(n, r->NL, r->h_level_start.data(), I.n_lakes, h_cell[0].data(), h_ptr[0].data(),
-                                          h_idx[0].data(), I.n_res, h_cell[1].data(), h_ptr[1].data(), h_idx[1].data(), P));
-                std::vector<uint8_t> flags((size_t)n, 0);
-                if (r->linked.p) {
-                    LF_HIP(hipMemcpyAsync(flags.data(), r->linked.p, (size_t)n, hipMemcpyDeviceToHost, s));
-                    LF_HIP(hipStreamSynchronize(s));
-                }
-                for (int64_t p = 0; p < n && P.applies; ++p) // a feeder that is no link of the graph would never be written
-                    if (P.slot_of[p] >= 0 && !flags[p]) P.applies = false;
-                if (P.applies) {
-                    for (int li = 0; li < 2; ++li)
-                        for (int32_t c : h_cell[li]) flags[c] |= 2;
-                    LF_TRY(r->tm_flags.upload(flags.data(), flags.size(), s));
-                    LF_TRY(r->tm_slot.upload(P.slot_of.data(), P.slot_of.size(), s));
-                    LF_TRY(r->tm_site_ptr.upload(P.level_ptr.data(), P.level_ptr.size(), s));
-                    LF_TRY(r->tm_site.upload(P.level_site.data(), P.level_site.size(), s));
-                    r->tm_level_ptr = P.level_ptr;
-                    r->tm_nfeed = P.nfeed;
-                    r->tm_applies = true;
-                }
-            }
-            LF_TRY(r->site_level.upload(lv.data(), (size_t)nsites, r->ctx->stream));
-            F.site_level = r->site_level.p;
-            lv_sorted = lv;
-            std::sort(lv_sorted.begin(), lv_sorted.end());
-            r->site_level_sorted = lv_sorted;
-            std::memcpy(r->site_key, key, sizeof(key));
-            r->site_cnt[0] = I.n_lakes;
-            r->site_cnt[1] = I.n_res;
-        }
+        LF_TRY(r->sites.ensure(n, r->h_level_start, r->linked.p, I, s));
     }
-    int64_t launches = 0;
-    {
-        const char *e = std::getenv("LF_NO_INERT_SKIP"); // A/B switch
-        if (!in && r->n_isolated > 0 && nsteps > 1 && !(e && e[0] == '1')) {
-            if (!r->inert.p) LF_TRY(r->inert.alloc(n));
-            if (!flags_ready) {
-                hipLaunchKernelGGL(k_inert_flags, dim3(blocks_for(n)), dim3(kBlock), 0, s, (long long)n, *a, r->isolated.p,
-                                   r->a1.p, r->a2.p, F.dx, r->inert.p);
-                ++launches;
-            }
-            F.inert = r->inert.p;
-        }
-    }
+    const fused_site_cache no_sites; // (a call with structures and no site: the schedules as with sites, none of them found)
+    const fused_site_cache &sc = nsites > 0 ? r->sites : no_sites;
+    F.site_level = sc.site_level.p;
     // time-major: without structures on a graph without links; with them when the site plan applies (no site: nothing to plan)
-    fused_tm_sites tms = {nullptr, nullptr, nullptr, nullptr, nullptr, 0, &r->tm_feed};
-    bool time_major = !in && !F.linked;
-    if (in && (nsites == 0 || r->tm_applies)) {
-        time_major = true;
-        if (nsites > 0) tms = {r->tm_flags.p, r->tm_slot.p, r->tm_site_ptr.p, r->tm_site.p, &r->tm_level_ptr, r->tm_nfeed, &r->tm_feed};
-    }
-    // (the time-major form reads a cell's statics once per model step: recomputing the five derived ones would save 40 B per
-    // cell where the check that allows it reads 72 -- with structures it streams them as given, one launch less)
+    const bool time_major = in ? nsites == 0 || sc.applies : !F.linked;
+    int64_t launches = 0;
     const bool tm_struct = in && time_major && fused_time_major_ready(*r, 0, (int)r->NL, nsteps, a->split != 0);
-    if (nsteps > 1 && fused_recompute() && !tm_struct) {
-        if (!flags_ready) {
-            LF_TRY(fused_check_derived(*r, *a, s));
-            ++launches;
-        }
-        F.recompute = r->derived_ok.p;
-    }
+    LF_TRY(fused_statics_flags(*r, F, in != nullptr, tm_struct, flags_ready, s, launches));
     const bool all35 = r->fused && a->Beta == 0.6; // otherwise: run-time flags and inlined OCML pow, as fused_cell
     auto cones = [&](int64_t ncones) {
         const dim3 grid((unsigned)ncones);
@@ -1422,9 +1314,9 @@ int fused_impl(lf_router *r, const lf_substep_args *a, int nsteps, int64_t sidef
     // lakes and reservoirs of the blocks / levels [lo, hi]: sub-step t - block / level, before the cells of that block / level
     std::vector<int> site_blocks; // sorted blocks of the lakes and reservoirs
     if (!r->fplan.empty())
-        for (int lv : lv_sorted) site_blocks.push_back(r->fplan.lvl2blk[lv]);
+        for (int lv : sc.site_level_sorted) site_blocks.push_back(r->fplan.lvl2blk[lv]);
     auto sites = [&](bool blocks, int lo, int hi) {
-        const std::vector<int> &units = blocks ? site_blocks : lv_sorted;
+        const std::vector<int> &units = blocks ? site_blocks : sc.site_level_sorted;
         auto it = std::lower_bound(units.begin(), units.end(), lo);
         if (it == units.end() || *it > hi) return;
         if (blocks)
@@ -1434,11 +1326,8 @@ int fused_impl(lf_router *r, const lf_substep_args *a, int nsteps, int64_t sidef
         ++launches;
     };
     const int NB = r->fplan.empty() ? -1 : r->fplan.nblocks();
-    LF_TRY(fused_wavefront<false>(*r, F, 0, (int)r->NL, 0, NB, time_major, s, launches, cones, levels, sites, in ? &tms : nullptr));
-    r->last_stats[0] = launches;
-    r->last_stats[1] = launches;
-    r->last_stats[2] = 0;
-    r->last_stats[3] = r->NL;
+    LF_TRY(fused_wavefront<false>(*r, F, 0, (int)r->NL, 0, NB, time_major, s, launches, cones, levels, sites, in ? &sc : nullptr));
+    fused_set_stats(r, launches);
     return LF_OK;
 }
 
@@ -1542,19 +1431,7 @@ int fused_members_impl(lf_router *r, const lf_substep_args *a, int nsteps, int64
         if (split && !r->fused_qr2.p) LF_TRY(r->fused_qr2.alloc(2 * n));
         fused_args F = fused_args_of(*r, *a, nsteps, nsteps, sideflow_stride, 0);
         hipStream_t s = r->ctx->stream;
-        const char *e = std::getenv("LF_NO_INERT_SKIP");
-        if (r->n_isolated > 0 && !(e && e[0] == '1')) { // statics only: once for all members
-            if (!r->inert.p) LF_TRY(r->inert.alloc(n));
-            hipLaunchKernelGGL(k_inert_flags, dim3(blocks_for(n)), dim3(kBlock), 0, s, (long long)n, *a, r->isolated.p, r->a1.p,
-                               r->a2.p, F.dx, r->inert.p);
-            F.inert = r->inert.p;
-            ++launches;
-        }
-        if (fused_recompute()) {
-            LF_TRY(fused_check_derived(*r, *a, s));
-            F.recompute = r->derived_ok.p;
-            ++launches;
-        }
+        LF_TRY(fused_statics_flags(*r, F, false, false, false, s, launches)); // statics only: once for all members
         F.hist1 = r->fused_hist1.p;
         F.hist2 = r->fused_hist2.p;
         F.nlevels = NL;
@@ -1575,10 +1452,7 @@ int fused_members_impl(lf_router *r, const lf_substep_args *a, int nsteps, int64
         r->last_fused_form = 1;
         LF_HIP(hipGetLastError());
     }
-    r->last_stats[0] = launches;
-    r->last_stats[1] = launches;
-    r->last_stats[2] = 0;
-    r->last_stats[3] = r->NL;
+    fused_set_stats(r, launches);
     return LF_OK;
 }
 
@@ -1598,10 +1472,7 @@ extern "C" int lf_routing_substeps_fused_members(lf_router *r, const lf_substep_
     if (member_stride < r->N)
         return lf_set_error(LF_E_INVALID, "member_stride %lld is less than the router's number of cells (%lld)",
                             (long long)member_stride, (long long)r->N);
-    if (!a->engine_order) return lf_set_error(LF_E_INVALID, "the fused sub-step wavefront needs engine-order vectors");
-    if (a->split && !r->has_floodplains)
-        return lf_set_error(LF_E_SECTION, "split routing requested but the router has no floodplain alpha");
-    if (sideflow_stride != 0 && sideflow_stride != r->N) return lf_set_error(LF_E_INVALID, "sideflow_stride must be 0 or N");
+    LF_TRY(fused_check_call(*r, *a, sideflow_stride, "fused sub-step wavefront needs"));
     const int64_t side_rows = sideflow_stride == 0 ? r->N : (int64_t)nsteps * r->N;
     if (sideflow_member_stride != 0 && sideflow_member_stride < side_rows)
         return lf_set_error(LF_E_INVALID, "sideflow_member_stride %lld is neither 0 nor a whole member's sideflow rows (%lld)",

@@ -1132,6 +1132,9 @@ struct lf_router_core {
     bool has_floodplains = false, dx_per_pixel = false;
     bool fused = false; // beta == 3/5: prep fused into the sweep, polynomial closure solve (lf_math.h)
     lf_dbuf<unsigned int> derived_ok; // fused sub-steps: flags of k_check_derived (fused_args::recompute)
+    lf_dbuf<uint8_t> isolated; // [N] by position: 1 = no upstream and no downstream cell (lf_router; n_isolated of them)
+    lf_dbuf<uint8_t> inert;    // [N] per fused call: isolated, not a channel, zero split-routing thresholds (k_inert_flags)
+    int64_t n_isolated = 0;
     lf_dbuf<int32_t> perm, ups_ptr;
     lf_dbuf<long long> level_start;
     lf_dbuf<double> a1, a2, dx, constant;

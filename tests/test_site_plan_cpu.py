@@ -145,6 +145,17 @@ def test_shared_cell_and_double_feeder_do_not_apply():
     assert rc == 0 and applies == 1 and (slot == -1).all() and (ptr == 0).all()
 
 
+def test_feeder_off_its_level_is_no_error():
+    """levels [0, 4) and [4, 8), one lake on cell 5: a feeder on the other level (cell 2) is a plan that does not apply
+    -- rc 0, not an error: refusing such lists is the fused call's business, not the plan's --, a feeder on the lake's
+    own level (cell 6) one that does"""
+    level_start = np.array([0, 4, 8], np.int64)
+    one, none = np.array([0, 1], np.int32), np.zeros(0, np.int32)
+    for feeder, want in ((2, 0), (6, 1)):
+        rc, applies, *_ = _plan(8, level_start, (np.array([5]), one, np.array([feeder]), none, np.zeros(1, np.int32), none))
+        assert rc == 0 and applies == want, feeder
+
+
 @pytest.mark.parametrize("bad", ["site cell", "negative site cell", "feeder", "pointer"])
 def test_out_of_range_is_refused(bad):
     """a cell or a pointer out of range is an error with a message, not a crash and not a plan"""

@@ -193,3 +193,66 @@ def test_one_sub_step_takes_the_skew(amd, monkeypatch):
     mb.dynamic_fused()
     assert mb.river_router.last_fused_form() in ("level blocks", "levels")
     _same(_snapshot(vb, keys), _snapshot(va, keys), "one sub-step")
+
+
+def _off_level_position(m):
+    """the first position of a non-empty level other than the one that holds the cell of lake 0"""
+    level_start = np.asarray(m.river_router.graph.layout()[2])
+    cell = int(m._st["dev"]["lake_cell"].download()[0])
+    own = int(np.searchsorted(level_start, cell, side="right")) - 1
+    k = next(k for k in range(level_start.size - 1) if k != own and level_start[k + 1] > level_start[k])
+    return int(level_start[k])
+
+
+@pytest.mark.parametrize("bad, message", [("feeder off its level", "not on its level"), ("site cell out of range", "out of range")])
+def test_refused_lists_leave_the_router_usable(amd, monkeypatch, bad, message):
+    """Entry 0 of the device lake_ups_idx set to a position on another level than lake 0's, or lake_cell[0] = N, and the
+    site cache reset: dynamic_fused() refuses the lists with a message.  The list restored under the same pointer, without
+    a reset: the next call takes the time-major form and leaves the bits of 24 x dynamic(s) in every vector of _loop_keys
+    -- the refused call left nothing behind that passes for checked lists."""
+    r, s, cut, mask = _loop_inputs("shallow")
+    switches = E.LOOP_OPTION_SETS["everything"]
+    want = _reference("shallow", "everything")
+    monkeypatch.setenv(SWITCH, "1")
+    vb, mb = _module(r, s, cut, mask, switches)
+    dev = mb._st["dev"]["lake_ups_idx" if bad == "feeder off its level" else "lake_cell"]
+    good = dev.download()
+    wrong = good.copy()
+    wrong[0] = _off_level_position(mb) if bad == "feeder off its level" else mb.river_router.num_pixels
+    assert wrong[0] != good[0]
+    dev.upload(wrong)
+    amd.check(amd.lib().lf_router_reset_site_cache(mb.river_router._h))
+    with pytest.raises(amd.LisfloodAmdError, match=message):
+        mb.dynamic_fused()
+    dev.upload(good)
+    mb.dynamic_fused()
+    assert mb.river_router.last_fused_form() == "time-major"
+    _same(_snapshot(vb, _loop_keys(switches)), want, (bad, "after the refused call"))
+
+
+def test_a_miss_between_two_hits_rebuilds_both_ways(amd, monkeypatch):
+    """A good call, a call whose lake_ups_idx points at a second device array with a feeder off its level (refused), and a
+    call with the pointer back at the first array, no reset in between: the third call takes the time-major form, and the
+    state equals 2 x 24 x dynamic(s) on a second module bit for bit -- the refused call neither advanced nor damaged it."""
+    r, s, cut, mask = _loop_inputs("shallow")
+    switches = E.LOOP_OPTION_SETS["everything"]
+    keys = _loop_keys(switches) + ["CrossSection2Area", "Sideflow1Chan", "LakeStorageM3", "ReservoirStorageM3"]
+    monkeypatch.setenv(SWITCH, "1")
+    (va, ma), (vb, mb) = _module(r, s, cut, mask, switches), _module(r, s, cut, mask, switches)
+    for step in range(2):
+        for sub in range(int(r["NoRoutSteps"])):
+            ma.dynamic(sub)
+    mb.dynamic_fused()
+    assert mb.river_router.last_fused_form() == "time-major"
+    good = mb._inloop.lake_ups_idx
+    wrong = mb._st["dev"]["lake_ups_idx"].download()
+    wrong[0] = _off_level_position(mb)
+    other = amd.DeviceArray.from_host(wrong, mb.device)
+    mb._inloop.lake_ups_idx = other.ptr.value
+    with pytest.raises(amd.LisfloodAmdError, match="not on its level"):
+        mb.dynamic_fused()
+    mb._inloop.lake_ups_idx = good
+    mb.dynamic_fused()
+    assert mb.river_router.last_fused_form() == "time-major"
+    _same(_snapshot(vb, keys), _snapshot(va, keys), "a miss between two hits")
+    other.free()
