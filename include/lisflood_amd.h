@@ -536,6 +536,30 @@ int lf_inloop_structures(int device, const lf_inloop_args *a);
  * It needs the site plan to apply (lf_site_plan: no chained sites, no shared cells) and room for the [nsteps][N]
  * history; otherwise the skewed wavefront runs.  Same bits either way; lf_router_last_fused_form tells which ran. */
 int lf_routing_substeps_fused_structures(lf_router *r, const lf_substep_args *a, const lf_inloop_args *in, int nsteps);
+/* An ensemble through that loop: `members` (>= 1) members on ONE router, with the lakes, reservoirs, inflow hydrographs and
+ * transmission loss of each inside the call.  `a` and `in` are member 0's blocks.  Shared by all members: every static of
+ * `a`, the site lists and site parameters of `in` (lake_cell .. LakeAreaCC, res_cell .. DeltaNFL), UpTrans and the scalars.
+ * Per member, m strides further than member 0's:
+ *   member_stride (>= N): the state and output rows of `a` and the dense [N] rows of `in` (QLakeOutM3Dt, QResOutM3Dt, QInDt,
+ *     QinADDEDM3, TransLossM3Dt, TransCum, SideflowChanM3; in->ChanQ is a->ChanQ);
+ *   lake_member_stride (>= n_lakes) / res_member_stride (>= n_res): the six lake / three reservoir state vectors (ignored
+ *     when the count is 0);
+ *   forcing_member_stride (0: every member reads member 0's, else >= N): ToChanM3RunoffDt, EvaAddM3Dt, WUseAddM3Dt,
+ *     ChannelToPolderM3Dt, QInM3Old, QDelta.
+ * Elements between a row's length and its stride are neither read nor written; a NULL pointer (option off) is NULL for every
+ * member.  members < 1, a negative or too small stride, a forcing stride strictly between 0 and N, null blocks and
+ * nsteps < 1 are refused with LF_E_INVALID and a message naming the argument, before any device is touched; a refused call
+ * advances nothing.  Where the time-major form applies to the ensemble (the site plan applies or there is no site, nsteps > 1,
+ * the width rule of lf_routing_substeps_fused with the lanes counted over the members; LF_FUSED_TIME_MAJOR=0 / 1: never /
+ * whenever possible) the members go slice by slice (lf_fused_members_slice over the history budget, LF_FUSED_MEMBERS_SLICE
+ * caps it): one launch per level for the cells of the whole slice and one more behind it on a level that holds sites, each
+ * member with a [nsteps + 1][feeders] buffer of its own.  Otherwise (chained sites, deep graphs, one sub-step, no room) the
+ * members run one after the other through the single call's schedule, the site checks and flag passes once.  Either way
+ * every member's result is bit-identical to lf_routing_substeps_fused_structures on that member alone; members = 1 IS that
+ * call.  lf_router_last_fused_form / lf_router_last_launches tell what ran (launches summed over slices or members). */
+int lf_routing_substeps_fused_structures_members(lf_router *r, const lf_substep_args *a, const lf_inloop_args *in,
+                                                 int nsteps, int members, int64_t member_stride, int64_t lake_member_stride,
+                                                 int64_t res_member_stride, int64_t forcing_member_stride);
 /* drops the cached validation of the site lists (call after rebuilding lake_cell / lake_ups_idx / res_cell /
  * res_ups_idx, even if the new lists live at the old addresses) */
 int lf_router_reset_site_cache(lf_router *r);

@@ -935,17 +935,33 @@ __global__ void __launch_bounds__(kBlock) LF_TM_ATTR k_fused_level_steps(fused_a
 // spilling, so there is no room to keep the statics of a cell in registers for several members (as k_level_members does).
 // The arithmetic is the same text -- a member's bits are those of its own k_fused_level_steps call.
 // (The strides are arguments behind k, not fields of fused_args: the struct keeps its layout.)
+//
+// STRUCT = 1 / 2 (lf_routing_substeps_fused_structures_members): the cell lanes / the site lanes of the level for every member
+// of the slice, as k_fused_level_steps<.., STRUCT> runs them for one.  Of the in-loop block the member owns
+//   the dense [N] rows (ChanQ, QLakeOutM3Dt, QResOutM3Dt, QInDt, QinADDEDM3, TransLossM3Dt, TransCum, SideflowChanM3), which
+//       move with member_stride like the rows of lf_substep_args;
+//   the site-state rows: six [n_lakes] vectors lake_member_stride apart, three [n_res] vectors res_member_stride apart;
+//   the forcing rows (ToChanM3RunoffDt, EvaAddM3Dt, WUseAddM3Dt, ChannelToPolderM3Dt, QInM3Old, QDelta),
+//       forcing_member_stride apart -- 0: every member reads member 0's;
+//   its own [nsteps + 1][tm_nfeed] feed buffer, one behind the other: what member m's feeders write only member m's sites read.
+// The site lists and parameters, UpTrans and the transmission scalars, the plan tables and every static are shared; a null
+// pointer (an option switched off) stays null, since the body asks the pointer whether the option is on.
 #if LF_TM_WAVES > 0
-#define LF_TM_ATTR_MEMBERS __attribute__((amdgpu_waves_per_eu(LF_TM_WAVES)))
+#define LF_TM_ATTR_MEMBERS __attribute__((amdgpu_waves_per_eu(STRUCT == 2 ? 2 : STRUCT == 1 ? LF_TM_WAVES_STRUCT : LF_TM_WAVES)))
 #else
 #define LF_TM_ATTR_MEMBERS
 #endif
-template <bool SPLIT, bool ALL35>
-__global__ void __launch_bounds__(kBlock) LF_TM_ATTR_MEMBERS k_fused_level_steps_members(fused_args F0, int k, long long member_stride,
-                                                                                        long long side_member_stride)
+template <class T>
+__device__ __forceinline__ void member_row(T *&x, long long off)
+{
+    if (x) x += off;
+}
+template <bool SPLIT, bool ALL35, int STRUCT = 0>
+__global__ void __launch_bounds__(kBlock) LF_TM_ATTR_MEMBERS k_fused_level_steps_members(
+    fused_args F0, int k, long long member_stride, long long side_member_stride, long long lake_member_stride,
+    long long res_member_stride, long long forcing_member_stride)
 {
     constexpr bool DIST = false; // the plain form only
-    constexpr int STRUCT = 0;
     fused_args F = F0;
     {
         const long long m = blockIdx.y, off = m * member_stride, hoff = m * F.nsteps * F.n;
@@ -965,6 +981,37 @@ __global__ void __launch_bounds__(kBlock) LF_TM_ATTR_MEMBERS k_fused_level_steps
         }
         F.hist1 += hoff;
         if (SPLIT) F.hist2 += hoff;
+        if constexpr (STRUCT != 0) {
+            lf_inloop_args &I = F.I;
+            member_row(I.ChanQ, off);
+            member_row(I.QLakeOutM3Dt, off);
+            member_row(I.QResOutM3Dt, off);
+            member_row(I.QInDt, off);
+            member_row(I.QinADDEDM3, off);
+            member_row(I.TransLossM3Dt, off);
+            member_row(I.TransCum, off);
+            member_row(I.SideflowChanM3, off);
+            if (STRUCT == 2) { // (only the site lanes touch the site state)
+                const long long loff = m * lake_member_stride, roff = m * res_member_stride;
+                member_row(I.LakeStorageM3CC, loff);
+                member_row(I.LakeInflowOldCC, loff);
+                member_row(I.LakeOutflowCC, loff);
+                member_row(I.LakeStorageM3BalanceCC, loff);
+                member_row(I.LakeLevelCC, loff);
+                member_row(I.LakeInflowCC, loff);
+                member_row(I.ReservoirStorageM3CC, roff);
+                member_row(I.ReservoirFillCC, roff);
+                member_row(I.ReservoirInflowCC, roff);
+            }
+            const long long foff = m * forcing_member_stride;
+            member_row(I.ToChanM3RunoffDt, foff);
+            member_row(I.EvaAddM3Dt, foff);
+            member_row(I.WUseAddM3Dt, foff);
+            member_row(I.ChannelToPolderM3Dt, foff);
+            member_row(I.QInM3Old, foff);
+            member_row(I.QDelta, foff);
+            member_row(F.tm_feed, m * (F.nsteps + 1) * F.tm_nfeed);
+        }
     }
 #include "lf_fused_level_steps.inc"
 }

@@ -1444,7 +1444,7 @@ int fused_members_impl(lf_router *r, const lf_substep_args *a, int nsteps, int64
                 if (w <= 0) continue;
                 pick_flags(split, all35, [&](auto sp, auto a35) {
                     hipLaunchKernelGGL((k_fused_level_steps_members<sp, a35>), dim3(blocks_for(w), (unsigned)cnt), dim3(kBlock), 0, s,
-                                       F, k, (long long)member_stride, (long long)side_member_stride);
+                                       F, k, (long long)member_stride, (long long)side_member_stride, 0ll, 0ll, 0ll);
                 });
                 ++launches;
             }
@@ -1456,7 +1456,176 @@ int fused_members_impl(lf_router *r, const lf_substep_args *a, int nsteps, int64
     return LF_OK;
 }
 
+// `in` with every per-member row moved m members on: the dense [N] rows by member_stride, the site-state rows by the site
+// strides, the forcing rows by forcing_stride (0: member 0's for all); site lists, site parameters, UpTrans and the scalars
+// are shared, and a null pointer (an option switched off) stays null -- as k_fused_level_steps_members<.., STRUCT> moves them
+lf_inloop_args member_inloop(const lf_inloop_args &in, int64_t m, int64_t member_stride, int64_t lake_stride, int64_t res_stride,
+                             int64_t forcing_stride)
+{
+    lf_inloop_args b = in;
+    auto move = [m](auto *&x, int64_t stride) {
+        if (x) x += m * stride;
+    };
+    for (auto x : {&b.QLakeOutM3Dt, &b.QResOutM3Dt, &b.QInDt, &b.QinADDEDM3, &b.TransLossM3Dt, &b.TransCum, &b.SideflowChanM3})
+        move(*x, member_stride);
+    move(b.ChanQ, member_stride);
+    for (auto x : {&b.LakeStorageM3CC, &b.LakeInflowOldCC, &b.LakeOutflowCC, &b.LakeStorageM3BalanceCC, &b.LakeLevelCC, &b.LakeInflowCC})
+        move(*x, lake_stride);
+    for (auto x : {&b.ReservoirStorageM3CC, &b.ReservoirFillCC, &b.ReservoirInflowCC}) move(*x, res_stride);
+    for (auto x : {&b.ToChanM3RunoffDt, &b.EvaAddM3Dt, &b.WUseAddM3Dt, &b.ChannelToPolderM3Dt, &b.QInM3Old, &b.QDelta})
+        move(*x, forcing_stride);
+    return b;
+}
+
+// The ensemble call with lakes, reservoirs, inflow hydrographs and transmission loss in the loop
+// (lf_routing_substeps_fused_structures_members; its arguments are checked there).  The site lists are shared by the
+// members: checked and planned once per call.  Where the time-major form applies to the ensemble -- the site plan applies (or
+// there is no site), more than one sub-step, the width rule over members * N lanes, room for a slice's history and feed
+// buffers -- the members of a slice are the second grid dimension of k_fused_level_steps_members<.., 1> (one launch per
+// level) and <.., 2> (one more behind it on a level that holds sites).  Otherwise member after member through fused_impl.
+int fused_structures_members_impl(lf_router *r, const lf_substep_args *a, const lf_inloop_args *in, int nsteps, int members,
+                                  int64_t member_stride, int64_t lake_stride, int64_t res_stride, int64_t forcing_stride)
+{
+    LF_HIP(hipSetDevice(r->device));
+    const int64_t n = r->N;
+    const int NL = (int)r->NL;
+    const bool split = a->split != 0;
+    hipStream_t s = r->ctx->stream;
+    lf_inloop_args I = *in; // member 0's block as fused_impl reads it
+    if (I.n_lakes <= 0) {
+        I.n_lakes = 0;
+        I.QLakeOutM3Dt = nullptr;
+    }
+    if (I.n_res <= 0) {
+        I.n_res = 0;
+        I.QResOutM3Dt = nullptr;
+    }
+    if (!I.ToChanM3RunoffDt || !I.SideflowChanM3 || I.N != n)
+        return lf_set_error(LF_E_INVALID, "lf_inloop_args: ToChanM3RunoffDt, SideflowChanM3 and N = num_pixels are needed");
+    I.ChanQ = a->ChanQ;
+    const int64_t nsites = I.n_lakes + I.n_res;
+    LF_TRY(r->sites.ensure(n, r->h_level_start, r->linked.p, I, s)); // shared lists: once for all members
+    const fused_site_cache no_sites;
+    const fused_site_cache &sc = nsites > 0 ? r->sites : no_sites;
+    // ---- does the member form apply, and on slices of how many members? (as fused_members_impl) ------------------------------
+    int64_t slice = 0;
+    size_t budget = 0;
+    if ((nsites == 0 || sc.applies) && nsteps > 1 && fused_time_major_wanted(NL, (int64_t)members * n) &&
+        lf_history_budget(r->fused_hist1, r->fused_hist2, budget)) {
+        const char *c = std::getenv("LF_FUSED_MEMBERS_SLICE"); // A/B switch, read per call
+        slice = lf_fused_members_slice(members, n, nsteps, split, (int64_t)std::min<size_t>(budget, INT64_MAX), c ? std::atoi(c) : 0);
+        // (a history or a feed buffer that does not come is not remembered in r->fused_hist_refused, which belongs to the
+        // single call's own, smaller, request: the members then run one after the other, each with that request)
+        size_t refused = SIZE_MAX;
+        if (slice > 0 && !lf_history_ensure(r->fused_hist1, r->fused_hist2, refused, (size_t)slice * nsteps * (size_t)n, split))
+            slice = 0;
+        const size_t feed = (size_t)slice * (size_t)(nsteps + 1) * (size_t)sc.nfeed;
+        if (slice > 0 && sc.feed.n < feed && sc.feed.grow(feed) != LF_OK) slice = 0;
+    }
+    int64_t launches = 0;
+    if (slice == 0) {
+        // Member after member through the single call's schedule.  What runs once: the site checks and the plan (above; every
+        // member's call finds the cache by the shared list pointers) and the flag pass over the statics (fused_check_derived
+        // reads the static vectors and the router's tables only: flags_ready from the second member on).  No pass of the call
+        // reads member state -- the inert flags, the one candidate, are never taken with structures in the loop --, so nothing
+        // is repeated per member but the wavefront itself.
+        for (int m = 0; m < members; ++m) {
+            const lf_substep_args b = member_args(*a, m, member_stride, 0);
+            const lf_inloop_args bi = member_inloop(*in, m, member_stride, lake_stride, res_stride, forcing_stride);
+            LF_TRY(fused_impl(r, &b, nsteps, 0, &bi, 0, 0, m > 0));
+            launches += r->last_stats[0];
+        }
+        fused_set_stats(r, launches);
+        return LF_OK;
+    }
+    if (!r->fused_qr1.p) LF_TRY(r->fused_qr1.alloc(2 * n)); // (as fused_impl leaves a router: other forms find them)
+    if (split && !r->fused_qr2.p) LF_TRY(r->fused_qr2.alloc(2 * n));
+    fused_args F = fused_args_of(*r, *a, nsteps, nsteps, 0, 0);
+    F.level_nlinked = r->level_nlinked.p;
+    F.fb_lvl2blk = r->fplan_dev.lvl2blk.p;
+    F.site_level = sc.site_level.p;
+    F.I = I;
+    LF_TRY(fused_statics_flags(*r, F, true, true, false, s, launches)); // (time-major with structures: neither flag is taken)
+    F.hist1 = r->fused_hist1.p;
+    F.hist2 = r->fused_hist2.p;
+    F.nlevels = NL;
+    F.tm_feed = sc.feed.p;
+    F.tm_nfeed = (int)sc.nfeed;
+    F.tm_slot = sc.slot.p;
+    F.tm_site_ptr = sc.site_ptr.p;
+    F.tm_site = sc.site.p;
+    F.linked = sc.flags.p ? sc.flags.p : r->linked.p; // 1: link, 2: site cell
+    const bool all35 = r->fused && a->Beta == 0.6;
+    for (int64_t m0 = 0; m0 < members; m0 += slice) {
+        const unsigned cnt = (unsigned)std::min<int64_t>(slice, members - m0);
+        F.S = member_args(*a, m0, member_stride, 0);
+        F.I = member_inloop(I, m0, member_stride, lake_stride, res_stride, forcing_stride);
+        for (int k = 0; k < NL; ++k) {
+            const int64_t w = r->h_level_start[k + 1] - r->h_level_start[k];
+            if (w <= 0) continue;
+            pick_flags(split, all35, [&](auto sp, auto a35) {
+                hipLaunchKernelGGL((k_fused_level_steps_members<sp, a35, 1>), dim3(blocks_for(w), cnt), dim3(kBlock), 0, s, F, k,
+                                   (long long)member_stride, 0ll, (long long)lake_stride, (long long)res_stride,
+                                   (long long)forcing_stride);
+            });
+            ++launches;
+            const int64_t ns = sc.level_ptr.empty() ? 0 : sc.level_ptr[k + 1] - sc.level_ptr[k];
+            if (ns > 0) { // the site cells of the level, each with its lake or reservoir, member by member on the grid
+                pick_flags(split, all35, [&](auto sp, auto a35) {
+                    hipLaunchKernelGGL((k_fused_level_steps_members<sp, a35, 2>), dim3(blocks_for(ns), cnt), dim3(kBlock), 0, s, F, k,
+                                       (long long)member_stride, 0ll, (long long)lake_stride, (long long)res_stride,
+                                       (long long)forcing_stride);
+                });
+                ++launches;
+            }
+        }
+    }
+    r->last_fused_form = 1;
+    LF_HIP(hipGetLastError());
+    fused_set_stats(r, launches);
+    return LF_OK;
+}
+
 } // namespace
+
+extern "C" int lf_routing_substeps_fused_structures_members(lf_router *r, const lf_substep_args *a, const lf_inloop_args *in,
+                                                            int nsteps, int members, int64_t member_stride,
+                                                            int64_t lake_member_stride, int64_t res_member_stride,
+                                                            int64_t forcing_member_stride)
+{
+    // ---- what needs no router, and so no device ----
+    if (members < 1) return lf_set_error(LF_E_INVALID, "members must be at least 1 (got %d)", members);
+    if (member_stride < 0)
+        return lf_set_error(LF_E_INVALID, "member_stride %lld is less than the router's number of cells", (long long)member_stride);
+    if (lake_member_stride < 0)
+        return lf_set_error(LF_E_INVALID, "lake_member_stride %lld is less than the number of lakes", (long long)lake_member_stride);
+    if (res_member_stride < 0)
+        return lf_set_error(LF_E_INVALID, "res_member_stride %lld is less than the number of reservoirs",
+                            (long long)res_member_stride);
+    if (forcing_member_stride < 0)
+        return lf_set_error(LF_E_INVALID, "forcing_member_stride %lld is neither 0 nor at least the router's number of cells",
+                            (long long)forcing_member_stride);
+    if (!r || !a || !in) return lf_set_error(LF_E_INVALID, "null argument");
+    if (nsteps < 1) return lf_set_error(LF_E_INVALID, "nsteps must be at least 1 (got %d)", nsteps);
+    // ---- against the router's and the lists' sizes: host fields, still no device ----
+    if (member_stride < r->N)
+        return lf_set_error(LF_E_INVALID, "member_stride %lld is less than the router's number of cells (%lld)",
+                            (long long)member_stride, (long long)r->N);
+    if (in->n_lakes > 0 && lake_member_stride < in->n_lakes)
+        return lf_set_error(LF_E_INVALID, "lake_member_stride %lld is less than the number of lakes (%lld)",
+                            (long long)lake_member_stride, (long long)in->n_lakes);
+    if (in->n_res > 0 && res_member_stride < in->n_res)
+        return lf_set_error(LF_E_INVALID, "res_member_stride %lld is less than the number of reservoirs (%lld)",
+                            (long long)res_member_stride, (long long)in->n_res);
+    if (forcing_member_stride != 0 && forcing_member_stride < r->N)
+        return lf_set_error(LF_E_INVALID, "forcing_member_stride %lld is neither 0 nor at least the router's number of cells (%lld)",
+                            (long long)forcing_member_stride, (long long)r->N);
+    LF_TRY(fused_check_call(*r, *a, 0, "fused sub-step wavefront needs"));
+    if (members == 1) return fused_impl(r, a, nsteps, 0, in);
+    if (r->N == 0) return LF_OK;
+    return fused_structures_members_impl(r, a, in, nsteps, members, member_stride, lake_member_stride, res_member_stride,
+                                         forcing_member_stride);
+}
 
 extern "C" int lf_routing_substeps_fused_members(lf_router *r, const lf_substep_args *a, int nsteps, int64_t sideflow_stride,
                                                  int members, int64_t member_stride, int64_t sideflow_member_stride)

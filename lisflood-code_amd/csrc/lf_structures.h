@@ -97,7 +97,9 @@ struct fused_site_cache {
     lf_dbuf<int> site_level;                // fused_args::site_level
     lf_dbuf<uint8_t> flags;                 // [N] 1: link, 2: site cell -- fused_args::linked of the time-major form
     lf_dbuf<int32_t> slot, site_ptr, site;  // fused_args::tm_slot / tm_site_ptr / tm_site
-    mutable lf_dbuf<double> feed; // [nsteps + 1][nfeed] ChanQ of the cells feeding a site: working storage, grown on demand
+    // [nsteps + 1][nfeed] ChanQ of the cells feeding a site ([slice] of them, one per member, in an ensemble call): working
+    // storage, grown on demand
+    mutable lf_dbuf<double> feed;
 
     bool matches(const lf_inloop_args &I) const
     {

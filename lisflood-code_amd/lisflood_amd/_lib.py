@@ -74,6 +74,7 @@ _SIGNATURES = {
     "pppi": "router_route_host router_route_device router_route_ordered routing_substeps_fused_structures",
     "pppii": "dist_routing_substep dist_router_compute_phase router_route_members_host",
     "pppiii": "dist_router_compute_part dist_router_exchange",
+    "pppiiqqqq": "routing_substeps_fused_structures_members",
     "pppiiqii": "dist_routing_model_steps_fused",
     "pppiqi": "router_route_ordered_members",
     "pppiqii": "dist_routing_substeps_fused",

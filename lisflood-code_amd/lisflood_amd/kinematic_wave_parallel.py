@@ -258,6 +258,27 @@ class kinematicWave:
         check(lib().lf_routing_substeps_fused_members(self._h, C.byref(args), nsteps, int(sideflow_stride), members,
                                                       member_stride, int(sideflow_member_stride)))
 
+    def routing_substeps_structures_members(self, args, inloop, nsteps, members, member_stride=None, lake_member_stride=None,
+                                            res_member_stride=None, forcing_member_stride=0):
+        """nsteps routing sub-steps of `members` members with lakes, reservoirs, inflow hydrographs and transmission loss in
+        the loop, in one call (lf_routing_substeps_fused_structures_members): `args` / `inloop` are member 0's lf_substep_args /
+        lf_inloop_args blocks in engine order.  Member m's state, output and dense in-loop rows sit m * member_stride elements
+        further (default N), its lake / reservoir state m * lake_member_stride / res_member_stride (default: the counts of
+        `inloop`), its forcing rows m * forcing_member_stride (default 0: every member reads member 0's); site lists, site
+        parameters and statics are shared.  Every member ends up as lf_routing_substeps_fused_structures on it alone would
+        leave it; asynchronous.  (Strides the router cannot take are the library's to refuse, with its own message.)"""
+        nsteps, members = int(nsteps), int(members)
+        if members < 1:
+            raise ValueError("members must be at least 1 (got %d)" % members)
+        if nsteps < 1:
+            raise ValueError("nsteps must be at least 1 (got %d)" % nsteps)
+        member_stride = self.num_pixels if member_stride is None else int(member_stride)
+        lake_member_stride = max(int(inloop.n_lakes), 0) if lake_member_stride is None else int(lake_member_stride)
+        res_member_stride = max(int(inloop.n_res), 0) if res_member_stride is None else int(res_member_stride)
+        check(lib().lf_routing_substeps_fused_structures_members(self._h, C.byref(args), C.byref(inloop), nsteps, members,
+                                                                 member_stride, lake_member_stride, res_member_stride,
+                                                                 int(forcing_member_stride)))
+
     def to_engine_order_members(self, src_pix_dev, members, dst_ord_dev=None):
         """[members, N] pixel order -> engine order, row by row (not on the hot path)"""
         N = self.num_pixels

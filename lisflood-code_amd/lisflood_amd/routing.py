@@ -129,6 +129,8 @@ _RES_PARAM = ("TotalReservoirStorageM3CC MinReservoirOutflowCC NormalReservoirOu
               "ConservativeStorageLimitCC NormalStorageLimitCC FloodStorageLimitCC Normal_FloodStorageLimitCC DeltaO "
               "DeltaLN DeltaNFL").split()
 _RES_STATE = "ReservoirStorageM3CC ReservoirFillCC ReservoirInflowCC".split()
+# the [N] vectors of lf_inloop_args that the loop writes (an ensemble keeps a row of each per member)
+_INLOOP_DENSE = "QLakeOutM3Dt QResOutM3Dt QInDt QinADDEDM3 TransLossM3Dt TransCum SideflowChanM3".split()
 
 
 class routing(HydroModule):
@@ -701,6 +703,18 @@ class routing(HydroModule):
         if self.options.get("repMBTs"):
             self.mbts_after_fused()
 
+    def ensemble(self, members, member_stride=None):
+        """A routingEnsemble of `members` members on this module's router (after attach_router and, optionally,
+        attach_structures): it shares the router, the device statics and -- with structures attached -- the site lists and
+        site parameters of the module, and keeps member rows of its own for every state, output, site-state and dense
+        in-loop vector.  Every member starts from the module's current state (`var`, and the site state of the device)."""
+        if self.river_router is None:
+            raise RuntimeError("routing.initialSecond()/attach_router() must be called first")
+        if not self.engine_order or self._nfull != self.river_router.num_pixels:
+            raise RuntimeError("an ensemble needs routing(..., engine_order=True) on the whole domain (compact=False)")
+        self._ensure_device()
+        return routingEnsemble(self.var, self.river_router, members, self._split(), member_stride, self.device, module=self)
+
     def mbts_after_fused(self):
         """The mass-balance bookkeeping of a whole model step after a fused call (state already on `var`): AddedTRUN of
         all sub-steps at once, then the last-sub-step block.  Equal to the sub-step-by-sub-step sums to rounding."""
@@ -770,9 +784,14 @@ class routingEnsemble:
     alpha_floodplains for split routing).  State and output rows are [members][member_stride] in engine order
     (member_stride >= N, default N); set_state / state permute at the boundary.  Every member ends up as its own
     routing.dynamic_fused call would leave it, bit for bit; where the library's time-major form applies
-    (last_fused_form() == "time-major") the whole ensemble costs the launches of one member per slice of members."""
+    (last_fused_form() == "time-major") the whole ensemble costs the launches of one member per slice of members.
 
-    def __init__(self, var, router, members, split_routing=False, member_stride=None, device=0):
+    With lakes, reservoirs, inflow hydrographs or transmission loss in the loop the ensemble comes from a routing module
+    (routing.ensemble(members), after attach_structures): it then shares the module's router, device statics, site lists and
+    site parameters, holds member rows of the dense in-loop vectors ([members, N]) and of the lake / reservoir state
+    ([members, n_lakes] / [members, n_res]) beside the routing state, and runs lf_routing_substeps_fused_structures_members."""
+
+    def __init__(self, var, router, members, split_routing=False, member_stride=None, device=0, module=None):
         members = int(members)
         if members < 1:
             raise ValueError("members must be at least 1 (got %d)" % members)
@@ -782,40 +801,145 @@ class routingEnsemble:
         if self.stride < N:
             raise ValueError("member_stride %d is less than the router's %d cells" % (self.stride, N))
         self.nsteps = int(var.NoRoutSteps)
-        self.perm = router.graph.layout()[0].astype(np.int64)                          # position -> pixel
         rows = (members - 1) * self.stride + N                                          # entries of a vector of member rows
-        host = substep_host_vectors(var, N, self.perm, _STATIC)
-        self.vectors = SubstepVectors(host, N, var.Beta, var.InvDtRouting, var.DtSec, self.split, True, device,
-                                      lengths={k: rows for k in _STATE + _OUT})
-        self._side = None
+        self._side = self._inloop = None
+        self._inloop_dev, self._forcing = {}, None
+        self._module = module                     # (the owner of the shared device vectors lives as long as the ensemble)
+        if module is None:
+            self.perm = router.graph.layout()[0].astype(np.int64)                      # position -> pixel
+            host = substep_host_vectors(var, N, self.perm, _STATIC)
+            self.vectors = SubstepVectors(host, N, var.Beta, var.InvDtRouting, var.DtSec, self.split, True, device,
+                                          lengths={k: rows for k in _STATE + _OUT})
+        else:                                     # the module's statics, shared: only the member rows are allocated here
+            self.perm = module._perm
+            self.vectors = SubstepVectors({}, N, var.Beta, var.InvDtRouting, var.DtSec, self.split, True, device,
+                                          order=_STATE + _OUT + ["scratch0", "scratch1"], lengths={k: rows for k in _STATE + _OUT})
+            for k in _STATIC:
+                setattr(self.vectors.args, k, getattr(module._args, k))
         start = substep_host_vectors(var, N, None, _STATE)
         for k in _STATE:
             self.set_state(k, np.broadcast_to(start[k], (members, N)))
+        if module is not None and getattr(module, "_inloop", None) is not None:
+            self._attach_inloop(module)
+
+    def _attach_inloop(self, module):
+        """member rows of the module's in-loop block; lists, parameters, UpTrans and scalars stay the module's"""
+        M, N, st = self.members, self.N, module._st
+        a = self._inloop = _InloopArgs.from_buffer_copy(module._inloop)
+        self._options = module.options
+        self.n_lakes, self.n_res = int(st["lakes"]), int(st["res"])
+        self._groups = {}                        # name -> (entries of a row, stride, pixel order?)
+        for k in _INLOOP_DENSE:
+            if k == "SideflowChanM3" or k in st["dev"]:
+                self._groups[k] = (N, self.stride, True)
+        for names, count in ((_LAKE_STATE, self.n_lakes), (_RES_STATE, self.n_res)):
+            for k in names if count else ():
+                self._groups[k] = (count, count, False)
+        v = self.var
+        for k, (count, stride, _) in self._groups.items():
+            d = self._inloop_dev[k] = DeviceArray(max((M - 1) * stride + count, 1), np.float64, self.device).zero()
+            setattr(a, k, d.ptr.value)
+            if k == "LakeStorageM3CC":            # as the module's model step starts: from the dense state maps
+                start = f64(np.asarray(v.LakeStorageM3)[np.asarray(v.LakeIndex)])
+            elif k == "ReservoirStorageM3CC":
+                start = f64(np.asarray(v.ReservoirStorageM3)[np.asarray(v.ReservoirIndex)])
+            else:
+                start = (module._dev if k == "SideflowChanM3" else st["dev"])[k].download()[:count]
+            self._put_rows(k, np.broadcast_to(start, (M, count)), permute=False)
+        a.ChanQ = self.vectors.args.ChanQ
+        self.vectors.args.SideflowChanM3 = a.SideflowChanM3
+
+    def _put_rows(self, name, host, permute=True):
+        count, stride, pixels = self._groups[name]
+        rows = np.zeros((self.members, stride))
+        rows[:, :count] = host[:, self.perm] if pixels and permute else host
+        self._inloop_dev[name].upload(np.ascontiguousarray(rows.reshape(-1)[:(self.members - 1) * stride + count]), prefix=True)
 
     def _member_rows(self, name, host):
-        """host [members, N] float64 in pixel order, or ValueError"""
-        if name not in _STATE + _OUT:
+        """host [members, N] float64 in pixel order ([members, n_lakes] / [members, n_res] for site state), or ValueError"""
+        groups = getattr(self, "_groups", None) or {}
+        if name not in _STATE + _OUT and name not in groups:
             raise ValueError("no state or output vector of the routing sub-step is called %r" % (name,))
-        if not (isinstance(host, np.ndarray) and host.dtype == np.float64 and host.shape == (self.members, self.N)):
-            raise ValueError("%s must be a float64 [%d, %d] array (members, pixels)" % (name, self.members, self.N))
+        width = groups[name][0] if name in groups else self.N
+        if not (isinstance(host, np.ndarray) and host.dtype == np.float64 and host.shape == (self.members, width)):
+            raise ValueError("%s must be a float64 [%d, %d] array (members, %s)" %
+                             (name, self.members, width, "pixels" if width == self.N else "sites"))
         return host
 
     def set_state(self, name, host):
-        """member rows of a state vector from host[members, N] in pixel order (the padding between rows becomes 0)"""
+        """member rows of a state vector from host[members, N] in pixel order (the padding between rows becomes 0); with
+        structures attached also the dense in-loop vectors ([members, N]) and the lake / reservoir state
+        ([members, n_lakes] / [members, n_res], in the order of LakeIndex / ReservoirIndex)"""
         host = self._member_rows(name, host)
+        if name in (getattr(self, "_groups", None) or {}):
+            return self._put_rows(name, host)
         rows = np.zeros((self.members, self.stride))
         rows[:, :self.N] = host[:, self.perm]
         self.vectors.upload(name, rows.reshape(-1)[:(self.members - 1) * self.stride + self.N])
 
     def state(self, name):
-        """host[members, N] in pixel order of a state or output vector"""
-        if name not in _STATE + _OUT:
+        """host[members, N] in pixel order of a state or output vector (site state: [members, sites])"""
+        groups = getattr(self, "_groups", None) or {}
+        if name not in _STATE + _OUT and name not in groups:
             raise ValueError("no state or output vector of the routing sub-step is called %r" % (name,))
-        flat = np.zeros(self.members * self.stride)
-        flat[:(self.members - 1) * self.stride + self.N] = self.vectors.download(name)
+        count, stride, pixels = groups.get(name, (self.N, self.stride, True))
+        flat = np.zeros(self.members * stride)
+        flat[:(self.members - 1) * stride + count] = \
+            (self._inloop_dev[name] if name in groups else self.vectors.dev[name]).download()[:(self.members - 1) * stride + count]
+        rows = flat.reshape(self.members, stride)[:, :count]
+        if not pixels:
+            return rows.copy()
         out = np.empty((self.members, self.N))
-        out[:, self.perm] = flat.reshape(self.members, self.stride)[:, :self.N]
+        out[:, self.perm] = rows
         return out
+
+    def _forcing_rows(self, forcing):
+        """-> (name -> host [N] or [members, N] in pixel order, common stride) for the forcing dict of a call with structures"""
+        M, N, o, v = self.members, self.N, self._options, self.var
+        if not isinstance(forcing, dict):
+            raise ValueError("with structures attached dynamic_fused takes a dict of forcing vectors (ToChanM3RunoffDt, ...)")
+        on = {"ToChanM3RunoffDt": True, "EvaAddM3Dt": bool(o.get("openwaterevapo")), "WUseAddM3Dt": bool(o.get("wateruse")),
+              "ChannelToPolderM3Dt": bool(o.get("simulatePolders")), "QInM3Old": bool(o.get("inflow")), "QDelta": bool(o.get("inflow"))}
+        for k in forcing:
+            if k not in on:
+                raise ValueError("no forcing vector of the routing loop is called %r" % (k,))
+            if not on[k]:
+                raise ValueError("%s belongs to an option that is switched off" % k)
+        if "ToChanM3RunoffDt" not in forcing:
+            raise ValueError("the forcing needs ToChanM3RunoffDt")
+        out = {}
+        for k in on:
+            if not on[k]:
+                continue
+            if k in forcing:
+                x = forcing[k]
+                if not (isinstance(x, np.ndarray) and x.dtype == np.float64 and x.shape in ((N,), (M, N))):
+                    raise ValueError("%s must be a float64 array shaped [%d] or [%d, %d] (pixels; members, pixels)" % (k, N, M, N))
+            elif k == "WUseAddM3Dt":             # a term left out: from `var`, as the module reads it (routing.py:466-467)
+                x = f64(np.broadcast_to(v.withdrawal_CH_actual_M3_routStep - v.returnflow_GwAbs2Channel_M3_routStep, (N,)))
+            else:
+                x = f64(np.broadcast_to(np.asarray(getattr(v, k), np.float64), (N,)))
+            out[k] = x
+        stride = N if any(x.ndim == 2 for x in out.values()) else 0
+        return out, stride
+
+    def _fused_with_structures(self, forcing):
+        host, fstride = self._forcing_rows(forcing)
+        M, N, a = self.members, self.N, self._inloop
+        rows = M if fstride else 1
+        names = list(host)
+        if self._forcing is None or self._forcing.shape != (len(names), rows, N):
+            if self._forcing is not None:
+                self._forcing.free()
+            self._forcing = DeviceArray((len(names), rows, N), np.float64, self.device)
+        block = np.empty((len(names), rows, N))
+        for i, k in enumerate(names):            # mixed shapes: broadcast to the common stride
+            block[i] = np.broadcast_to(host[k], (rows, N))[:, self.perm]
+            setattr(a, k, self._forcing.ptr.value + 8 * i * rows * N)
+        self._forcing.upload(block)
+        self.vectors.dev["sumDisDay"].zero()
+        self.router.routing_substeps_structures_members(self.vectors.args, a, self.nsteps, M, self.stride,
+                                                        self.n_lakes, self.n_res, fstride)
 
     def _sideflow_rows(self, sideflows):
         """-> (host array as given, sideflow_stride, sideflow_member_stride) for [N], [M, N] or [M, NoRoutSteps, N]"""
@@ -829,7 +953,14 @@ class routingEnsemble:
     def dynamic_fused(self, sideflows):
         """One model step (NoRoutSteps sub-steps) of every member in one call.  `sideflows` (pixel order): [N] -- one vector for
         all members and sub-steps --, [members, N] or [members, NoRoutSteps, N].  sumDisDay is zeroed first, as the model does
-        at the start of a model step (Lisflood_dynamic.py:177)."""
+        at the start of a model step (Lisflood_dynamic.py:177).
+        With structures attached (routing.ensemble after attach_structures) the argument is the forcing of the model step
+        instead, a dict of float64 vectors in pixel order, each [N] or [members, N] (mixed shapes are broadcast to one common
+        stride): ToChanM3RunoffDt, and -- for the options that are on -- EvaAddM3Dt, WUseAddM3Dt, ChannelToPolderM3Dt,
+        QInM3Old, QDelta (one left out is read from `var`, as the module does).  Lake and reservoir state carry over from
+        model step to model step in the member rows."""
+        if getattr(self, "_inloop", None) is not None:
+            return self._fused_with_structures(sideflows)
         x, side_stride, side_member_stride = self._sideflow_rows(sideflows)
         x = f64(x[..., self.perm])
         if self._side is None or self._side.nbytes != x.nbytes:
@@ -850,6 +981,9 @@ class routingEnsemble:
         if self._side is not None:
             self._side.free()
             self._side = None
+        for d in list(self._inloop_dev.values()) + ([] if self._forcing is None else [self._forcing]):
+            d.free()
+        self._inloop_dev, self._forcing = {}, None
 
 
 def var_from_fixture(g):
