@@ -436,6 +436,37 @@ int lf_canopy_device(int device, const lf_canopy_args *a);
  * otherwise (use the separate entry points then).  soil->ESMax is not read; ESRef_dev is the [N] vector. */
 int lf_land_columns_device(int device, const lf_canopy_args *canopy, const lf_soil_args *soil, const double *ESRef_dev,
                            int derived);
+/* The soil columns / the land surface of an ENSEMBLE -- members that share the LDD, the geometry and the parameters -- in
+ * one call.  The convention of lf_routing_substeps_fused_members: the argument blocks are those of the single calls and
+ * their per-member pointers name member 0.
+ *   per member, m * member_stride elements further on (member_stride >= V*N; the elements between are neither read nor
+ *     written): every vector the single call writes, LeafDrainage / Interception / ESMax of the soil block, the ten in/out
+ *     rows of the canopy block, SoilMoistureStressDays, WFilla and WFillb when given
+ *   per-member forcing, m * forcing_member_stride elements further on (0: every member reads member 0's, otherwise >= N):
+ *     Rain, SnowMelt, isFrozenSoil (bytes), EWRef, ETRef, ESRef
+ *   shared: every [L,N] array, the five [N] calibration vectors (b_Xinanjiang, PowerInfPot, PowerPrefFlow, UpperZoneK,
+ *     GwPercStep), LAI, LAITerm, WPF3a / WPF3b, paddy_inactive
+ * A NULL diagnostic pointer (Theta*, Sat*) means "not reported" for every member.  The checks of the single calls apply
+ * unchanged; members < 1, member_stride < V*N, 0 < forcing_member_stride < N and members * tiles (256 columns each) beyond
+ * the 32-bit range are refused with LF_E_INVALID before any device is touched.  The unit of work is (tile, member): ONE
+ * launch of the column kernel covers all of them, tile-major, dealt to the workgroups so that the members of a tile run next
+ * to each other on one XCD (lf_land_members_unit), and one launch of the straggler kernel runs behind it; the statics of a
+ * tile are then streamed from HBM once per tile, not once per member.  Every member's result is bit-identical to the single
+ * call on that member alone; members == 1 IS the single call.  LF_LAND_MEMBERS=0: the members one after the other through
+ * the single call (the same bits).  The workspace grows to members times the single call's; afterwards
+ * lf_soil_last_deferred and lf_soil_substep_histogram cover all members (the sums of the members' own). */
+int lf_soil_columns_members_device(int device, const lf_soil_args *a, int derived, int members, int64_t member_stride,
+                                   int64_t forcing_member_stride);
+int lf_land_columns_members_device(int device, const lf_canopy_args *canopy, const lf_soil_args *soil,
+                                   const double *ESRef_dev, int derived, int members, int64_t member_stride,
+                                   int64_t forcing_member_stride);
+/* the form the last soil / land-surface call on the device took: 0 none yet, 1 single call, 2 members in one launch,
+ * 3 member after member */
+int lf_soil_last_form(int device);
+/* (tile, member) of launch position `position` of the member launch over ntiles * members units, when the workgroup at
+ * position 0 has linear id 0: the workgroups of one XCD (linear id mod 8) get a run of consecutive units of the tile-major
+ * order tile * members + member (host only: the function the kernel calls, for the tests) */
+int lf_land_members_unit(int64_t ntiles, int members, int64_t position, int64_t *tile, int *member);
 
 /* suctionUnsaturatedSoilPF + pressureHead (soilloop.py:427-432, 673-695; option simulatePF): pF = log10 of the capillary
  * head of the three soil layers, -1 where the head is not positive.  [V,N] by vegetation row, [L,N] by land-use row. */

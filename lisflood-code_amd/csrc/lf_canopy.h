@@ -25,12 +25,15 @@ struct column_out {
 struct column_in {
     double lai_term, lai, cum, crop_coef, cgn, wwp1, wwp1a, wwp1b, wfc1, wfc1a, wfc1b, w1, w1a, w1b, wpf3a, wpf3b;
 };
-__device__ __forceinline__ column_in load(const lf_canopy_args &A, int veg, long long i, long long j)
+// ms: where the column's member keeps its rows, in elements behind the vectors the struct names (the ensemble form of the
+// land-surface kernel: the state rows and the outputs are a member's own, LAI / LAITerm and every [L,N] parameter are
+// shared, so the two kinds of row take two kinds of address); 0 for a call without members
+__device__ __forceinline__ column_in load(const lf_canopy_args &A, int veg, long long i, long long j, long long ms = 0)
 {
     column_in c;
     c.lai_term = A.LAITerm[i];
     c.lai = A.LAI[i];
-    c.cum = A.CumInterception[i];
+    c.cum = (A.CumInterception + ms)[i];
     c.crop_coef = A.CropCoef[j];
     c.cgn = A.CropGroupNumber[j];
     c.wwp1 = A.WWP1[j];
@@ -39,9 +42,9 @@ __device__ __forceinline__ column_in load(const lf_canopy_args &A, int veg, long
     c.wfc1 = A.WFC1[j];
     c.wfc1a = A.WFC1a[j];
     c.wfc1b = A.WFC1b[j];
-    c.w1 = A.W1[j]; // the reference indexes W1 by the land-use row here (:592)
-    c.w1a = A.W1a[j];
-    c.w1b = A.W1b[j];
+    c.w1 = (A.W1 + ms)[j]; // the reference indexes W1 by the land-use row here (:592)
+    c.w1a = (A.W1a + ms)[j];
+    c.w1b = (A.W1b + ms)[j];
     c.wpf3a = c.wpf3b = 0.;
     if (A.WFilla && veg == (int)A.irrigated_veg) { // (uniform over a tile: a vegetation row)
         c.wpf3a = A.WPF3a[j];
@@ -52,9 +55,10 @@ __device__ __forceinline__ column_in load(const lf_canopy_args &A, int veg, long
 
 // i = veg * N + pix (row of the vegetation fraction), j = landuse * N + pix (row of its land use).  Stores the seven
 // canopy outputs (and the option outputs); the three soil-moisture values are RETURNED -- the caller stores them
-// (k_canopy) or carries them into the soil water balance of the same column (k_soil_fused).
+// (k_canopy) or carries them into the soil water balance of the same column (k_soil_fused).  ms: as in load().
 __device__ __forceinline__ column_out compute(const lf_canopy_args &A, int veg, long long pix, long long i, long long j,
-                                              const column_in &in, double rain, double ewref, double etref, bool frozen)
+                                              const column_in &in, double rain, double ewref, double etref, bool frozen,
+                                              long long ms = 0)
 {
     // --- interception (soilloop.py:531-544, kernel 27-70) ---
     const double one_minus_lt = 1. - in.lai_term;        // :531
@@ -86,14 +90,14 @@ __device__ __forceinline__ column_out compute(const lf_canopy_args &A, int veg, 
         ta_int = 0.;
         drain = 0.;
     }
-    A.Interception[i] = inter;
-    A.TaInterception[i] = ta_int;
-    A.LeafDrainage[i] = drain;
-    A.CumInterception[i] = cum;
+    (A.Interception + ms)[i] = inter;
+    (A.TaInterception + ms)[i] = ta_int;
+    (A.LeafDrainage + ms)[i] = drain;
+    (A.CumInterception + ms)[i] = cum;
     // --- potential transpiration (:549-556) ---
     const double transpir_max = in.crop_coef * etref * one_minus_lt;
     const double pot = npmax(transpir_max - ta_int, 0.);
-    A.potential_transpiration[i] = pot;
+    (A.potential_transpiration + ms)[i] = pot;
     // --- water stress and abstraction (:564-627) ---
     const double cgn = in.cgn;
     const double e = npmin(0.1 * etref * A.InvDtDay, 1.0);
@@ -107,16 +111,16 @@ __device__ __forceinline__ column_out compute(const lf_canopy_args &A, int veg, 
     const double w1 = in.w1;
     double rws = ((wcrit1 - wwp1) > 0) ? (w1 - wwp1) / (wcrit1 - wwp1) : 1.;
     rws = npmax(npmin(rws, 1.), 0.);
-    A.RWS[i] = rws;
-    if (A.SoilMoistureStressDays) A.SoilMoistureStressDays[i] = (rws < 1) ? A.DtDay : 0.; // :597-598 (repStressDays)
+    (A.RWS + ms)[i] = rws;
+    if (A.SoilMoistureStressDays) (A.SoilMoistureStressDays + ms)[i] = (rws < 1) ? A.DtDay : 0.; // :597-598 (repStressDays)
     if (A.WFilla && veg == (int)A.irrigated_veg) {                                          // :582-587 (wateruse)
-        A.WFilla[pix] = npmin(wcrit1a, in.wpf3a);
-        A.WFillb[pix] = npmin(wcrit1b, in.wpf3b);
+        (A.WFilla + ms)[pix] = npmin(wcrit1a, in.wpf3a);
+        (A.WFillb + ms)[pix] = npmin(wcrit1b, in.wpf3b);
     }
     const double transpirable = npmax(w1 - wwp1, 0.);
     double ta = npmin(rws * pot, transpirable);
     if (frozen) ta = 0.;
-    A.Ta[i] = ta;
+    (A.Ta + ms)[i] = ta;
     double w1a = in.w1a, w1b = in.w1b;
     const double wc1a = npmax(w1a - wcrit1a, 0.), wc1b = npmax(w1b - wcrit1b, 0.);
     double ta1a = npmin(ta, wc1a);

@@ -12,6 +12,7 @@
 #include <cstdlib>
 
 #include "lf_common.h"
+#include "lf_blocks.h"
 #include "lf_canopy.h"
 #include "lf_math.h"
 #include "lf_soil_math.h"
@@ -164,9 +165,40 @@ struct soil_tail {
     int flags; // 1 frozen, 2 / 4 / 8 pore space in 1a / 1b / 2
 };
 
-// phase 3: soilloop.py:313-354 for one column, 18 stores
+// ---- the ensemble form (lf_soil_columns_members_device, lf_land_columns_members_device) ----------------------------
+// Members share the LDD, the geometry and the parameters: every [L,N] array, the five [N] calibration vectors, LAI / LAITerm
+// and the paddy mask are ONE set of vectors, a member's own are its [V,N] rows (mo = m * stride elements behind the vectors
+// the argument blocks name) and its forcing (fo = m * fstride elements behind).  The unit of work is (tile, member) and one
+// launch covers all of them; a lane's arithmetic is the single call's, operation by operation -- only the addresses change,
+// and they change by an offset that is uniform over the workgroup (a scalar add to the vector's base).
+// Units are ordered tile-major, u = tile * members + m, and dealt to the workgroups with lf_xcd_contiguous: workgroups go to
+// the eight XCDs round robin, so the workgroups of one XCD get a run of consecutive units -- the members of a tile run next
+// to each other on ONE XCD, whose L2 then holds the tile's 176 B per column of statics for all of them (at most 7 tiles
+// straddle two XCDs).  In member-major order a static line's reuse distance is a whole member's traffic and no cache helps.
+// HIP promises no placement: with another dispatch order the result is the same and only the gain is lost.
+// -DLF_LAND_MEMBERS_XCD=0: plain tile-major launch order (A/B, tools/build_variant.sh).
+#ifndef LF_LAND_MEMBERS_XCD
+#define LF_LAND_MEMBERS_XCD 1
+#endif
+template <bool MEMBERS>
+struct soil_members {}; // the single call: nothing
+template <>
+struct soil_members<true> {
+    unsigned int members, ntiles; // ntiles: tiles of ONE member (the workspace holds members * ntiles, member-major)
+    long long stride, fstride;
+};
+// (tile, member) of the workgroup at `position` of the launch whose linear id is `linear_id`
+__host__ __device__ inline void land_members_unit(unsigned int units, unsigned int members, unsigned int position,
+                                                  unsigned int linear_id, unsigned int &tile, unsigned int &member)
+{
+    const unsigned int u = LF_LAND_MEMBERS_XCD ? (unsigned int)lf_xcd_contiguous((int)position, (int)units, linear_id) : position;
+    tile = u / members;
+    member = u - tile * members;
+}
+
+// phase 3: soilloop.py:313-354 for one column, 18 stores.  mo: the member's offset (0: no members)
 __device__ __forceinline__ void soil_finish(const lf_soil_args &A, long long i, bool drained, const soil_tail &T, double sa,
-                                            double sb, double sg)
+                                            double sb, double sg, long long mo = 0)
 {
     const bool frozen = (T.flags & 1) != 0, pore1a = (T.flags & 2) != 0, pore1b = (T.flags & 4) != 0, pore2 = (T.flags & 8) != 0;
     if (frozen) sa = sb = sg = 0.; // :313-316
@@ -186,26 +218,26 @@ __device__ __forceinline__ void soil_finish(const lf_soil_args &A, long long i, 
         uz += sg + T.pref;
     const double perc = dmin(T.gwp, uz);
     uz = dmax(uz - perc, 0.);
-    A.SeepTopToSubA[i] = sa;
-    A.SeepTopToSubB[i] = sb;
-    A.SeepSubToGW[i] = sg;
-    A.Infiltration[i] = inf;
-    A.W1a[i] = w1a;
-    A.W1b[i] = w1b;
-    A.W1[i] = w1;
-    A.W2[i] = w2;
+    (A.SeepTopToSubA + mo)[i] = sa;
+    (A.SeepTopToSubB + mo)[i] = sb;
+    (A.SeepSubToGW + mo)[i] = sg;
+    (A.Infiltration + mo)[i] = inf;
+    (A.W1a + mo)[i] = w1a;
+    (A.W1b + mo)[i] = w1b;
+    (A.W1 + mo)[i] = w1;
+    (A.W2 + mo)[i] = w2;
     // diagnostics, :330-336.  Nothing on the hot path reads them (the per-pixel Theta averages apart): each is computed
     // and stored only if the caller passed a vector for it (a NULL pointer = the map is not reported; uniform branches)
-    if (A.Theta1a) A.Theta1a[i] = pore1a ? w1a / T.sd1a : 0.;
-    if (A.Theta1b) A.Theta1b[i] = pore1b ? w1b / T.sd1b : 0.;
-    if (A.Theta2) A.Theta2[i] = pore2 ? w2 / T.sd2 : 0.;
-    if (A.Sat1a) A.Sat1a[i] = (w1a - T.wwp1a) / (T.wfc1a - T.wwp1a);
-    if (A.Sat1b) A.Sat1b[i] = (w1b - T.wwp1b) / (T.wfc1b - T.wwp1b);
-    if (A.Sat1) A.Sat1[i] = (w1 - T.wwp1) / (T.wfc1 - T.wwp1);
-    if (A.Sat2) A.Sat2[i] = (w2 - T.wwp2) / (T.wfc2 - T.wwp2);
-    A.UZOutflow[i] = uzout;
-    A.GwPercUZLZ[i] = perc;
-    A.UZ[i] = uz;
+    if (A.Theta1a) (A.Theta1a + mo)[i] = pore1a ? w1a / T.sd1a : 0.;
+    if (A.Theta1b) (A.Theta1b + mo)[i] = pore1b ? w1b / T.sd1b : 0.;
+    if (A.Theta2) (A.Theta2 + mo)[i] = pore2 ? w2 / T.sd2 : 0.;
+    if (A.Sat1a) (A.Sat1a + mo)[i] = (w1a - T.wwp1a) / (T.wfc1a - T.wwp1a);
+    if (A.Sat1b) (A.Sat1b + mo)[i] = (w1b - T.wwp1b) / (T.wfc1b - T.wwp1b);
+    if (A.Sat1) (A.Sat1 + mo)[i] = (w1 - T.wwp1) / (T.wfc1 - T.wwp1);
+    if (A.Sat2) (A.Sat2 + mo)[i] = (w2 - T.wwp2) / (T.wfc2 - T.wwp2);
+    (A.UZOutflow + mo)[i] = uzout;
+    (A.GwPercUZLZ + mo)[i] = perc;
+    (A.UZ + mo)[i] = uz;
 }
 
 // straggler records: [tile][slot][kStragFields] doubles, a tile's records one contiguous run; per tile a count and per
@@ -229,10 +261,16 @@ struct soil_strag {
 // LAITerm (soilloop.py:638) -- in registers instead of through HBM: the canopy's 24 streams per column shrink to the 12 the
 // soil part does not read anyway, inside a kernel whose sub-step arithmetic leaves the memory system idle part of the time.
 // Requires index_landuse[veg] == veg (a column's canopy and soil rows coincide) and every fraction active (mode 1).
-template <bool FASTPOW, bool DERIVED, bool CANOPY>
+// MEMBERS (the ensemble form, see soil_members): the workgroup's unit is (tile, member); the member's own rows lie mo, its
+// forcing fo elements behind the vectors A, C and ESRef name, its lists and records in workspace tile member * ntiles + tile.
+// (Loading the statics once per lane and looping over the members in registers was considered and is not wanted: the kernel
+// holds 161 VGPRs under amdgpu_waves_per_eu(3), the four-wave build already spilled, and eleven more doubles held across
+// the sub-step phase do not fit.)
+template <bool FASTPOW, bool DERIVED, bool CANOPY, bool MEMBERS = false>
 __global__ void __launch_bounds__(kTile) __attribute__((amdgpu_waves_per_eu(3)))
 k_soil_fused(lf_soil_args A, veg_plan P, unsigned short *__restrict__ all_list, unsigned int *__restrict__ all_count,
-             soil_strag G, unsigned int tile0, unsigned int tiles_per_veg, lf_canopy_args C, const double *__restrict__ ESRef)
+             soil_strag G, unsigned int tile0, unsigned int tiles_per_veg, lf_canopy_args C, const double *__restrict__ ESRef,
+             soil_members<MEMBERS> M)
 {
     constexpr int kLoopCap = kTile / 2; // multi-sub-step columns of a tile handled per round (more -> another round)
     __shared__ unsigned int s_count, s_next, s_all, s_strag;
@@ -250,7 +288,16 @@ k_soil_fused(lf_soil_args A, veg_plan P, unsigned short *__restrict__ all_list, 
     __syncthreads();
     const long long N = A.N;
     const double DtDay = A.DtDay;
-    const unsigned int tile = tile0 + blockIdx.x; // tiles of a vegetation row one after the other, row after row
+    unsigned int tile = tile0 + blockIdx.x; // tiles of a vegetation row one after the other, row after row
+    unsigned int wtile = tile;              // the tile's lists and records in the workspace
+    long long mo = 0, fo = 0;
+    if constexpr (MEMBERS) {
+        unsigned int m;
+        land_members_unit(M.members * M.ntiles, M.members, blockIdx.x, blockIdx.x, tile, m);
+        wtile = m * M.ntiles + tile;
+        mo = (long long)m * M.stride;
+        fo = (long long)m * M.fstride;
+    }
     const int veg = (int)(tile / tiles_per_veg);
     const long long pix = (long long)(tile - (unsigned int)veg * tiles_per_veg) * kTile + threadIdx.x;
     const int mode = P.mode[veg];
@@ -270,7 +317,7 @@ k_soil_fused(lf_soil_args A, veg_plan P, unsigned short *__restrict__ all_list, 
     if (active) {
         // every input of the column before any arithmetic: ~50 independent loads in flight per lane (the kernel is a
         // stream of ~70 vectors; memory-level parallelism, not ALU, sets the speed of this phase)
-        const double in_rain = A.Rain[pix], in_snow = A.SnowMelt[pix];
+        const double in_rain = (A.Rain + fo)[pix], in_snow = (A.SnowMelt + fo)[pix];
         double in_leaf, in_int, in_w1a, in_w1b, in_w1, in_esmax;
         // CANOPY: what the canopy of the column reads goes out FIRST and in one go (lf_canopy::load), the soil's own ~45
         // inputs right behind it; the canopy's arithmetic and its stores run while those travel.  (Input by input between
@@ -279,18 +326,18 @@ k_soil_fused(lf_soil_args A, veg_plan P, unsigned short *__restrict__ all_list, 
         double c_ewref = 0., c_etref = 0., c_esref = 0.;
         unsigned char c_frozen = 0;
         if (CANOPY) {
-            cin = lf_canopy::load(C, veg, i, j);
-            c_ewref = C.EWRef[pix];
-            c_etref = C.ETRef[pix];
-            c_esref = ESRef[pix];
-            c_frozen = A.isFrozenSoil[pix];
+            cin = lf_canopy::load(C, veg, i, j, mo);
+            c_ewref = (C.EWRef + fo)[pix];
+            c_etref = (C.ETRef + fo)[pix];
+            c_esref = (ESRef + fo)[pix];
+            c_frozen = (A.isFrozenSoil + fo)[pix];
         } else {
-            in_leaf = A.LeafDrainage[i]; in_int = A.Interception[i];
-            in_w1a = A.W1a[i]; in_w1b = A.W1b[i]; in_w1 = A.W1[i];
-            in_esmax = A.ESMax[i];
+            in_leaf = (A.LeafDrainage + mo)[i]; in_int = (A.Interception + mo)[i];
+            in_w1a = (A.W1a + mo)[i]; in_w1b = (A.W1b + mo)[i]; in_w1 = (A.W1 + mo)[i];
+            in_esmax = (A.ESMax + mo)[i];
         }
-        const double in_dslr = A.DSLR[i], in_w2 = A.W2[i];
-        const double in_uz = A.UZ[i];
+        const double in_dslr = (A.DSLR + mo)[i], in_w2 = (A.W2 + mo)[i];
+        const double in_uz = (A.UZ + mo)[i];
         const double in_store = A.StoreMaxPervious[j];
         const double in_bx = A.b_Xinanjiang[pix], in_pinf = A.PowerInfPot[pix], in_ppref = A.PowerPrefFlow[pix];
         const double in_uzk = A.UpperZoneK[pix];
@@ -304,12 +351,12 @@ k_soil_fused(lf_soil_args A, veg_plan P, unsigned short *__restrict__ all_list, 
         const double ws1a = A.WS1a[j], ws1b = A.WS1b[j], ws2 = A.WS2[j];
         T.ws1a = ws1a;
         if (CANOPY) {
-            const lf_canopy::column_out o = lf_canopy::compute(C, veg, pix, i, j, cin, in_rain, c_ewref, c_etref, c_frozen != 0);
+            const lf_canopy::column_out o = lf_canopy::compute(C, veg, pix, i, j, cin, in_rain, c_ewref, c_etref, c_frozen != 0, mo);
             in_leaf = o.leaf_drainage; in_int = o.interception;
             in_w1a = o.w1a; in_w1b = o.w1b; in_w1 = o.w1;
             in_esmax = c_esref * cin.lai_term;                                   // soilloop.py:638
         }
-        const bool is_frozen = A.isFrozenSoil[pix] != 0;
+        const bool is_frozen = (A.isFrozenSoil + fo)[pix] != 0;
         double im1a, im1b, im2, in_wres1, in_ws1;
         int flags;
         if (DERIVED) {
@@ -364,10 +411,10 @@ k_soil_fused(lf_soil_args A, veg_plan P, unsigned short *__restrict__ all_list, 
         const double w2 = in_w2;
         T.w1a = w1a; T.w1b = w1b; T.w2 = w2; T.inf = inf; T.pref = pref;
         // the outputs the sub-step loop does not touch
-        A.DSLR[i] = dslr;
-        A.ESAct[i] = esact;
-        A.PrefFlow[i] = pref;
-        A.AvailableWaterForInfiltration[i] = awi;
+        (A.DSLR + mo)[i] = dslr;
+        (A.ESAct + mo)[i] = esact;
+        (A.PrefFlow + mo)[i] = pref;
+        (A.AvailableWaterForInfiltration + mo)[i] = awi;
         // upper-zone outflow before the seepage arrives, :340-341
         T.uzout = dmin(in_uzk * in_uz, in_uz);
         T.uz = dmax(in_uz - T.uzout, 0.);
@@ -399,7 +446,7 @@ k_soil_fused(lf_soil_args A, veg_plan P, unsigned short *__restrict__ all_list, 
             long long c = (long long)nsub_f;
             c = c < kClasses - 1 ? c : kClasses - 1;
             const unsigned short key = (unsigned short)(threadIdx.x | ((int)c << 8));
-            all_list[(size_t)tile * kTile + atomicAdd(&s_all, 1u)] = key;
+            all_list[(size_t)wtile * kTile + atomicAdd(&s_all, 1u)] = key;
             unsigned int sr = 0xffffffffu;
             if (G.trip_cap > 0 && nsub_f > (double)G.trip_cap) sr = atomicAdd(&s_strag, 1u);
             if (sr < (unsigned int)kStragCap) { // a straggler: its record, then placeholders through phase 3 (sa = sb = sg = 0)
@@ -412,7 +459,7 @@ k_soil_fused(lf_soil_args A, veg_plan P, unsigned short *__restrict__ all_list, 
                 R[29] = T.sd1a; R[30] = T.sd1b; R[31] = T.sd2;
                 R[32] = T.wwp1a; R[33] = T.wwp1b; R[34] = T.wwp1; R[35] = T.wwp2;
                 R[36] = T.wfc1a; R[37] = T.wfc1b; R[38] = T.wfc1; R[39] = T.wfc2;
-                G.key[(size_t)tile * kStragCap + sr] = key;
+                G.key[(size_t)wtile * kStragCap + sr] = key;
             } else {
                 rank = atomicAdd(&s_count, 1u); // LDS: position in the tile's list
                 if (rank < (unsigned int)kLoopCap) { // the first round's records (nearly always the only round)
@@ -436,10 +483,10 @@ k_soil_fused(lf_soil_args A, veg_plan P, unsigned short *__restrict__ all_list, 
     {
         const unsigned int ns = s_strag < (unsigned int)kStragCap ? s_strag : (unsigned int)kStragCap;
         if (threadIdx.x == 0) {
-            all_count[tile] = s_all;
-            if (G.trip_cap > 0) G.count[tile] = ns;
+            all_count[wtile] = s_all;
+            if (G.trip_cap > 0) G.count[wtile] = ns;
         }
-        double *dst = G.rec + (size_t)tile * kStragCap * kStragFields; // the tile's records as ONE contiguous run
+        double *dst = G.rec + (size_t)wtile * kStragCap * kStragFields; // the tile's records as ONE contiguous run
         for (unsigned int idx = threadIdx.x; idx < ns * kStragFields; idx += kTile) dst[idx] = s_stage[idx];
     }
     for (unsigned int base = 0; base < count; base += kLoopCap) { // (uniform over the workgroup; nearly always one round)
@@ -503,14 +550,17 @@ k_soil_fused(lf_soil_args A, veg_plan P, unsigned short *__restrict__ all_list, 
         }
     }
     if (!active) return;
-    soil_finish(A, i, P.drained[veg] != 0, T, sa, sb, sg);
+    soil_finish(A, i, P.drained[veg] != 0, T, sa, sb, sg, mo);
 }
 
 // The stragglers of kStragGroup consecutive tiles: sorted by trip count in LDS, 20 columns per wavefront (three lanes per
 // column), heaviest first; the lane of layer 0 finishes the column (phase 3 of k_soil_fused) over the placeholders.
-template <bool FASTPOW>
+// MEMBERS: `ntiles` counts the workspace tiles of all members (member-major), so a group may pool the last tiles of one
+// member with the first of the next; a column's tile and member come from its workspace tile.
+template <bool FASTPOW, bool MEMBERS = false>
 __global__ void __launch_bounds__(kTile) k_soil_stragglers(lf_soil_args A, veg_plan P, soil_strag G, unsigned int group0,
-                                                           unsigned int ntiles, unsigned int tiles_per_veg)
+                                                           unsigned int ntiles, unsigned int tiles_per_veg,
+                                                           soil_members<MEMBERS> M)
 {
     constexpr int kMaxEntries = kStragGroup * kStragCap;
     static_assert(kClasses <= kTile && kClasses % 64 == 0 && kStragCap < 256 && kStragGroup < 256, "list layout");
@@ -574,8 +624,8 @@ __global__ void __launch_bounds__(kTile) k_soil_stragglers(lf_soil_args A, veg_p
         const unsigned int e = t * kColsPerWave + col;
         const bool valid = col_in_row < 5u && e < total;
         const unsigned int ent = entry[total - 1u - (valid ? e : t * kColsPerWave)]; // heaviest first
-        const unsigned int tile = t0 + (ent >> 8);
-        const double *__restrict__ R = G.rec + ((size_t)tile * kStragCap + (ent & 0xffu)) * kStragFields;
+        const unsigned int wtile = t0 + (ent >> 8);
+        const double *__restrict__ R = G.rec + ((size_t)wtile * kStragCap + (ent & 0xffu)) * kStragFields;
         const double *__restrict__ L = R + 7u * layer;
         const double w = L[0], wres = L[1], ws = L[2], ks = L[3], im = L[4], m = L[5], k0 = L[6];
         const int fl = (int)R[21];
@@ -597,9 +647,16 @@ __global__ void __launch_bounds__(kTile) k_soil_stragglers(lf_soil_args A, veg_p
             T.sd1a = R[29]; T.sd1b = R[30]; T.sd2 = R[31];
             T.wwp1a = R[32]; T.wwp1b = R[33]; T.wwp1 = R[34]; T.wwp2 = R[35];
             T.wfc1a = R[36]; T.wfc1b = R[37]; T.wfc1 = R[38]; T.wfc2 = R[39];
+            unsigned int tile = wtile;
+            long long mo = 0;
+            if constexpr (MEMBERS) {
+                const unsigned int m = wtile / M.ntiles;
+                tile = wtile - m * M.ntiles;
+                mo = (long long)m * M.stride;
+            }
             const int veg = (int)(tile / tiles_per_veg);
             const long long pix = (long long)(tile - (unsigned int)veg * tiles_per_veg) * kTile + (long long)R[23];
-            soil_finish(A, (long long)veg * A.N + pix, P.drained[veg] != 0, T, sum, sb, sg);
+            soil_finish(A, (long long)veg * A.N + pix, P.drained[veg] != 0, T, sum, sb, sg, mo);
         }
     }
 }
@@ -715,8 +772,15 @@ int lf_soil_substep_histogram(int device, int64_t *hist, int nbins)
     return LF_OK;
 }
 
+// what a call is of an ensemble (nullptr: the single call).  The workspace holds members * ntiles tiles, member-major.
+struct soil_ensemble {
+    int members;
+    int64_t stride, fstride;
+    int only; // -1: every member in one launch; m >= 0: member m alone through the single call's kernels (its pointers
+              // are the member's already), its lists and records in the member's part of the workspace
+};
 static int soil_columns_device(int device, const lf_soil_args *a, bool derived, const lf_canopy_args *canopy = nullptr,
-                               const double *esref = nullptr);
+                               const double *esref = nullptr, const soil_ensemble *ens = nullptr);
 
 int lf_soil_columns_device(int device, const lf_soil_args *a) { return soil_columns_device(device, a, false); }
 
@@ -729,7 +793,15 @@ int lf_soil_columns_device_derived(int device, const lf_soil_args *a) { return s
 // describe the same columns: same V = L, N, identity land-use rows, no paddy fraction, and the vectors both name (W1a, W1b,
 // W1, Interception, LeafDrainage, Rain, isFrozenSoil, the WWP / WFC parameters) must be the SAME device vectors; soil->ESMax
 // is not read.  Same results, bit for bit, as lf_canopy_device + lf_scale_rows_device + lf_soil_columns_device[_derived].
+static int land_columns_check(const lf_canopy_args *canopy, const lf_soil_args *soil, const double *ESRef_dev);
+
 int lf_land_columns_device(int device, const lf_canopy_args *canopy, const lf_soil_args *soil, const double *ESRef_dev, int derived)
+{
+    LF_TRY(land_columns_check(canopy, soil, ESRef_dev));
+    return soil_columns_device(device, soil, derived != 0, canopy, ESRef_dev);
+}
+
+static int land_columns_check(const lf_canopy_args *canopy, const lf_soil_args *soil, const double *ESRef_dev)
 {
     if (!canopy || !soil || !ESRef_dev || !canopy->index_landuse || !soil->index_landuse_all)
         return lf_set_error(LF_E_INVALID, "null argument");
@@ -747,10 +819,112 @@ int lf_land_columns_device(int device, const lf_canopy_args *canopy, const lf_so
                       canopy->WWP1a == soil->WWP1a && canopy->WWP1b == soil->WWP1b && canopy->WFC1a == soil->WFC1a &&
                       canopy->WFC1b == soil->WFC1b;
     if (!same) return lf_set_error(LF_E_INVALID, "land columns: canopy and soil arguments name different vectors");
-    return soil_columns_device(device, soil, derived != 0, canopy, ESRef_dev);
+    return LF_OK;
 }
 
-static int soil_columns_device(int device, const lf_soil_args *a, bool derived, const lf_canopy_args *canopy, const double *esref)
+// ---- an ensemble's soil columns / land surface in one call ------------------------------------------------------------
+// what the member arguments must satisfy on top of the single call's own checks, before any device is touched
+static int members_check(const lf_soil_args *a, int members, int64_t member_stride, int64_t forcing_member_stride)
+{
+    if (members < 1) return lf_set_error(LF_E_INVALID, "members = %d: at least one member", members);
+    if (a->V < 0 || a->N < 0) return lf_set_error(LF_E_INVALID, "V and N must not be negative");
+    if ((unsigned long long)a->V * (unsigned long long)a->N >= 0xffffffffull)
+        return lf_set_error(LF_E_INVALID, "V*N exceeds the 32-bit column id range");
+    if (member_stride < a->V * a->N)
+        return lf_set_error(LF_E_INVALID, "member_stride = %lld is less than V*N = %lld", (long long)member_stride,
+                            (long long)(a->V * a->N));
+    if (forcing_member_stride < 0 || (forcing_member_stride > 0 && forcing_member_stride < a->N))
+        return lf_set_error(LF_E_INVALID, "forcing_member_stride = %lld: 0 (shared forcing) or at least N = %lld",
+                            (long long)forcing_member_stride, (long long)a->N);
+    const unsigned long long ntiles = (unsigned long long)((a->N + kTile - 1) / kTile) * (unsigned long long)a->V;
+    if (ntiles * (unsigned long long)members > 0x7fffffffull)
+        return lf_set_error(LF_E_INVALID, "members * tiles = %llu exceeds the 32-bit range of a launch", ntiles * (unsigned long long)members);
+    return LF_OK;
+}
+
+// member m's own argument blocks: the per-member vectors m strides further on, the shared ones as they are
+static void member_blocks(lf_soil_args &s, lf_canopy_args *cn, const double *&esref, int m, int64_t stride, int64_t fstride)
+{
+    const int64_t mo = (int64_t)m * stride, fo = (int64_t)m * fstride;
+    auto mv = [mo](auto *&p) { if (p) p += mo; };
+    auto fv = [fo](auto *&p) { if (p) p += fo; };
+    mv(s.LeafDrainage); mv(s.Interception); mv(s.ESMax);
+    mv(s.AvailableWaterForInfiltration); mv(s.DSLR); mv(s.ESAct); mv(s.PrefFlow); mv(s.Infiltration);
+    mv(s.W1a); mv(s.W1b); mv(s.W1); mv(s.W2);
+    mv(s.Theta1a); mv(s.Theta1b); mv(s.Theta2); mv(s.Sat1a); mv(s.Sat1b); mv(s.Sat1); mv(s.Sat2);
+    mv(s.SeepTopToSubA); mv(s.SeepTopToSubB); mv(s.SeepSubToGW); mv(s.UZOutflow); mv(s.UZ); mv(s.GwPercUZLZ);
+    fv(s.Rain); fv(s.SnowMelt); fv(s.isFrozenSoil);
+    if (cn) {
+        mv(cn->Interception); mv(cn->TaInterception); mv(cn->LeafDrainage); mv(cn->CumInterception);
+        mv(cn->potential_transpiration); mv(cn->RWS); mv(cn->Ta); mv(cn->W1a); mv(cn->W1b); mv(cn->W1);
+        mv(cn->SoilMoistureStressDays); mv(cn->WFilla); mv(cn->WFillb);
+        fv(cn->Rain); fv(cn->EWRef); fv(cn->ETRef); fv(cn->isFrozenSoil);
+        fv(esref);
+    }
+}
+
+static int columns_members_device(int device, const lf_canopy_args *canopy, const lf_soil_args *soil, const double *esref,
+                                  bool derived, int members, int64_t member_stride, int64_t forcing_member_stride)
+{
+    if (!soil || !soil->index_landuse_all) return lf_set_error(LF_E_INVALID, "null argument");
+    if (canopy) LF_TRY(land_columns_check(canopy, soil, esref));
+    LF_TRY(members_check(soil, members, member_stride, forcing_member_stride));
+    if (members == 1) return soil_columns_device(device, soil, derived, canopy, esref); // IS the single call
+    soil_ensemble ens{members, member_stride, forcing_member_stride, -1};
+    // LF_LAND_MEMBERS=0: the members one after the other through the single call's kernels (A/B; the same bits)
+    const char *e = std::getenv("LF_LAND_MEMBERS");
+    if (!(e && e[0] == '0')) return soil_columns_device(device, soil, derived, canopy, esref, &ens);
+    for (int m = 0; m < members; ++m) {
+        lf_soil_args s = *soil;
+        lf_canopy_args cn{};
+        if (canopy) cn = *canopy;
+        const double *es = esref;
+        member_blocks(s, canopy ? &cn : nullptr, es, m, member_stride, forcing_member_stride);
+        ens.only = m;
+        LF_TRY(soil_columns_device(device, &s, derived, canopy ? &cn : nullptr, es, &ens));
+    }
+    return LF_OK;
+}
+
+int lf_soil_columns_members_device(int device, const lf_soil_args *a, int derived, int members, int64_t member_stride,
+                                   int64_t forcing_member_stride)
+{
+    return columns_members_device(device, nullptr, a, nullptr, derived != 0, members, member_stride, forcing_member_stride);
+}
+
+int lf_land_columns_members_device(int device, const lf_canopy_args *canopy, const lf_soil_args *soil, const double *ESRef_dev,
+                                   int derived, int members, int64_t member_stride, int64_t forcing_member_stride)
+{
+    if (!canopy) return lf_set_error(LF_E_INVALID, "null argument");
+    return columns_members_device(device, canopy, soil, ESRef_dev, derived != 0, members, member_stride, forcing_member_stride);
+}
+
+// which form the last soil / land-surface call on `device` took: 0 none yet, 1 the single call, 2 the members in one launch,
+// 3 member after member through the single call's kernels
+int lf_soil_last_form(int device)
+{
+    lf_device_ctx *c;
+    LF_TRY(lf_ctx(device, &c));
+    return c->soil_last_form;
+}
+
+// (tile, member) of launch position `position` of the member launch over ntiles * members units whose first workgroup has
+// linear id 0 -- the function the kernel calls (host only, for the tests)
+int lf_land_members_unit(int64_t ntiles, int members, int64_t position, int64_t *tile, int *member)
+{
+    if (!tile || !member) return lf_set_error(LF_E_INVALID, "null argument");
+    if (ntiles < 1 || members < 1 || (unsigned long long)ntiles * (unsigned long long)members > 0x7fffffffull)
+        return lf_set_error(LF_E_INVALID, "ntiles and members must be positive and their product within the 32-bit range");
+    if (position < 0 || position >= ntiles * members) return lf_set_error(LF_E_INVALID, "position outside the launch");
+    unsigned int t, m;
+    land_members_unit((unsigned int)(ntiles * members), (unsigned int)members, (unsigned int)position, (unsigned int)position, t, m);
+    *tile = t;
+    *member = (int)m;
+    return LF_OK;
+}
+
+static int soil_columns_device(int device, const lf_soil_args *a, bool derived, const lf_canopy_args *canopy, const double *esref,
+                               const soil_ensemble *ens)
 {
     if (!a || !a->index_landuse_all) return lf_set_error(LF_E_INVALID, "null argument");
     lf_device_ctx *c;
@@ -765,7 +939,8 @@ static int soil_columns_device(int device, const lf_soil_args *a, bool derived, 
         return lf_set_error(LF_E_INVALID, "V*N exceeds the 32-bit column id range");
     const unsigned int tiles_per_veg = (unsigned int)((a->N + kTile - 1) / kTile);
     const size_t ntiles = (size_t)tiles_per_veg * (size_t)a->V;
-    const soil_ws_layout L = soil_layout(ntiles);
+    const size_t ws_tiles = ntiles * (size_t)(ens ? ens->members : 1), ws_tile0 = ens && ens->only > 0 ? ntiles * (size_t)ens->only : 0;
+    const soil_ws_layout L = soil_layout(ws_tiles);
     if (c->soil_ws_bytes < L.bytes) {
         if (c->soil_ws) LF_HIP(hipFree(c->soil_ws));
         c->soil_ws = nullptr;
@@ -773,14 +948,15 @@ static int soil_columns_device(int device, const lf_soil_args *a, bool derived, 
         LF_HIP(hipMalloc(&c->soil_ws, L.bytes));
         c->soil_ws_bytes = L.bytes;
     }
-    c->soil_ntiles = ntiles;
+    c->soil_ntiles = ws_tiles;
+    c->soil_last_form = !ens ? 1 : ens->only < 0 ? 2 : 3;
     char *ws = (char *)c->soil_ws;
-    unsigned int *all_count = (unsigned int *)(ws + L.all_count);
-    unsigned short *all_list = (unsigned short *)(ws + L.all_list);
+    unsigned int *all_count = (unsigned int *)(ws + L.all_count) + ws_tile0;
+    unsigned short *all_list = (unsigned short *)(ws + L.all_list) + ws_tile0 * kTile;
     soil_strag G;
-    G.count = (unsigned int *)(ws + L.s_count);
-    G.key = (unsigned short *)(ws + L.s_key);
-    G.rec = (double *)(ws + L.s_rec);
+    G.count = (unsigned int *)(ws + L.s_count) + ws_tile0;
+    G.key = (unsigned short *)(ws + L.s_key) + ws_tile0 * kStragCap;
+    G.rec = (double *)(ws + L.s_rec) + ws_tile0 * kStragCap * kStragFields;
     // columns above this many Courant sub-steps leave their tile for k_soil_stragglers; LF_SOIL_TRIP_CAP=0: none do
     G.trip_cap = kSoilTripCap;
     if (const char *e = std::getenv("LF_SOIL_TRIP_CAP")) G.trip_cap = (int)std::atol(e) > 0 ? (int)std::atol(e) : 0;
@@ -791,15 +967,24 @@ static int soil_columns_device(int device, const lf_soil_args *a, bool derived, 
     // of the next chunk was measured and dropped: 2.28 / 2.29 / 2.35 / 2.50 / 2.90 ms for 1 / 2 / 4 / 8 / 16 chunks on the wet
     // synthetic soil -- the streaming launch fills every compute unit, the second stream only gets the chunk tails.  So was
     // a build at four wavefronts per SIMD: the state a lane holds across the sub-step phase spills, 1.72 vs 1.26 ms.)
-    const dim3 grid((unsigned)ntiles), block(kTile);
+    const bool one_launch = ens && ens->only < 0; // every (tile, member) unit in one grid
+    const dim3 grid((unsigned)(one_launch ? ws_tiles : ntiles)), block(kTile);
     size_t dyn = 0; // LF_SOIL_DEBUG_LDS=<bytes>: extra LDS per workgroup, to bound the tiles in flight per compute unit (timing experiments)
     if (const char *e = std::getenv("LF_SOIL_DEBUG_LDS")) dyn = (size_t)std::atol(e);
     if (const char *e = std::getenv("LF_SOIL_NO_DERIVED")) derived = derived && e[0] != '1'; // A/B switch
     lf_canopy_args C{};
     if (canopy) C = *canopy;
+    soil_members<true> M{};
+    if (one_launch) M = soil_members<true>{(unsigned int)ens->members, (unsigned int)ntiles, ens->stride, ens->fstride};
 #define LF_SOIL_LAUNCH(FP, DR, CN)                                                                                        \
-    hipLaunchKernelGGL((k_soil_fused<FP, DR, CN>), grid, block, dyn, c->stream, *a, P, all_list, all_count, G, 0u,       \
-                       tiles_per_veg, C, esref)
+    do {                                                                                                                  \
+        if (one_launch)                                                                                                   \
+            hipLaunchKernelGGL((k_soil_fused<FP, DR, CN, true>), grid, block, dyn, c->stream, *a, P, all_list, all_count, \
+                               G, 0u, tiles_per_veg, C, esref, M);                                                        \
+        else                                                                                                              \
+            hipLaunchKernelGGL((k_soil_fused<FP, DR, CN>), grid, block, dyn, c->stream, *a, P, all_list, all_count, G,    \
+                               0u, tiles_per_veg, C, esref, soil_members<false>{});                                       \
+    } while (0)
     if (canopy) {
         if (fastpow && derived) LF_SOIL_LAUNCH(true, true, true);
         else if (fastpow) LF_SOIL_LAUNCH(true, false, true);
@@ -813,11 +998,17 @@ static int soil_columns_device(int device, const lf_soil_args *a, bool derived, 
     }
 #undef LF_SOIL_LAUNCH
     if (G.trip_cap > 0) {
-        const dim3 grid2((unsigned)((ntiles + kStragGroup - 1) / kStragGroup));
-        if (fastpow)
-            hipLaunchKernelGGL(k_soil_stragglers<true>, grid2, block, 0, c->stream, *a, P, G, 0u, (unsigned int)ntiles, tiles_per_veg);
+        const unsigned int nt = (unsigned int)(one_launch ? ws_tiles : ntiles); // (the pools of a member launch span members)
+        const dim3 grid2((nt + kStragGroup - 1) / kStragGroup);
+        if (one_launch) {
+            if (fastpow)
+                hipLaunchKernelGGL((k_soil_stragglers<true, true>), grid2, block, 0, c->stream, *a, P, G, 0u, nt, tiles_per_veg, M);
+            else
+                hipLaunchKernelGGL((k_soil_stragglers<false, true>), grid2, block, 0, c->stream, *a, P, G, 0u, nt, tiles_per_veg, M);
+        } else if (fastpow)
+            hipLaunchKernelGGL((k_soil_stragglers<true>), grid2, block, 0, c->stream, *a, P, G, 0u, nt, tiles_per_veg, soil_members<false>{});
         else
-            hipLaunchKernelGGL(k_soil_stragglers<false>, grid2, block, 0, c->stream, *a, P, G, 0u, (unsigned int)ntiles, tiles_per_veg);
+            hipLaunchKernelGGL((k_soil_stragglers<false>), grid2, block, 0, c->stream, *a, P, G, 0u, nt, tiles_per_veg, soil_members<false>{});
     }
     LF_HIP(hipGetLastError());
     return LF_OK;

@@ -23,7 +23,7 @@ _KIND = {"p": C.c_void_p, "i": C.c_int, "u": C.c_uint, "q": C.c_int64, "z": C.c_
 _SIGNATURES = {
     "": "version",
     "i": "side_stream_begin side_stream_end side_stream_join lane_fork lane_join device_trim "
-         "device_synchronize timer_start",
+         "device_synchronize timer_start soil_last_form",
     "ii": "upload_begin upload_end upload_wait compute_acquire compute_release lane_select",
     "iippq": "calibration_streams",
     "iiqp": "substep_stage",
@@ -31,9 +31,11 @@ _SIGNATURES = {
           "pixel_aggregates_device interception_host soil_columns_host interception_device soil_columns_device "
           "soil_columns_device_derived soil_last_deferred",
     "ipi": "soil_substep_histogram",
+    "ipiiqq": "soil_columns_members_device",
     "ipiz": "memset",
     "ippii": "lddrepair_raster_device",
     "ipppi": "land_columns_device",
+    "ipppiiqq": "land_columns_members_device",
     "ipppii": "router_route_device_multi upstream_sum_raster_device lddmask_raster_device ldd_raster_host",
     "ipppqq": "scale_rows_device",
     "ippqi": "calibration_copy",
@@ -85,6 +87,7 @@ _SIGNATURES = {
     "ppppppp": "dist_graph_get_fused_plan",
     "pppppppp": "dist_graph_get_route_plan",
     "qipqpppqppppppp": "site_plan",
+    "qiqpp": "land_members_unit",
     "p>q": "graph_num_pixels graph_num_levels router_num_pixels dist_graph_num_pixels dist_graph_state_size "
            "dist_graph_num_launch_units dist_graph_num_noncontiguous dist_router_state_size "
            "dist_router_last_launches",

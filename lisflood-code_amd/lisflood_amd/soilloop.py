@@ -350,3 +350,221 @@ class _SoilPfArgs(C.Structure):  # lf_soil_pf_args
     _fields_ = ([(k, C.c_void_p) for k in ["pF0", "pF1", "pF2"] + soilloop._PF_V + soilloop._PF_L] +
                 [("index_landuse_all", C.c_void_p), ("HeadMax", C.c_double), ("V", C.c_int64), ("L", C.c_int64),
                  ("N", C.c_int64)])
+
+
+# =================================================================================================
+# Ensembles: members that share the LDD, the geometry and the parameters -- one call per model step
+# =================================================================================================
+_STATIC_N = "b_Xinanjiang PowerInfPot PowerPrefFlow UpperZoneK GwPercStep".split()
+_SOIL_FORCING = "Rain SnowMelt isFrozenSoil".split()
+_LAND_FORCING = "Rain SnowMelt isFrozenSoil EWRef ETRef ESRef".split()
+GAP_BYTE = 0xA5                          # what set_gaps() puts between the members' rows of a byte vector
+
+
+class _EnsembleVectors:
+    """The device vectors of an ensemble call (lf_soil_columns_members_device / lf_land_columns_members_device): a member's
+    own [V,N] rows `stride` = V*N + pad elements apart, its forcing `fstride` = N + pad elements apart, everything else
+    once.  A shared forcing vector is kept in every member's row all the same, so that a later per-member one needs no
+    re-layout; the call passes forcing_member_stride = 0 while every forcing vector is shared."""
+
+    def _setup(self, members, V, N, device, pad):
+        self.members, self.V, self.N, self.device, self.pad = int(members), V, N, device, int(pad)
+        if self.members < 1 or self.pad < 0:
+            raise ValueError("members must be at least 1 and pad not negative")
+        self.stride, self.fstride = V * N + self.pad, N + self.pad
+        self.dev, self.shared = {}, {}
+        self._member, self._forcing, self._static = [], [], []
+        self._shared_forcing = {}
+        self._gap = 0.0
+
+    def _layout(self, name, value, width, stride, dtype):
+        """value broadcast over the members -> [members * stride] with the gaps holding the gap value"""
+        full = np.empty((self.members, stride), dtype)
+        full[:, width:] = GAP_BYTE if dtype == np.uint8 else self._gap
+        rows = np.asarray(value, dtype).reshape((-1, width))
+        if rows.shape[0] not in (1, self.members):
+            raise ValueError("%s: %d rows for %d members" % (name, rows.shape[0], self.members))
+        full[:, :width] = rows
+        return full.reshape(-1)
+
+    def _put(self, name, value):
+        if name in ("WFilla", "WFillb"):
+            raise ValueError("%s is an output of the call" % name)
+        if name in self._member:
+            host = self._layout(name, f64(value), self.V * self.N, self.stride, np.float64)
+        elif name in self._forcing:
+            byte = name in _BOOL
+            value = u8(value) if byte else f64(value)
+            self._shared_forcing[name] = value.ndim == 1
+            host = self._layout(name, value, self.N, self.fstride, np.uint8 if byte else np.float64)
+        else:
+            raise ValueError("%s is one of the arrays the members share: it is static" % name
+                             if name in self._static else "%s is no vector of this call" % name)
+        if name in self.dev:
+            self.dev[name].upload(host)
+        else:
+            self.dev[name] = DeviceArray.from_host(host, self.device)
+
+    def _put_static(self, name, value):
+        self._static.append(name)
+        self.dev[name] = DeviceArray.from_host(u8(value) if name in _BOOL else f64(value), self.device)
+
+    def forcing_member_stride(self):
+        return 0 if all(self._shared_forcing.values()) else self.fstride
+
+    def get(self, name):
+        """[members,V,N] of a member vector, [members,N] of a forcing vector, the array itself of a shared one"""
+        out = self.dev[name].download()
+        if name in ("WFilla", "WFillb"):               # [N] per member, at the head of the member's stride
+            return np.ascontiguousarray(out.reshape(self.members, self.stride)[:, :self.N])
+        if name in self._member:
+            return np.ascontiguousarray(out.reshape(self.members, self.stride)[:, :self.V * self.N]).reshape(self.members, self.V, self.N)
+        if name in self._forcing:
+            return np.ascontiguousarray(out.reshape(self.members, self.fstride)[:, :self.N])
+        return out
+
+    def set(self, name, value):
+        """a member vector from [V,N] (every member) or [members,V,N], a forcing vector from [N] or [members,N]; the arrays
+        the members share are static and refused"""
+        self._put(name, value)
+
+    def gaps(self, name):
+        """[members, pad]: the elements between the members' rows, which no call reads or writes"""
+        out = self.dev[name].download()
+        width, stride = (self.V * self.N, self.stride) if name in self._member else (self.N, self.fstride)
+        return out.reshape(self.members, stride)[:, width:]
+
+    def set_gaps(self, value):
+        """plant `value` (GAP_BYTE in byte vectors) between the members' rows of every vector"""
+        self._gap = float(value)
+        for name in self._member + self._forcing:
+            host = self.dev[name].download()
+            width, stride = (self.V * self.N, self.stride) if name in self._member else (self.N, self.fstride)
+            host.reshape(self.members, stride)[:, width:] = GAP_BYTE if host.dtype == np.uint8 else self._gap
+            self.dev[name].upload(host)
+
+    def last_form(self):
+        """lf_soil_last_form: 0 none yet, 1 single call, 2 members in one launch, 3 member after member"""
+        rc = lib().lf_soil_last_form(self.device)
+        if rc < 0:
+            check(rc)
+        return rc
+
+    def substep_histogram(self, nbins=128):
+        """SoilColumnsDevice.substep_histogram over all members of the last step"""
+        hist = (C.c_int64 * nbins)()
+        check(lib().lf_soil_substep_histogram(self.device, hist, nbins))
+        return np.array(hist[:], dtype=np.int64)
+
+    def last_deferred(self):
+        n = C.c_int64(0)
+        check(lib().lf_soil_last_deferred(self.device, C.byref(n)))
+        return n.value
+
+    def free(self):
+        for a in self.dev.values():
+            a.free()
+        self.dev = {}
+
+    def _soil_block(self, d, names):
+        a = self.soil = _SoilArgs()
+        for k in names:
+            if k in self.dev:
+                setattr(a, k, self.dev[k].ptr.value)
+        a.DtDay, a.AvWaterThreshold = float(d["DtDay"]), float(d["AvWaterThreshold"])
+        a.CourantCrit, a.DrainedFraction = float(d["CourantCrit"]), float(d["DrainedFraction"])
+        a.V, a.L, a.N = self.V, self.L, self.N
+        return a
+
+
+class SoilColumnsEnsemble(_EnsembleVectors):
+    """SoilColumnsDevice for an ensemble: `step()` is one soilColumnsWaterBalance pass of every member in ONE launch
+    (lf_soil_columns_members_device).  d: the arrays of the reference call; the [V,N] vectors as [V,N] (every member starts
+    there) or [members,V,N], Rain / SnowMelt / isFrozenSoil as [N] or [members,N]; the [L,N] arrays, the five [N]
+    calibration vectors and the paddy mask are shared."""
+
+    def __init__(self, d, members, device=0, pad=0):
+        V, N = np.asarray(d["Interception"]).shape[-2:]
+        self._setup(members, V, N, device, pad)
+        self.L = np.asarray(d["WS1a"]).shape[0]
+        self.derived = derived_parameters_hold(d)
+        self._member, self._forcing = _V_IN + _V_IO, list(_SOIL_FORCING)
+        for k in _L_FIELDS + _STATIC_N:
+            self._put_static(k, d[k])
+        for k in self._member + self._forcing:
+            self._put(k, d[k])
+        a = self._soil_block(d, _L_FIELDS + _N_FIELDS + _V_IN + _V_IO)
+        self._keep = []
+        if _fill_small(a, self._keep, d, V):
+            pi = u8(d["paddy_inactive"])
+            self._static.append("paddy_inactive")
+            self.dev["paddy_inactive"] = DeviceArray.from_host(pi, device)
+            a.paddy_inactive = self.dev["paddy_inactive"].ptr.value
+            any_ = np.ascontiguousarray(pi.reshape(-1, N).any(axis=1).astype(np.uint8))
+            self._keep.append(any_)
+            a.paddy_any = any_.ctypes.data
+
+    def step(self, forcing=None):
+        for k, x in (forcing or {}).items():
+            self._put(k, x)
+        check(lib().lf_soil_columns_members_device(self.device, C.byref(self.soil), 1 if self.derived else 0, self.members,
+                                                   self.stride, self.forcing_member_stride()))
+
+
+class LandSurfaceEnsemble(_EnsembleVectors):
+    """The land surface (canopy, ESMax = ESRef * LAITerm, soil columns) of an ensemble, device-resident: `step(forcing)` is
+    ONE launch for every member (lf_land_columns_members_device).  d: the fields of _CanopyArgs / _SoilArgs by name, ESRef
+    and the scalars (DtDay, InvDtDay, LeafDrainageK, AvWaterThreshold, CourantCrit, DrainedFraction; is_irrigated, default
+    the third fraction) -- e.g. dict(values, **scalars) of synthetic.hotpath_scenario.  State rows as [V,N] (every member
+    starts there) or [members,V,N]; the forcing (Rain, SnowMelt, EWRef, ETRef, ESRef, isFrozenSoil) as [N] or [members,N],
+    zero where d has none.  Needs V = L with identity land-use rows and no paddy fraction, as lf_land_columns_device does.
+    The derived form is used when derived_parameters_hold(d)."""
+
+    def __init__(self, d, members, device=0, pad=0):
+        V, N = np.asarray(d["W1a"]).shape[-2:]
+        self._setup(members, V, N, device, pad)
+        self.L = np.asarray(d["WS1a"]).shape[0]
+        self.derived = derived_parameters_hold(d)
+        self._member = list(dict.fromkeys(_CANOPY_IO + _V_IO + [k for k in ("SoilMoistureStressDays",) if k in d]))
+        self._forcing = list(_LAND_FORCING)
+        wateruse = "WFilla" in d
+        for k in _L_FIELDS:
+            if k in d:                                 # (the ten derived ones may be left out of a derived call)
+                self._put_static(k, d[k])
+        for k in _STATIC_N + _CANOPY_V_IN + ["CropCoef", "CropGroupNumber"] + (["WPF3a", "WPF3b"] if wateruse else []):
+            self._put_static(k, d[k])
+        for k in self._member:
+            self._put(k, d[k] if k in d else np.zeros((V, N)))
+        for k in self._forcing:
+            self._put(k, d[k] if k in d else np.zeros(N, bool if k in _BOOL else np.float64))
+        s = self._soil_block(d, _L_FIELDS + _N_FIELDS + _V_IN + _V_IO)         # (ESMax stays NULL: the land form does not read it)
+        c = self.canopy = _CanopyArgs()
+        for k in _CANOPY_IO + _CANOPY_V_IN + _CANOPY_L_IN + _CANOPY_N_IN + ["SoilMoistureStressDays"]:
+            if k in self.dev:
+                setattr(c, k, self.dev[k].ptr.value)
+        c.irrigated_veg = -1
+        if wateruse:                                   # WFilla / WFillb [N] per member: the first N of a member's stride
+            self._member += ["WFilla", "WFillb"]
+            for k in ("WFilla", "WFillb"):
+                host = np.full((self.members, self.stride), self._gap)
+                host[:, :N] = np.asarray(d[k], np.float64).reshape(-1, N)
+                self.dev[k] = DeviceArray.from_host(host.reshape(-1), device)
+                setattr(c, k, self.dev[k].ptr.value)
+            c.WPF3a, c.WPF3b = self.dev["WPF3a"].ptr.value, self.dev["WPF3b"].ptr.value
+            c.irrigated_veg = int(d.get("irrigated_veg", V - 1))
+        self._idx = np.arange(V, dtype=np.int64)
+        self._irr = u8(d["is_irrigated"]) if "is_irrigated" in d else u8(np.arange(V) == 2)
+        self._pad = np.zeros(V, np.uint8)
+        c.index_landuse = s.index_landuse_all = self._idx.ctypes.data
+        s.is_irrigated, s.is_paddy_irrig = self._irr.ctypes.data, self._pad.ctypes.data
+        c.LeafDrainageK, c.DtDay = float(d["LeafDrainageK"]), float(d["DtDay"])
+        c.InvDtDay = float(d["InvDtDay"]) if "InvDtDay" in d else 1.0 / float(d["DtDay"])
+        c.V, c.L, c.N = V, self.L, N
+
+    def step(self, forcing=None):
+        """forcing: dict of [N] or [members,N] vectors; shared forcing only if all of the call's forcing vectors are [N]"""
+        for k, x in (forcing or {}).items():
+            self._put(k, x)
+        check(lib().lf_land_columns_members_device(self.device, C.byref(self.canopy), C.byref(self.soil),
+                                                   self.dev["ESRef"].ptr, 1 if self.derived else 0, self.members, self.stride,
+                                                   self.forcing_member_stride()))
