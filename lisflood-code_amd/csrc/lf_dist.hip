@@ -1195,9 +1195,7 @@ int dist_fused_prepare(lf_dist_router *r, const lf_substep_args *a, int nsteps)
     if (!r || !a || nsteps < 1) return lf_set_error(LF_E_INVALID, "bad argument");
     LF_TRY(fused_check_call(*r, *a, 0, "partitioned sub-steps need")); // (the sideflow stride comes with the phases)
     LF_HIP(hipSetDevice(r->device));
-    const size_t n = (size_t)std::max<int64_t>(r->N, 1);
-    if (!r->fused_qr1.p) LF_TRY(r->fused_qr1.alloc(2 * n));
-    if (a->split && !r->fused_qr2.p) LF_TRY(r->fused_qr2.alloc(2 * n));
+    LF_TRY(fused_parity_ensure(*r, a->split != 0, (size_t)std::max<int64_t>(r->N, 1)));
     const size_t need = (size_t)std::max<int64_t>(r->n_slots, 1) * (size_t)nsteps;
     if (r->slab_steps < nsteps || !r->slab1.p) {
         LF_HIP(hipStreamSynchronize(r->ctx->stream)); // nobody may still read the old slabs

@@ -1737,18 +1737,6 @@ inline int fused_statics_flags(lf_router_core &r, fused_args &F, bool structures
     return LF_OK;
 }
 
-// The wavefront over levels [level0, level0 + nlevels) -- and, if nblocks >= 0, their level blocks [b0, b0 + nblocks) of
-// r.fplan --
-// for F.nsteps sub-steps; fills F's wave fields and adds its launches to `launches`.  Of the three schedules the first that
-// applies runs:
-//   time-major   (time_major: the caller's precondition) one k_fused_level_steps launch per level; with structures in the
-//                loop (tm: their site cache) also one per level that holds a site, behind the level's own;
-//   level blocks (nblocks >= 0, F.nsteps <= kMaxPackedSteps) per wave time t: cones(ncones) launches the multi-level
-//                blocks through a cone kernel on a packed grid of ncones workgroups, levels(grid) the single levels
-//                through k_fused_substeps (F.use_lvl);
-//   levels       per wave time t: levels(grid), level t - s for sub-step s.
-// sites(blocks, lo, hi) runs first at every wave time t, with the window [lo, hi] of the level blocks (blocks = true) or
-// levels in flight, counted from b0 / level0.  r.last_fused_form tells which of the three ran.
 // Whether the wavefront over levels [level0, level0 + nlevels) takes the time-major form, its caller's precondition given:
 // few, wide levels -- level after level, every level through all its sub-steps (k_fused_level_steps).
 // LF_FUSED_TIME_MAJOR=0 / 1: never / whenever it applies (A/B switch, read per call); LF_FUSED_TIME_MAJOR_LEVELS: the level
@@ -1774,58 +1762,104 @@ inline bool fused_time_major_ready(lf_router_core &r, int level0, int nlevels, i
            lf_history_ensure(r.fused_hist1, r.fused_hist2, r.fused_hist_refused, (size_t)nsteps * (size_t)r.N, split);
 }
 
+// The router outputs by sub-step parity (fused_args::qr1 / qr2) of a router of n cells: taken once, by the first fused call
+inline int fused_parity_ensure(lf_router_core &r, bool split, size_t n)
+{
+    if (!r.fused_qr1.p) LF_TRY(r.fused_qr1.alloc(2 * n));
+    if (split && !r.fused_qr2.p) LF_TRY(r.fused_qr2.alloc(2 * n));
+    return LF_OK;
+}
+
+// An ensemble on one router: how many members, and how far apart their rows lie (k_fused_level_steps_members; 0: shared or
+// not there).  For fused_time_major_levels `members` counts the slice of one launch.
+struct fused_member_strides {
+    int members;
+    int64_t member, side, lake, res, forcing;
+};
+
+// The time-major schedule over levels [level0, level0 + nlevels), on a history that is there (F.nsteps > 1): one launch of
+// the level kernel per level that has cells and, with structures in the loop (tm: their site cache, its feed buffer grown
+// by the caller), one more behind it on a level that holds sites; F.linked is the cache's cell flags meanwhile.  mem: the
+// members of an ensemble slice as the second grid dimension (k_fused_level_steps_members; single domain only), null: a
+// single call.  Fills F's time-major fields and adds its launches to `launches`; the caller asks hipGetLastError.
+template <bool DIST>
+void fused_time_major_levels(lf_router_core &r, fused_args &F, int level0, int nlevels, const fused_site_cache *tm,
+                             const fused_member_strides *mem, hipStream_t s, int64_t &launches)
+{
+    const bool split = F.S.split != 0, all35 = r.fused && F.S.Beta == 0.6; // otherwise: run-time flags and OCML pow
+    F.level0 = level0;
+    F.nlevels = nlevels;
+    F.hist1 = r.fused_hist1.p;
+    F.hist2 = r.fused_hist2.p;
+    if (tm) {
+        F.tm_feed = tm->feed.p;
+        F.tm_nfeed = (int)tm->nfeed;
+        F.tm_slot = tm->slot.p;
+        F.tm_site_ptr = tm->site_ptr.p;
+        F.tm_site = tm->site.p;
+    }
+    const uint8_t *const linked = F.linked;
+    if (tm && tm->flags.p) F.linked = tm->flags.p; // 1: link, 2: site cell
+    // st: 0 without structures, 1 the cells and 2 the sites of level k with them (the kernels' STRUCT)
+    auto launch = [&](auto st, int k, int64_t lanes) {
+        pick_flags(split, all35, [&](auto sp, auto a35) {
+            if constexpr (!DIST) {
+                if (mem) {
+                    hipLaunchKernelGGL((k_fused_level_steps_members<sp, a35, st>), dim3(blocks_for(lanes), (unsigned)mem->members),
+                                       dim3(kBlock), 0, s, F, k, (long long)mem->member, (long long)mem->side, (long long)mem->lake,
+                                       (long long)mem->res, (long long)mem->forcing);
+                    return;
+                }
+            }
+            hipLaunchKernelGGL((k_fused_level_steps<sp, a35, DIST, st>), dim3(blocks_for(lanes)), dim3(kBlock), 0, s, F, k);
+        });
+        ++launches;
+    };
+    for (int k = level0; k < level0 + nlevels; ++k) {
+        const int64_t w = r.h_level_start[k + 1] - r.h_level_start[k];
+        if (w <= 0) continue;
+        if constexpr (!DIST) {
+            if (tm) {
+                launch(std::integral_constant<int, 1>(), k, w);
+                // the site cells of the level, each with its lake or reservoir
+                const int64_t ns = tm->level_ptr.empty() ? 0 : tm->level_ptr[k + 1] - tm->level_ptr[k];
+                if (ns > 0) launch(std::integral_constant<int, 2>(), k, ns);
+                continue;
+            }
+        }
+        launch(std::integral_constant<int, 0>(), k, w);
+    }
+    F.linked = linked;
+}
+
+// The wavefront over levels [level0, level0 + nlevels) -- and, if nblocks >= 0, their level blocks [b0, b0 + nblocks) of
+// r.fplan -- for F.nsteps sub-steps; fills F's wave fields and adds its launches to `launches`.  Of the three schedules the
+// first that applies runs:
+//   time-major   (time_major: the caller's precondition; fused_time_major_ready) fused_time_major_levels, with structures
+//                in the loop on tm, their site cache, whose feed buffer is grown here: a refusal is the call's error;
+//   level blocks (nblocks >= 0, F.nsteps <= kMaxPackedSteps) per wave time t: cones(ncones) launches the multi-level
+//                blocks through a cone kernel on a packed grid of ncones workgroups, levels(grid) the single levels
+//                through k_fused_substeps (F.use_lvl);
+//   levels       per wave time t: levels(grid), level t - s for sub-step s.
+// sites(blocks, lo, hi) runs first at every wave time t, with the window [lo, hi] of the level blocks (blocks = true) or
+// levels in flight, counted from b0 / level0.  r.last_fused_form tells which of the three ran.
 template <bool DIST, class Cones, class Levels, class Sites>
 int fused_wavefront(lf_router_core &r, fused_args &F, int level0, int nlevels, int b0, int nblocks, bool time_major, hipStream_t s,
                     int64_t &launches, Cones &&cones, Levels &&levels, Sites &&sites, const fused_site_cache *tm = nullptr)
 {
     const int nsteps = F.nsteps;
-    const bool split = F.S.split != 0, all35 = r.fused && F.S.Beta == 0.6; // otherwise: run-time flags and OCML pow
     auto width = [&](int k) { return r.h_level_start[k + 1] - r.h_level_start[k]; };
-    F.level0 = level0;
-    F.nlevels = nlevels;
     // ---- few, wide levels: level after level, every level through all its sub-steps (k_fused_level_steps) ----------------
-    if (time_major && fused_time_major_ready(r, level0, nlevels, nsteps, split)) {
-        F.hist1 = r.fused_hist1.p;
-        F.hist2 = r.fused_hist2.p;
-        if (tm) {
-            const size_t need = (size_t)(nsteps + 1) * (size_t)tm->nfeed;
-            if (tm->feed.n < need) LF_TRY(tm->feed.grow(need));
-            F.tm_feed = tm->feed.p;
-            F.tm_nfeed = (int)tm->nfeed;
-            F.tm_slot = tm->slot.p;
-            F.tm_site_ptr = tm->site_ptr.p;
-            F.tm_site = tm->site.p;
-        }
-        const uint8_t *const linked = F.linked;
-        if (tm && tm->flags.p) F.linked = tm->flags.p;
-        for (int k = level0; k < level0 + nlevels; ++k) {
-            const int64_t w = width(k);
-            if (w <= 0) continue;
-            pick_flags(split, all35, [&](auto sp, auto a35) {
-                if constexpr (!DIST) {
-                    if (tm) {
-                        hipLaunchKernelGGL((k_fused_level_steps<sp, a35, false, 1>), dim3(blocks_for(w)), dim3(kBlock), 0, s, F, k);
-                        return;
-                    }
-                }
-                hipLaunchKernelGGL((k_fused_level_steps<sp, a35, DIST>), dim3(blocks_for(w)), dim3(kBlock), 0, s, F, k);
-            });
-            ++launches;
-            if constexpr (!DIST) {
-                const int64_t ns = tm && !tm->level_ptr.empty() ? tm->level_ptr[k + 1] - tm->level_ptr[k] : 0;
-                if (ns > 0) { // the site cells of the level, each with its lake or reservoir
-                    pick_flags(split, all35, [&](auto sp, auto a35) {
-                        hipLaunchKernelGGL((k_fused_level_steps<sp, a35, false, 2>), dim3(blocks_for(ns)), dim3(kBlock), 0, s, F, k);
-                    });
-                    ++launches;
-                }
-            }
-        }
-        F.linked = linked;
+    if (time_major && fused_time_major_ready(r, level0, nlevels, nsteps, F.S.split != 0)) {
+        const size_t need = tm ? (size_t)(nsteps + 1) * (size_t)tm->nfeed : 0;
+        if (tm && tm->feed.n < need) LF_TRY(tm->feed.grow(need));
+        fused_time_major_levels<DIST>(r, F, level0, nlevels, tm, nullptr, s, launches);
         r.last_fused_form = 1;
         LF_HIP(hipGetLastError());
         return LF_OK;
     }
+    F.level0 = level0;
+    F.nlevels = nlevels;
     // grid of a level-kernel launch whose blocks, packed by sub-step, are F.blk_start[0 .. nsteps]: the packed 1-D grid
     // only where it saves at least half of the blocks of the 2-D one sized by the widest level -- finding its sub-step
     // costs a block ~1.7 us (24 scalar kernarg loads), which shows on latency-bound launches (deep 5000^2: 65.2 vs 56.7 ms

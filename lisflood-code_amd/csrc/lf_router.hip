@@ -1222,8 +1222,34 @@ void fused_set_stats(lf_router *r, int64_t launches) // what lf_router_last_laun
     r->last_stats[3] = r->NL;
 }
 
+// Structures in the loop: I = the caller's block `in` (an ensemble's: member 0's) as the kernels read it, its site lists
+// checked and planned once per set of lists (r->sites).  sc: the site cache of the call -- r->sites, or an empty one for a
+// call without structures (in null, I untouched) or without a site: the schedules as with sites, none of them found.
+int fused_inloop_of(lf_router *r, const lf_substep_args &a, const lf_inloop_args *in, lf_inloop_args &I, hipStream_t s,
+                    const fused_site_cache *&sc)
+{
+    static const fused_site_cache no_sites;
+    sc = &no_sites;
+    if (!in) return LF_OK;
+    I = *in;
+    if (I.n_lakes <= 0) {
+        I.n_lakes = 0;
+        I.QLakeOutM3Dt = nullptr;
+    }
+    if (I.n_res <= 0) {
+        I.n_res = 0;
+        I.QResOutM3Dt = nullptr;
+    }
+    if (!I.ToChanM3RunoffDt || !I.SideflowChanM3 || I.N != r->N)
+        return lf_set_error(LF_E_INVALID, "lf_inloop_args: ToChanM3RunoffDt, SideflowChanM3 and N = num_pixels are needed");
+    I.ChanQ = a.ChanQ;
+    LF_TRY(r->sites.ensure(r->N, r->h_level_start, r->linked.p, I, s));
+    if (I.n_lakes + I.n_res > 0) sc = &r->sites;
+    return LF_OK;
+}
+
 // A fused call on the single domain: check, sites, flags, pick the schedule, run.
-// flags_ready: see fused_statics_flags (fused_members_impl)
+// flags_ready: see fused_statics_flags (fused_ensemble_impl)
 int fused_impl(lf_router *r, const lf_substep_args *a, int nsteps, int64_t sideflow_stride, const lf_inloop_args *in,
                int msteps = 0, int64_t side_mstride = 0, bool flags_ready = false)
 {
@@ -1237,34 +1263,16 @@ int fused_impl(lf_router *r, const lf_substep_args *a, int nsteps, int64_t sidef
     LF_HIP(hipSetDevice(r->device));
     const int64_t n = r->N;
     if (n == 0) return LF_OK;
-    if (!r->fused_qr1.p) LF_TRY(r->fused_qr1.alloc(2 * n));
-    if (a->split && !r->fused_qr2.p) LF_TRY(r->fused_qr2.alloc(2 * n));
+    LF_TRY(fused_parity_ensure(*r, a->split != 0, (size_t)n));
     fused_args F = fused_args_of(*r, *a, nsteps, msteps, sideflow_stride, side_mstride);
     F.linked = r->linked.p;
     F.level_nlinked = r->level_nlinked.p;
     F.fb_lvl2blk = r->fplan_dev.lvl2blk.p;
     hipStream_t s = r->ctx->stream;
-    // ---- structures: the site lists, checked and planned once per set of lists (r->sites) ---------------------------------
-    int64_t nsites = 0;
-    if (in) {
-        F.I = *in;
-        lf_inloop_args &I = F.I;
-        if (I.n_lakes <= 0) {
-            I.n_lakes = 0;
-            I.QLakeOutM3Dt = nullptr;
-        }
-        if (I.n_res <= 0) {
-            I.n_res = 0;
-            I.QResOutM3Dt = nullptr;
-        }
-        if (!I.ToChanM3RunoffDt || !I.SideflowChanM3 || I.N != n)
-            return lf_set_error(LF_E_INVALID, "lf_inloop_args: ToChanM3RunoffDt, SideflowChanM3 and N = num_pixels are needed");
-        I.ChanQ = a->ChanQ;
-        nsites = I.n_lakes + I.n_res;
-        LF_TRY(r->sites.ensure(n, r->h_level_start, r->linked.p, I, s));
-    }
-    const fused_site_cache no_sites; // (a call with structures and no site: the schedules as with sites, none of them found)
-    const fused_site_cache &sc = nsites > 0 ? r->sites : no_sites;
+    const fused_site_cache *sites_of = nullptr;
+    LF_TRY(fused_inloop_of(r, *a, in, F.I, s, sites_of));
+    const fused_site_cache &sc = *sites_of;
+    const int64_t nsites = F.I.n_lakes + F.I.n_res;
     F.site_level = sc.site_level.p;
     // time-major: without structures on a graph without links; with them when the site plan applies (no site: nothing to plan)
     const bool time_major = in ? nsites == 0 || sc.applies : !F.linked;
@@ -1360,7 +1368,8 @@ extern "C" int lf_routing_substeps_fused_structures(lf_router *r, const lf_subst
 // Where the time-major form applies the members are a second grid dimension of its level kernel
 // (k_fused_level_steps_members), slice by slice: a slice is as many members as the history [slice][nsteps][N] has room
 // for inside its budget.  Otherwise the members run one after the other through the single-member schedule -- correct and
-// bit-identical, with no gain but the flag passes, which run once.
+// bit-identical, with no gain but the flag passes, which run once.  Both calls, plain and with structures in the loop, are
+// one implementation (fused_ensemble_impl) behind one set of refusals (fused_members_check).
 // ================================================================================================
 extern "C" int64_t lf_fused_members_slice(int members, int64_t n, int nsteps, int split, int64_t budget_bytes, int cap)
 {
@@ -1395,67 +1404,6 @@ lf_substep_args member_args(const lf_substep_args &a, int64_t m, int64_t member_
     return b;
 }
 
-int fused_members_impl(lf_router *r, const lf_substep_args *a, int nsteps, int64_t sideflow_stride, int members,
-                       int64_t member_stride, int64_t side_member_stride)
-{
-    LF_HIP(hipSetDevice(r->device));
-    const int64_t n = r->N;
-    const int NL = (int)r->NL;
-    const bool split = a->split != 0;
-    // ---- does the member form of the time-major schedule apply, and on slices of how many members? -------------------
-    int64_t slice = 0;
-    {
-        // the single call's rule (fused_time_major_ready) with the lanes of a launch counted over the members
-        const bool want = fused_time_major_wanted(NL, (int64_t)members * n);
-        size_t budget = 0;
-        if (want && nsteps > 1 && lf_history_budget(r->fused_hist1, r->fused_hist2, budget)) {
-            const char *c = std::getenv("LF_FUSED_MEMBERS_SLICE"); // A/B switch, read per call
-            slice = lf_fused_members_slice(members, n, nsteps, split, (int64_t)std::min<size_t>(budget, INT64_MAX),
-                                           c ? std::atoi(c) : 0);
-            // (the size was cut to the budget first, so nothing is refused for its size -- and a history that still does not
-            // come is not remembered in r->fused_hist_refused, which belongs to the single call's own, smaller, request)
-            size_t refused = SIZE_MAX;
-            if (slice > 0 && !lf_history_ensure(r->fused_hist1, r->fused_hist2, refused, (size_t)slice * nsteps * (size_t)n, split))
-                slice = 0;
-        }
-    }
-    int64_t launches = 0;
-    if (slice == 0) { // member after member through the single-member schedule
-        for (int m = 0; m < members; ++m) {
-            const lf_substep_args b = member_args(*a, m, member_stride, side_member_stride);
-            LF_TRY(fused_impl(r, &b, nsteps, sideflow_stride, nullptr, 0, 0, m > 0));
-            launches += r->last_stats[0];
-        }
-    } else {
-        if (!r->fused_qr1.p) LF_TRY(r->fused_qr1.alloc(2 * n)); // (as fused_impl leaves a router: other forms find them)
-        if (split && !r->fused_qr2.p) LF_TRY(r->fused_qr2.alloc(2 * n));
-        fused_args F = fused_args_of(*r, *a, nsteps, nsteps, sideflow_stride, 0);
-        hipStream_t s = r->ctx->stream;
-        LF_TRY(fused_statics_flags(*r, F, false, false, false, s, launches)); // statics only: once for all members
-        F.hist1 = r->fused_hist1.p;
-        F.hist2 = r->fused_hist2.p;
-        F.nlevels = NL;
-        const bool all35 = r->fused && a->Beta == 0.6;
-        for (int64_t m0 = 0; m0 < members; m0 += slice) {
-            const int64_t cnt = std::min<int64_t>(slice, members - m0);
-            F.S = member_args(*a, m0, member_stride, side_member_stride);
-            for (int k = 0; k < NL; ++k) {
-                const int64_t w = r->h_level_start[k + 1] - r->h_level_start[k];
-                if (w <= 0) continue;
-                pick_flags(split, all35, [&](auto sp, auto a35) {
-                    hipLaunchKernelGGL((k_fused_level_steps_members<sp, a35>), dim3(blocks_for(w), (unsigned)cnt), dim3(kBlock), 0, s,
-                                       F, k, (long long)member_stride, (long long)side_member_stride, 0ll, 0ll, 0ll);
-                });
-                ++launches;
-            }
-        }
-        r->last_fused_form = 1;
-        LF_HIP(hipGetLastError());
-    }
-    fused_set_stats(r, launches);
-    return LF_OK;
-}
-
 // `in` with every per-member row moved m members on: the dense [N] rows by member_stride, the site-state rows by the site
 // strides, the forcing rows by forcing_stride (0: member 0's for all); site lists, site parameters, UpTrans and the scalars
 // are shared, and a null pointer (an option switched off) stays null -- as k_fused_level_steps_members<.., STRUCT> moves them
@@ -1477,111 +1425,120 @@ lf_inloop_args member_inloop(const lf_inloop_args &in, int64_t m, int64_t member
     return b;
 }
 
-// The ensemble call with lakes, reservoirs, inflow hydrographs and transmission loss in the loop
-// (lf_routing_substeps_fused_structures_members; its arguments are checked there).  The site lists are shared by the
-// members: checked and planned once per call.  Where the time-major form applies to the ensemble -- the site plan applies (or
-// there is no site), more than one sub-step, the width rule over members * N lanes, room for a slice's history and feed
-// buffers -- the members of a slice are the second grid dimension of k_fused_level_steps_members<.., 1> (one launch per
-// level) and <.., 2> (one more behind it on a level that holds sites).  Otherwise member after member through fused_impl.
-int fused_structures_members_impl(lf_router *r, const lf_substep_args *a, const lf_inloop_args *in, int nsteps, int members,
-                                  int64_t member_stride, int64_t lake_stride, int64_t res_stride, int64_t forcing_stride)
+// What both ensemble calls refuse, in this order; structures: the call with lakes, reservoirs, inflow hydrographs and
+// transmission loss in the loop (needs `in`, has no sideflow strides), otherwise the plain one (no site and forcing strides)
+int fused_members_check(const lf_router *r, const lf_substep_args *a, const lf_inloop_args *in, bool structures, int nsteps,
+                        int64_t sideflow_stride, const fused_member_strides &M)
+{
+    // ---- what needs no router, and so no device ----
+    if (M.members < 1) return lf_set_error(LF_E_INVALID, "members must be at least 1 (got %d)", M.members);
+    if (M.member < 0)
+        return lf_set_error(LF_E_INVALID, "member_stride %lld is less than the router's number of cells", (long long)M.member);
+    if (M.side < 0)
+        return lf_set_error(LF_E_INVALID, "sideflow_member_stride %lld is neither 0 nor a whole member's sideflow rows",
+                            (long long)M.side);
+    if (M.lake < 0)
+        return lf_set_error(LF_E_INVALID, "lake_member_stride %lld is less than the number of lakes", (long long)M.lake);
+    if (M.res < 0)
+        return lf_set_error(LF_E_INVALID, "res_member_stride %lld is less than the number of reservoirs", (long long)M.res);
+    if (M.forcing < 0)
+        return lf_set_error(LF_E_INVALID, "forcing_member_stride %lld is neither 0 nor at least the router's number of cells",
+                            (long long)M.forcing);
+    if (!r || !a || (structures && !in)) return lf_set_error(LF_E_INVALID, "null argument");
+    if (nsteps < 1)
+        return structures ? lf_set_error(LF_E_INVALID, "nsteps must be at least 1 (got %d)", nsteps)
+                          : lf_set_error(LF_E_INVALID, "bad argument");
+    // ---- against the router's and the lists' sizes: host fields, still no device ----
+    if (M.member < r->N)
+        return lf_set_error(LF_E_INVALID, "member_stride %lld is less than the router's number of cells (%lld)",
+                            (long long)M.member, (long long)r->N);
+    if (in && in->n_lakes > 0 && M.lake < in->n_lakes)
+        return lf_set_error(LF_E_INVALID, "lake_member_stride %lld is less than the number of lakes (%lld)", (long long)M.lake,
+                            (long long)in->n_lakes);
+    if (in && in->n_res > 0 && M.res < in->n_res)
+        return lf_set_error(LF_E_INVALID, "res_member_stride %lld is less than the number of reservoirs (%lld)", (long long)M.res,
+                            (long long)in->n_res);
+    if (M.forcing != 0 && M.forcing < r->N)
+        return lf_set_error(LF_E_INVALID, "forcing_member_stride %lld is neither 0 nor at least the router's number of cells (%lld)",
+                            (long long)M.forcing, (long long)r->N);
+    LF_TRY(fused_check_call(*r, *a, sideflow_stride, "fused sub-step wavefront needs"));
+    const int64_t side_rows = sideflow_stride == 0 ? r->N : (int64_t)nsteps * r->N;
+    if (M.side != 0 && M.side < side_rows)
+        return lf_set_error(LF_E_INVALID, "sideflow_member_stride %lld is neither 0 nor a whole member's sideflow rows (%lld)",
+                            (long long)M.side, (long long)side_rows);
+    if (!structures && r->linked.p)
+        return lf_set_error(LF_E_INVALID, "a router on a graph with structure links runs no ensemble through the sub-step loop "
+                                          "(lf_routing_substeps_fused_members)");
+    return LF_OK;
+}
+
+// An ensemble call of M.members > 1 members on a router with cells, its arguments checked (fused_members_check); in: the
+// in-loop block of the call with structures (member 0's; the site lists are shared by the members: checked and planned once
+// per call), null: the plain call.  Where the time-major form applies to the ensemble -- more than one sub-step, the single
+// call's width rule with the lanes of a launch counted over the members (members * N), room for a slice's history and, with
+// structures, a site plan that applies (or no site) and room for a slice's feed buffers -- the members of a slice are the
+// second grid dimension of the level kernel (fused_time_major_levels).  Otherwise member after member through fused_impl.
+int fused_ensemble_impl(lf_router *r, const lf_substep_args *a, const lf_inloop_args *in, int nsteps, int64_t sideflow_stride,
+                        const fused_member_strides &M)
 {
     LF_HIP(hipSetDevice(r->device));
     const int64_t n = r->N;
     const int NL = (int)r->NL;
     const bool split = a->split != 0;
     hipStream_t s = r->ctx->stream;
-    lf_inloop_args I = *in; // member 0's block as fused_impl reads it
-    if (I.n_lakes <= 0) {
-        I.n_lakes = 0;
-        I.QLakeOutM3Dt = nullptr;
-    }
-    if (I.n_res <= 0) {
-        I.n_res = 0;
-        I.QResOutM3Dt = nullptr;
-    }
-    if (!I.ToChanM3RunoffDt || !I.SideflowChanM3 || I.N != n)
-        return lf_set_error(LF_E_INVALID, "lf_inloop_args: ToChanM3RunoffDt, SideflowChanM3 and N = num_pixels are needed");
-    I.ChanQ = a->ChanQ;
-    const int64_t nsites = I.n_lakes + I.n_res;
-    LF_TRY(r->sites.ensure(n, r->h_level_start, r->linked.p, I, s)); // shared lists: once for all members
-    const fused_site_cache no_sites;
-    const fused_site_cache &sc = nsites > 0 ? r->sites : no_sites;
-    // ---- does the member form apply, and on slices of how many members? (as fused_members_impl) ------------------------------
+    lf_inloop_args I = {};
+    const fused_site_cache *sc = nullptr;
+    LF_TRY(fused_inloop_of(r, *a, in, I, s, sc));
+    // ---- does the member form of the time-major schedule apply, and on slices of how many members? -------------------
     int64_t slice = 0;
     size_t budget = 0;
-    if ((nsites == 0 || sc.applies) && nsteps > 1 && fused_time_major_wanted(NL, (int64_t)members * n) &&
+    if (fused_time_major_wanted(NL, (int64_t)M.members * n) && nsteps > 1 && (I.n_lakes + I.n_res == 0 || sc->applies) &&
         lf_history_budget(r->fused_hist1, r->fused_hist2, budget)) {
         const char *c = std::getenv("LF_FUSED_MEMBERS_SLICE"); // A/B switch, read per call
-        slice = lf_fused_members_slice(members, n, nsteps, split, (int64_t)std::min<size_t>(budget, INT64_MAX), c ? std::atoi(c) : 0);
-        // (a history or a feed buffer that does not come is not remembered in r->fused_hist_refused, which belongs to the
-        // single call's own, smaller, request: the members then run one after the other, each with that request)
+        slice = lf_fused_members_slice(M.members, n, nsteps, split, (int64_t)std::min<size_t>(budget, INT64_MAX), c ? std::atoi(c) : 0);
+        // (the size was cut to the budget first, so nothing is refused for its size -- and a history or a feed buffer that
+        // still does not come is not remembered in r->fused_hist_refused, which belongs to the single call's own, smaller,
+        // request: the members then run one after the other, each with that request)
         size_t refused = SIZE_MAX;
         if (slice > 0 && !lf_history_ensure(r->fused_hist1, r->fused_hist2, refused, (size_t)slice * nsteps * (size_t)n, split))
             slice = 0;
-        const size_t feed = (size_t)slice * (size_t)(nsteps + 1) * (size_t)sc.nfeed;
-        if (slice > 0 && sc.feed.n < feed && sc.feed.grow(feed) != LF_OK) slice = 0;
+        const size_t feed = (size_t)slice * (size_t)(nsteps + 1) * (size_t)sc->nfeed;
+        if (in && slice > 0 && sc->feed.n < feed && sc->feed.grow(feed) != LF_OK) slice = 0;
     }
     int64_t launches = 0;
     if (slice == 0) {
         // Member after member through the single call's schedule.  What runs once: the site checks and the plan (above; every
-        // member's call finds the cache by the shared list pointers) and the flag pass over the statics (fused_check_derived
-        // reads the static vectors and the router's tables only: flags_ready from the second member on).  No pass of the call
-        // reads member state -- the inert flags, the one candidate, are never taken with structures in the loop --, so nothing
-        // is repeated per member but the wavefront itself.
-        for (int m = 0; m < members; ++m) {
-            const lf_substep_args b = member_args(*a, m, member_stride, 0);
-            const lf_inloop_args bi = member_inloop(*in, m, member_stride, lake_stride, res_stride, forcing_stride);
-            LF_TRY(fused_impl(r, &b, nsteps, 0, &bi, 0, 0, m > 0));
+        // member's call finds the cache by the shared list pointers) and the flag passes over the statics (flags_ready from
+        // the second member on).  With structures in the loop no pass of the call reads member state -- the inert flags, the
+        // one candidate, are never taken then --, so nothing is repeated per member but the wavefront itself.
+        for (int m = 0; m < M.members; ++m) {
+            const lf_substep_args b = member_args(*a, m, M.member, M.side);
+            const lf_inloop_args bi = in ? member_inloop(*in, m, M.member, M.lake, M.res, M.forcing) : I;
+            LF_TRY(fused_impl(r, &b, nsteps, sideflow_stride, in ? &bi : nullptr, 0, 0, m > 0));
             launches += r->last_stats[0];
         }
-        fused_set_stats(r, launches);
-        return LF_OK;
-    }
-    if (!r->fused_qr1.p) LF_TRY(r->fused_qr1.alloc(2 * n)); // (as fused_impl leaves a router: other forms find them)
-    if (split && !r->fused_qr2.p) LF_TRY(r->fused_qr2.alloc(2 * n));
-    fused_args F = fused_args_of(*r, *a, nsteps, nsteps, 0, 0);
-    F.level_nlinked = r->level_nlinked.p;
-    F.fb_lvl2blk = r->fplan_dev.lvl2blk.p;
-    F.site_level = sc.site_level.p;
-    F.I = I;
-    LF_TRY(fused_statics_flags(*r, F, true, true, false, s, launches)); // (time-major with structures: neither flag is taken)
-    F.hist1 = r->fused_hist1.p;
-    F.hist2 = r->fused_hist2.p;
-    F.nlevels = NL;
-    F.tm_feed = sc.feed.p;
-    F.tm_nfeed = (int)sc.nfeed;
-    F.tm_slot = sc.slot.p;
-    F.tm_site_ptr = sc.site_ptr.p;
-    F.tm_site = sc.site.p;
-    F.linked = sc.flags.p ? sc.flags.p : r->linked.p; // 1: link, 2: site cell
-    const bool all35 = r->fused && a->Beta == 0.6;
-    for (int64_t m0 = 0; m0 < members; m0 += slice) {
-        const unsigned cnt = (unsigned)std::min<int64_t>(slice, members - m0);
-        F.S = member_args(*a, m0, member_stride, 0);
-        F.I = member_inloop(I, m0, member_stride, lake_stride, res_stride, forcing_stride);
-        for (int k = 0; k < NL; ++k) {
-            const int64_t w = r->h_level_start[k + 1] - r->h_level_start[k];
-            if (w <= 0) continue;
-            pick_flags(split, all35, [&](auto sp, auto a35) {
-                hipLaunchKernelGGL((k_fused_level_steps_members<sp, a35, 1>), dim3(blocks_for(w), cnt), dim3(kBlock), 0, s, F, k,
-                                   (long long)member_stride, 0ll, (long long)lake_stride, (long long)res_stride,
-                                   (long long)forcing_stride);
-            });
-            ++launches;
-            const int64_t ns = sc.level_ptr.empty() ? 0 : sc.level_ptr[k + 1] - sc.level_ptr[k];
-            if (ns > 0) { // the site cells of the level, each with its lake or reservoir, member by member on the grid
-                pick_flags(split, all35, [&](auto sp, auto a35) {
-                    hipLaunchKernelGGL((k_fused_level_steps_members<sp, a35, 2>), dim3(blocks_for(ns), cnt), dim3(kBlock), 0, s, F, k,
-                                       (long long)member_stride, 0ll, (long long)lake_stride, (long long)res_stride,
-                                       (long long)forcing_stride);
-                });
-                ++launches;
-            }
+    } else {
+        LF_TRY(fused_parity_ensure(*r, split, (size_t)n)); // (as fused_impl leaves a router: other forms find them)
+        fused_args F = fused_args_of(*r, *a, nsteps, nsteps, sideflow_stride, 0);
+        if (in) {
+            F.linked = r->linked.p; // (fused_time_major_levels: the site plan's cell flags in its place)
+            F.level_nlinked = r->level_nlinked.p;
+            F.fb_lvl2blk = r->fplan_dev.lvl2blk.p;
+            F.site_level = sc->site_level.p;
+            F.I = I;
         }
+        // once for all members -- plain: both flags; time-major with structures: neither is taken
+        LF_TRY(fused_statics_flags(*r, F, in != nullptr, in != nullptr, false, s, launches));
+        fused_member_strides Ms = M;
+        for (int64_t m0 = 0; m0 < M.members; m0 += slice) {
+            Ms.members = (int)std::min<int64_t>(slice, M.members - m0);
+            F.S = member_args(*a, m0, M.member, M.side);
+            if (in) F.I = member_inloop(I, m0, M.member, M.lake, M.res, M.forcing);
+            fused_time_major_levels<false>(*r, F, 0, NL, in ? sc : nullptr, &Ms, s, launches);
+        }
+        r->last_fused_form = 1;
+        LF_HIP(hipGetLastError());
     }
-    r->last_fused_form = 1;
-    LF_HIP(hipGetLastError());
     fused_set_stats(r, launches);
     return LF_OK;
 }
@@ -1593,65 +1550,21 @@ extern "C" int lf_routing_substeps_fused_structures_members(lf_router *r, const 
                                                             int64_t lake_member_stride, int64_t res_member_stride,
                                                             int64_t forcing_member_stride)
 {
-    // ---- what needs no router, and so no device ----
-    if (members < 1) return lf_set_error(LF_E_INVALID, "members must be at least 1 (got %d)", members);
-    if (member_stride < 0)
-        return lf_set_error(LF_E_INVALID, "member_stride %lld is less than the router's number of cells", (long long)member_stride);
-    if (lake_member_stride < 0)
-        return lf_set_error(LF_E_INVALID, "lake_member_stride %lld is less than the number of lakes", (long long)lake_member_stride);
-    if (res_member_stride < 0)
-        return lf_set_error(LF_E_INVALID, "res_member_stride %lld is less than the number of reservoirs",
-                            (long long)res_member_stride);
-    if (forcing_member_stride < 0)
-        return lf_set_error(LF_E_INVALID, "forcing_member_stride %lld is neither 0 nor at least the router's number of cells",
-                            (long long)forcing_member_stride);
-    if (!r || !a || !in) return lf_set_error(LF_E_INVALID, "null argument");
-    if (nsteps < 1) return lf_set_error(LF_E_INVALID, "nsteps must be at least 1 (got %d)", nsteps);
-    // ---- against the router's and the lists' sizes: host fields, still no device ----
-    if (member_stride < r->N)
-        return lf_set_error(LF_E_INVALID, "member_stride %lld is less than the router's number of cells (%lld)",
-                            (long long)member_stride, (long long)r->N);
-    if (in->n_lakes > 0 && lake_member_stride < in->n_lakes)
-        return lf_set_error(LF_E_INVALID, "lake_member_stride %lld is less than the number of lakes (%lld)",
-                            (long long)lake_member_stride, (long long)in->n_lakes);
-    if (in->n_res > 0 && res_member_stride < in->n_res)
-        return lf_set_error(LF_E_INVALID, "res_member_stride %lld is less than the number of reservoirs (%lld)",
-                            (long long)res_member_stride, (long long)in->n_res);
-    if (forcing_member_stride != 0 && forcing_member_stride < r->N)
-        return lf_set_error(LF_E_INVALID, "forcing_member_stride %lld is neither 0 nor at least the router's number of cells (%lld)",
-                            (long long)forcing_member_stride, (long long)r->N);
-    LF_TRY(fused_check_call(*r, *a, 0, "fused sub-step wavefront needs"));
+    const fused_member_strides M = {members, member_stride, 0, lake_member_stride, res_member_stride, forcing_member_stride};
+    LF_TRY(fused_members_check(r, a, in, true, nsteps, 0, M));
     if (members == 1) return fused_impl(r, a, nsteps, 0, in);
     if (r->N == 0) return LF_OK;
-    return fused_structures_members_impl(r, a, in, nsteps, members, member_stride, lake_member_stride, res_member_stride,
-                                         forcing_member_stride);
+    return fused_ensemble_impl(r, a, in, nsteps, 0, M);
 }
 
 extern "C" int lf_routing_substeps_fused_members(lf_router *r, const lf_substep_args *a, int nsteps, int64_t sideflow_stride,
                                                  int members, int64_t member_stride, int64_t sideflow_member_stride)
 {
-    if (members < 1) return lf_set_error(LF_E_INVALID, "members must be at least 1 (got %d)", members);
-    if (member_stride < 0)
-        return lf_set_error(LF_E_INVALID, "member_stride %lld is less than the router's number of cells", (long long)member_stride);
-    if (sideflow_member_stride < 0)
-        return lf_set_error(LF_E_INVALID, "sideflow_member_stride %lld is neither 0 nor a whole member's sideflow rows",
-                            (long long)sideflow_member_stride);
-    if (!r || !a) return lf_set_error(LF_E_INVALID, "null argument");
-    if (nsteps < 1) return lf_set_error(LF_E_INVALID, "bad argument");
-    if (member_stride < r->N)
-        return lf_set_error(LF_E_INVALID, "member_stride %lld is less than the router's number of cells (%lld)",
-                            (long long)member_stride, (long long)r->N);
-    LF_TRY(fused_check_call(*r, *a, sideflow_stride, "fused sub-step wavefront needs"));
-    const int64_t side_rows = sideflow_stride == 0 ? r->N : (int64_t)nsteps * r->N;
-    if (sideflow_member_stride != 0 && sideflow_member_stride < side_rows)
-        return lf_set_error(LF_E_INVALID, "sideflow_member_stride %lld is neither 0 nor a whole member's sideflow rows (%lld)",
-                            (long long)sideflow_member_stride, (long long)side_rows);
-    if (r->linked.p)
-        return lf_set_error(LF_E_INVALID, "a router on a graph with structure links runs no ensemble through the sub-step loop "
-                                          "(lf_routing_substeps_fused_members)");
+    const fused_member_strides M = {members, member_stride, sideflow_member_stride, 0, 0, 0};
+    LF_TRY(fused_members_check(r, a, nullptr, false, nsteps, sideflow_stride, M));
     if (members == 1) return fused_impl(r, a, nsteps, sideflow_stride, nullptr);
     if (r->N == 0) return LF_OK;
-    return fused_members_impl(r, a, nsteps, sideflow_stride, members, member_stride, sideflow_member_stride);
+    return fused_ensemble_impl(r, a, nullptr, nsteps, sideflow_stride, M);
 }
 
 // ================================================================================================

@@ -237,6 +237,16 @@ class kinematicWave:
                                  "%d bytes)" % (members, N, stride, need, a.dtype, a.nbytes))
         return members
 
+    @staticmethod
+    def _substep_counts(nsteps, members):
+        """(nsteps, members) of an ensemble sub-step call as ints, at least 1 each"""
+        nsteps, members = int(nsteps), int(members)
+        if members < 1:
+            raise ValueError("members must be at least 1 (got %d)" % members)
+        if nsteps < 1:
+            raise ValueError("nsteps must be at least 1 (got %d)" % nsteps)
+        return nsteps, members
+
     def routing_substeps_members(self, args, nsteps, members, member_stride=None, sideflow_stride=0,
                                  sideflow_member_stride=None):
         """nsteps routing sub-steps of `members` members in one call (lf_routing_substeps_fused_members): `args` is one
@@ -245,11 +255,7 @@ class kinematicWave:
         back -- N with sideflow_stride 0, nsteps * N with sideflow_stride N; 0: every member reads member 0's).  Every member
         ends up as lf_routing_substeps_fused on it alone would leave it; asynchronous.  (Strides the router cannot take are
         the library's to refuse, with its own message.)"""
-        nsteps, members, N = int(nsteps), int(members), self.num_pixels
-        if members < 1:
-            raise ValueError("members must be at least 1 (got %d)" % members)
-        if nsteps < 1:
-            raise ValueError("nsteps must be at least 1 (got %d)" % nsteps)
+        (nsteps, members), N = self._substep_counts(nsteps, members), self.num_pixels
         if int(sideflow_stride) not in (0, N):
             raise ValueError("sideflow_stride must be 0 or %d (got %d)" % (N, int(sideflow_stride)))
         member_stride = N if member_stride is None else int(member_stride)
@@ -267,11 +273,7 @@ class kinematicWave:
         `inloop`), its forcing rows m * forcing_member_stride (default 0: every member reads member 0's); site lists, site
         parameters and statics are shared.  Every member ends up as lf_routing_substeps_fused_structures on it alone would
         leave it; asynchronous.  (Strides the router cannot take are the library's to refuse, with its own message.)"""
-        nsteps, members = int(nsteps), int(members)
-        if members < 1:
-            raise ValueError("members must be at least 1 (got %d)" % members)
-        if nsteps < 1:
-            raise ValueError("nsteps must be at least 1 (got %d)" % nsteps)
+        nsteps, members = self._substep_counts(nsteps, members)
         member_stride = self.num_pixels if member_stride is None else int(member_stride)
         lake_member_stride = max(int(inloop.n_lakes), 0) if lake_member_stride is None else int(lake_member_stride)
         res_member_stride = max(int(inloop.n_res), 0) if res_member_stride is None else int(res_member_stride)

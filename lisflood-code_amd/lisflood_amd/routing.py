@@ -791,6 +791,8 @@ class routingEnsemble:
     site parameters, holds member rows of the dense in-loop vectors ([members, N]) and of the lake / reservoir state
     ([members, n_lakes] / [members, n_res]) beside the routing state, and runs lf_routing_substeps_fused_structures_members."""
 
+    _groups = {}    # (what an ensemble put together without __init__ reads: no in-loop vectors; never written to)
+
     def __init__(self, var, router, members, split_routing=False, member_stride=None, device=0, module=None):
         members = int(members)
         if members < 1:
@@ -804,6 +806,7 @@ class routingEnsemble:
         rows = (members - 1) * self.stride + N                                          # entries of a vector of member rows
         self._side = self._inloop = None
         self._inloop_dev, self._forcing = {}, None
+        self._groups = {}                        # in-loop vector -> (entries of a row, stride, pixel order?): _attach_inloop
         self._module = module                     # (the owner of the shared device vectors lives as long as the ensemble)
         if module is None:
             self.perm = router.graph.layout()[0].astype(np.int64)                      # position -> pixel
@@ -828,7 +831,6 @@ class routingEnsemble:
         a = self._inloop = _InloopArgs.from_buffer_copy(module._inloop)
         self._options = module.options
         self.n_lakes, self.n_res = int(st["lakes"]), int(st["res"])
-        self._groups = {}                        # name -> (entries of a row, stride, pixel order?)
         for k in _INLOOP_DENSE:
             if k == "SideflowChanM3" or k in st["dev"]:
                 self._groups[k] = (N, self.stride, True)
@@ -855,12 +857,17 @@ class routingEnsemble:
         rows[:, :count] = host[:, self.perm] if pixels and permute else host
         self._inloop_dev[name].upload(np.ascontiguousarray(rows.reshape(-1)[:(self.members - 1) * stride + count]), prefix=True)
 
+    def _layout(self, name):
+        """(entries of a member's row, stride, pixel order?) of a state, output or in-loop vector, or ValueError"""
+        if name in self._groups:
+            return self._groups[name]
+        if name not in _STATE + _OUT:
+            raise ValueError("no state or output vector of the routing sub-step is called %r" % (name,))
+        return self.N, self.stride, True
+
     def _member_rows(self, name, host):
         """host [members, N] float64 in pixel order ([members, n_lakes] / [members, n_res] for site state), or ValueError"""
-        groups = getattr(self, "_groups", None) or {}
-        if name not in _STATE + _OUT and name not in groups:
-            raise ValueError("no state or output vector of the routing sub-step is called %r" % (name,))
-        width = groups[name][0] if name in groups else self.N
+        width = self._layout(name)[0]
         if not (isinstance(host, np.ndarray) and host.dtype == np.float64 and host.shape == (self.members, width)):
             raise ValueError("%s must be a float64 [%d, %d] array (members, %s)" %
                              (name, self.members, width, "pixels" if width == self.N else "sites"))
@@ -871,7 +878,7 @@ class routingEnsemble:
         structures attached also the dense in-loop vectors ([members, N]) and the lake / reservoir state
         ([members, n_lakes] / [members, n_res], in the order of LakeIndex / ReservoirIndex)"""
         host = self._member_rows(name, host)
-        if name in (getattr(self, "_groups", None) or {}):
+        if name in self._groups:
             return self._put_rows(name, host)
         rows = np.zeros((self.members, self.stride))
         rows[:, :self.N] = host[:, self.perm]
@@ -879,13 +886,10 @@ class routingEnsemble:
 
     def state(self, name):
         """host[members, N] in pixel order of a state or output vector (site state: [members, sites])"""
-        groups = getattr(self, "_groups", None) or {}
-        if name not in _STATE + _OUT and name not in groups:
-            raise ValueError("no state or output vector of the routing sub-step is called %r" % (name,))
-        count, stride, pixels = groups.get(name, (self.N, self.stride, True))
+        count, stride, pixels = self._layout(name)
         flat = np.zeros(self.members * stride)
         flat[:(self.members - 1) * stride + count] = \
-            (self._inloop_dev[name] if name in groups else self.vectors.dev[name]).download()[:(self.members - 1) * stride + count]
+            (self._inloop_dev[name] if name in self._groups else self.vectors.dev[name]).download()[:(self.members - 1) * stride + count]
         rows = flat.reshape(self.members, stride)[:, :count]
         if not pixels:
             return rows.copy()
