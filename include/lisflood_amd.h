@@ -218,6 +218,21 @@ int lf_router_route_ordered(lf_router *r, double *discharge_ord_dev, const doubl
  * and stride are neither read nor written.  (General exponent: the router's `constant` grows to members * N.) */
 int lf_router_route_ordered_members(lf_router *r, double *discharge_ord_dev, const double *lateral_ord_dev,
                                     int members, int64_t stride, int section);
+/* The same for `count` (1 to 4) routers at once -- the three overland routers of an ensemble: router i sweeps its own
+ * [members][stride] rows discharge_ord_dev[i] / lateral_ord_dev[i].  Routers that lf_router_route_device_multi would sweep
+ * together (same graph and schedule, same device, no links, not profiling) share every launch: one per wide level / narrow
+ * run / level block for all count * members (router, member) units (general exponent: one preparing launch for all units,
+ * each router's `constant` grows to members * N; more units than a grid's second dimension holds: in slices of members).
+ * Other routers get one lf_router_route_ordered_members call each.  Every (router, member) row is bit-identical to
+ * lf_router_route_ordered on that router with that row alone.  count, members and stride are checked before a router or a
+ * device is touched. */
+int lf_router_route_ordered_members_multi(int count, lf_router **routers, double **discharge_ord_dev,
+                                          const double **lateral_ord_dev, int members, int64_t stride, int section);
+/* dst[r * dst_stride + i] = src[r * src_stride + index[i]], i < n, r < rows: lf_gather_device for `rows` rows with one index
+ * table in one launch (each member's ToChanM3RunoffDt from the overland order into the channel router's engine order).
+ * dst_stride >= n; the elements between the rows of dst are not written. */
+int lf_gather_rows_device(int device, int64_t n, const int32_t *index_dev, const double *src_dev, int64_t src_stride,
+                          double *dst_dev, int64_t dst_stride, int rows);
 /* host form: discharge_host[members][N] in PIXEL order updated in place, lateral_host[members][N] */
 int lf_router_route_members_host(lf_router *r, double *discharge_host, const double *lateral_host,
                                  int members, int section);
@@ -511,6 +526,29 @@ int lf_surface_step(lf_router *direct_router, lf_router *other_router, lf_router
  * per-pixel fields once (lf_graph_layout gives the table) -- lisflood_amd.hotpath.HotPathDevice does. */
 int lf_surface_step_ordered(lf_router *direct_router, lf_router *other_router, lf_router *forest_router,
                             const lf_surface_args *a);
+/* lf_surface_step_ordered for an ENSEMBLE, in the convention of lf_land_columns_members_device: `a` is the block of the
+ * single call and names member 0's rows, every vector in the sweep order of the routers' graph.
+ *   shared: SoilFraction, OFAlpha, IsChannel
+ *   per member, m * member_stride elements further on (member_stride >= 3 * N): AvailableWaterForInfiltration, Infiltration,
+ *     SurfaceRunSoil
+ *   per member, m * pixel_member_stride elements further on (pixel_member_stride >= N): every other [N] vector
+ *   scratch: 3 * members * pixel_member_stride elements, laid out [3][members][pixel_member_stride] by the call -- the three
+ *     lateral-inflow row sets then have the stride of the discharge rows
+ * Elements between rows are neither read nor written.  The two element-wise kernels run once for all (block of 256 pixels,
+ * member) units, block-major and dealt to the workgroups as lf_land_members_unit says; between them ONE
+ * lf_router_route_ordered_members_multi call sweeps the three routers.  Every member's result is bit-identical to
+ * lf_surface_step_ordered on that member alone; members == 1 IS that call.  LF_SURFACE_MEMBERS=0, read per call: member
+ * after member through the single call (the same bits).  members < 1, a stride too small and members * blocks beyond the
+ * 32-bit range are refused with LF_E_INVALID before a device is touched. */
+int lf_surface_step_members(lf_router *direct_router, lf_router *other_router, lf_router *forest_router,
+                            const lf_surface_args *a, int members, int64_t member_stride, int64_t pixel_member_stride);
+/* the form the last pixel-aggregates (stage 0) / surface-step (stage 1) call on the device took: 0 none yet, 1 single call,
+ * 2 members in one launch, 3 member after member (as lf_soil_last_form) */
+int lf_module_last_form(int device, int stage);
+/* (pixel block, member) of launch position `position` of the element-wise member kernels (the per-pixel aggregates and the two
+ * kernels of the overland step) over nblocks * members units, when the workgroup at position 0 has linear id 0: the order of
+ * lf_land_members_unit (host only: the function the kernels call, for the tests) */
+int lf_module_members_unit(int64_t nblocks, int members, int64_t position, int64_t *block, int *member);
 
 /* In-loop structures of routing.dynamic (routing.py:441-478): lakes (lakes.py:199-297, Modified Puls), reservoirs
  * (reservoir.py:173-322), inflow hydrographs (inflow.py:129-147), transmission loss (transmission.py:67-89) and
@@ -621,6 +659,22 @@ typedef struct lf_pixel_args {
     int64_t N;
 } lf_pixel_args;
 int lf_pixel_aggregates_device(int device, const lf_pixel_args *a);
+/* The per-pixel aggregates of an ENSEMBLE in one launch, in the convention of lf_land_columns_members_device: `a` is the
+ * block of the single call and names member 0's rows.
+ *   shared: SoilFraction, SoilDepthTotal, SMaxSealed, DirectRunoffFraction, WaterFraction, LowerZoneK, LZThreshold, GwLossStep
+ *   per member, m * member_stride elements further on (member_stride >= 3 * N, the land ensemble's stride): every other [3,N]
+ *     input, and Theta
+ *   per member, m * pixel_member_stride elements further on (pixel_member_stride >= N): every [N] state and output
+ *   forcing, m * forcing_member_stride elements further on (0: shared, otherwise >= N): Rain, SnowMelt, EWRef
+ * Elements between rows are neither read nor written; NULL (not reported) maps work as in the single call, for every member.
+ * The unit of work is (block of 256 pixels, member): one launch covers all units, block-major and dealt to the workgroups as
+ * lf_land_members_unit says, so the members of a block run next to each other on one XCD whose L2 holds the block's 13
+ * static values per pixel.  Every member's result is bit-identical to the single call on that member alone; members == 1 IS
+ * the single call.  LF_PIXEL_MEMBERS=0, read per call: member after member through the single kernel (the same bits).
+ * The checks of the single call apply; members < 1, a stride too small, 0 < forcing_member_stride < N and members * blocks
+ * beyond the 32-bit range are refused with LF_E_INVALID before a device is touched. */
+int lf_pixel_aggregates_members_device(int device, const lf_pixel_args *a, int members, int64_t member_stride,
+                                       int64_t pixel_member_stride, int64_t forcing_member_stride);
 
 /* host-buffer forms (drop-in for the numba kernels; PCIe-inclusive) */
 int lf_interception_host(int device, const lf_interception_args *a);

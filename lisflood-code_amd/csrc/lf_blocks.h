@@ -33,6 +33,21 @@ __host__ __device__ inline int lf_xcd_contiguous(int i, int n, unsigned linear_i
     return before + ((i - r_mine) >> 3);
 }
 
+// The ensemble launches whose unit of work is (tile of 256 columns or pixels, member) -- the land surface (lf_soil.hip) and
+// the element-wise member kernels (lf_modules.hip) -- order their units tile-major, u = tile * members + member, and deal
+// them to the workgroups with lf_xcd_contiguous: the members of a tile run next to each other on one XCD.
+// -> (tile, member) of the workgroup at `position` of the launch whose linear id is `linear_id`
+#ifndef LF_LAND_MEMBERS_XCD
+#define LF_LAND_MEMBERS_XCD 1
+#endif
+__host__ __device__ inline void land_members_unit(unsigned int units, unsigned int members, unsigned int position,
+                                                  unsigned int linear_id, unsigned int &tile, unsigned int &member)
+{
+    const unsigned int u = LF_LAND_MEMBERS_XCD ? (unsigned int)lf_xcd_contiguous((int)position, (int)units, linear_id) : position;
+    tile = u / members;
+    member = u - tile * members;
+}
+
 // Runs of consecutive levels [k_lo, k_hi) of at most `wide` cells are cut into blocks of up to lmax levels; a wider level
 // is a block of its own.  A block is cut into CONES: chunks of its last level, as long as possible with no level of the
 // cone wider than `max_cone` cells, each with the range of every earlier level that drains into it (`child(pos)` = first

@@ -46,6 +46,7 @@ struct lf_device_ctx {
     void *soil_ws = nullptr; // lists and straggler records of the soil call (lf_soil.hip: soil_ws_layout)
     size_t soil_ws_bytes = 0, soil_ntiles = 0;
     int soil_last_form = 0; // of the last soil / land-surface call: lf_soil_last_form
+    int module_last_form[2] = {0, 0}; // of the last pixel-aggregates / surface-step call: lf_module_last_form
     // upload stream for double-buffered inputs (lf_upload_*): copies of the NEXT step's forcing overlap the kernels of
     // the current one; per buffer set an event "copy finished" and an event "last kernel reading the set finished"
     hipStream_t copy_stream = nullptr;

@@ -7,6 +7,7 @@
 #include <cstdlib>
 
 #include "lf_common.h"
+#include "lf_blocks.h"
 #include "lf_canopy.h"
 #include "lf_math.h"
 #include "lf_structures.h"
@@ -53,11 +54,10 @@ __global__ void __launch_bounds__(kBlock) k_scale_rows(long long V, long long N,
 }
 
 // surface_routing.py:122-149: runoff components and the three sideflows (scratch rows: Direct, Other, Forest)
-__global__ void __launch_bounds__(kBlock) k_surface_pre(lf_surface_args A)
+// (the body of a pixel; srow: elements between the three rows of A.scratch -- N, or members * stride in the member form)
+__device__ __forceinline__ void surface_pre_pixel(const lf_surface_args &A, long long p, long long srow)
 {
-    const long long p = (long long)blockIdx.x * kBlock + threadIdx.x;
     const long long N = A.N;
-    if (p >= N) return;
     double srs[3];
 #pragma unroll
     for (int l = 0; l < 3; ++l) { // one prescribed fraction per land use: the np.sum over it is that single term
@@ -70,16 +70,20 @@ __global__ void __launch_bounds__(kBlock) k_surface_pre(lf_surface_args A)
     A.SurfaceRunoff[p] = surf;
     A.TotalRunoff[p] = surf + A.UZOutflowPixel[p] + A.LZOutflowToChannelPixel[p];
     A.scratch[p] = direct * A.MMtoM3 * A.InvPixelLength * A.InvDtSec;                       // SideflowDirect
-    A.scratch[N + p] = (srs[0] + srs[2]) * A.MMtoM3 * A.InvPixelLength * A.InvDtSec;       // Rainfed + Irrigated
-    A.scratch[2 * N + p] = srs[1] * A.MMtoM3 * A.InvPixelLength * A.InvDtSec;              // Forest
+    A.scratch[srow + p] = (srs[0] + srs[2]) * A.MMtoM3 * A.InvPixelLength * A.InvDtSec;    // Rainfed + Irrigated
+    A.scratch[2 * srow + p] = srs[1] * A.MMtoM3 * A.InvPixelLength * A.InvDtSec;           // Forest
+}
+__global__ void __launch_bounds__(kBlock) k_surface_pre(lf_surface_args A)
+{
+    const long long p = (long long)blockIdx.x * kBlock + threadIdx.x;
+    if (p >= A.N) return;
+    surface_pre_pixel(A, p, A.N);
 }
 
 // surface_routing.py:191-212
-__global__ void __launch_bounds__(kBlock) k_surface_post(lf_surface_args A)
+__device__ __forceinline__ void surface_post_pixel(const lf_surface_args &A, long long p)
 {
-    const long long p = (long long)blockIdx.x * kBlock + threadIdx.x;
     const long long N = A.N;
-    if (p >= N) return;
     const bool b35 = A.Beta == 0.6;
     const double qd = A.OFQDirect[p], qo = A.OFQOther[p], qf = A.OFQForest[p];
     // OFAlpha rows follow dim_runoff = [Other, Forest, Direct] (Lisflood_initial.py:288-290)
@@ -97,6 +101,89 @@ __global__ void __launch_bounds__(kBlock) k_surface_post(lf_surface_args A)
     A.ToChanM3Runoff[p] = run;
     A.ToChanM3RunoffDt[p] = run * A.InvNoRoutSteps;
 }
+__global__ void __launch_bounds__(kBlock) k_surface_post(lf_surface_args A)
+{
+    const long long p = (long long)blockIdx.x * kBlock + threadIdx.x;
+    if (p >= A.N) return;
+    surface_post_pixel(A, p);
+}
+
+// ---- the ensemble forms (lf_pixel_aggregates_members_device, lf_surface_step_members) ---------------------------------
+// Members share the statics; a member's own vectors are its rows: the [3,N] ones mo = m * member_stride elements behind the
+// vectors the argument block names, the [N] ones po = m * pixel_member_stride behind, the forcing fo behind.  The unit of
+// work is (block of 256 pixels, member), one launch covers all units, block-major and dealt to the workgroups by
+// land_members_unit (lf_blocks.h) exactly as the land surface's: the members of a pixel block run next to each other on one
+// XCD, whose L2 holds the block's static values for all of them.  A lane's arithmetic is the single kernel's (the same
+// body); only the base addresses change, by an offset that is uniform over the workgroup.
+struct module_members {
+    unsigned int members, nblocks; // nblocks: pixel blocks of ONE member
+    long long stride, pstride, fstride;
+};
+template <class T>
+__host__ __device__ __forceinline__ void row_shift(T *&x, long long by) // (a NULL pointer -- a map not reported -- stays NULL)
+{
+    if (x) x += by;
+}
+// `A` with every per-member row moved on: what the member kernels hand to the single kernels' bodies, and what the
+// member-after-member form hands to the single kernels
+__host__ __device__ __forceinline__ lf_surface_args surface_member_view(lf_surface_args A, long long mo, long long po, long long so)
+{
+    row_shift(A.AvailableWaterForInfiltration, mo); row_shift(A.Infiltration, mo); row_shift(A.SurfaceRunSoil, mo);
+    row_shift(A.DirectRunoff, po); row_shift(A.UZOutflowPixel, po); row_shift(A.LZOutflowToChannelPixel, po);
+    row_shift(A.OFQDirect, po); row_shift(A.OFQOther, po); row_shift(A.OFQForest, po);
+    row_shift(A.OFM3Direct, po); row_shift(A.OFM3Other, po); row_shift(A.OFM3Forest, po);
+    row_shift(A.SurfaceRunoff, po); row_shift(A.TotalRunoff, po); row_shift(A.OFToChanM3, po); row_shift(A.WaterDepth, po);
+    row_shift(A.ToChanM3Runoff, po); row_shift(A.ToChanM3RunoffDt, po);
+    row_shift(A.scratch, so);
+    return A; // shared: SoilFraction, OFAlpha, IsChannel
+}
+__host__ __device__ __forceinline__ lf_pixel_args pixel_member_view(lf_pixel_args A, long long mo, long long po, long long fo)
+{
+    row_shift(A.TaInterception, mo); row_shift(A.Ta, mo); row_shift(A.ESAct, mo); row_shift(A.PrefFlow, mo);
+    row_shift(A.Infiltration, mo); row_shift(A.SeepTopToSubA, mo); row_shift(A.SeepTopToSubB, mo); row_shift(A.SeepSubToGW, mo);
+    row_shift(A.Theta1a, mo); row_shift(A.Theta1b, mo); row_shift(A.Theta2, mo); row_shift(A.W1a, mo); row_shift(A.W1b, mo);
+    row_shift(A.W2, mo); row_shift(A.UZOutflow, mo); row_shift(A.GwPercUZLZ, mo); row_shift(A.Theta, mo);
+    row_shift(A.Rain, fo); row_shift(A.SnowMelt, fo); row_shift(A.EWRef, fo);
+    row_shift(A.CumInterSealed, po); row_shift(A.LZ, po); row_shift(A.LZInflowCUM, po); row_shift(A.TaInterceptionCUM, po);
+    row_shift(A.TaCUM, po); row_shift(A.ESActCUM, po); row_shift(A.GwLossCUM, po);
+    row_shift(A.RainSnowmelt, po); row_shift(A.EWaterAct, po); row_shift(A.InterSealed, po); row_shift(A.TASealed, po);
+    row_shift(A.DirectRunoff, po); row_shift(A.TaInterceptionAll, po); row_shift(A.TaPixel, po); row_shift(A.ESActPixel, po);
+    row_shift(A.PrefFlowPixel, po); row_shift(A.InfiltrationPixel, po); row_shift(A.ThetaAll, po);
+    row_shift(A.SeepTopToSubPixelA, po); row_shift(A.SeepTopToSubPixelB, po); row_shift(A.SeepSubToGWPixel, po);
+    row_shift(A.Theta1aPixel, po); row_shift(A.Theta1bPixel, po); row_shift(A.Theta2Pixel, po); row_shift(A.LZOutflow, po);
+    row_shift(A.UZOutflowPixel, po); row_shift(A.GwPercUZLZPixel, po); row_shift(A.GwLossLZ, po); row_shift(A.LZAvInflow, po);
+    row_shift(A.LZOutflowToChannelPixel, po);
+    return A; // shared: SoilFraction, SoilDepthTotal and the six [N] statics
+}
+// (pixel block, member) of the workgroup at `position` of a member launch whose linear id is `linear_id`: the land surface's
+// dealing rule over members * nblocks units (what the three member kernels run; lf_module_members_unit shows it to the tests)
+__host__ __device__ inline void module_members_unit(const module_members &M, unsigned int position, unsigned int linear_id,
+                                                    unsigned int &block, unsigned int &m)
+{
+    land_members_unit(M.members * M.nblocks, M.members, position, linear_id, block, m);
+}
+// the (pixel, member) of this lane -> false: beyond the member's last pixel
+__device__ __forceinline__ bool members_lane(const module_members &M, long long N, long long &p, unsigned int &m)
+{
+    unsigned int block;
+    module_members_unit(M, blockIdx.x, blockIdx.x, block, m);
+    p = (long long)block * kBlock + threadIdx.x;
+    return p < N;
+}
+__global__ void __launch_bounds__(kBlock) k_surface_pre_members(lf_surface_args A, module_members M)
+{
+    long long p;
+    unsigned int m;
+    if (!members_lane(M, A.N, p, m)) return;
+    surface_pre_pixel(surface_member_view(A, m * M.stride, m * M.pstride, m * M.pstride), p, (long long)M.members * M.pstride);
+}
+__global__ void __launch_bounds__(kBlock) k_surface_post_members(lf_surface_args A, module_members M)
+{
+    long long p;
+    unsigned int m;
+    if (!members_lane(M, A.N, p, m)) return;
+    surface_post_pixel(surface_member_view(A, m * M.stride, m * M.pstride, m * M.pstride), p);
+}
 // opensealed.dynamic + soil.dynamic_perpixel + groundwater.dynamic, one lane per pixel
 // Every diagnostic output is optional: a NULL pointer means the map is not reported, it is then not computed and the
 // [3,N] vectors only it needs are not read (uniform branches on kernel arguments).  What the rest of the model step needs
@@ -107,12 +194,11 @@ __global__ void __launch_bounds__(kBlock) k_surface_post(lf_surface_args A)
 // trips, because the struct's pointers may alias and no load may pass the store before it; 8 wavefronts x 3 loads in
 // flight per SIMD.  With ~70 loads in flight per lane (3 wavefronts per SIMD) the same bytes move at the rate of
 // independent streams (tools/micro/stream_count.hip).  Same operations per map, same bits.
+// (the body of pixel p, shared with the member kernel, which hands it the member's view of the argument block)
 template <bool ALL>
-__global__ void __launch_bounds__(kBlock) k_pixel_aggregates(lf_pixel_args A)
+__device__ __forceinline__ void pixel_aggregates_pixel(const lf_pixel_args &A, long long p)
 {
-    const long long p = (long long)blockIdx.x * kBlock + threadIdx.x;
     const long long N = A.N;
-    if (p >= N) return;
 #define LF_ST(X, v)                                                                                                      \
     do {                                                                                                                 \
         if (ALL || A.X) A.X[p] = (v);                                                                                    \
@@ -221,6 +307,21 @@ __global__ void __launch_bounds__(kBlock) k_pixel_aggregates(lf_pixel_args A)
 #undef LF_DEF
 #undef LF_ST
 }
+template <bool ALL>
+__global__ void __launch_bounds__(kBlock) k_pixel_aggregates(lf_pixel_args A)
+{
+    const long long p = (long long)blockIdx.x * kBlock + threadIdx.x;
+    if (p >= A.N) return;
+    pixel_aggregates_pixel<ALL>(A, p);
+}
+template <bool ALL>
+__global__ void __launch_bounds__(kBlock) k_pixel_aggregates_members(lf_pixel_args A, module_members M)
+{
+    long long p;
+    unsigned int m;
+    if (!members_lane(M, A.N, p, m)) return;
+    pixel_aggregates_pixel<ALL>(pixel_member_view(A, m * M.stride, m * M.pstride, m * M.fstride), p);
+}
 
 // lakes.dynamic_inloop (lakes.py:215-258) and reservoir.dynamic_inloop (reservoir.py:190-296): one lane per site
 __global__ void __launch_bounds__(kBlock) k_inloop_sites(lf_inloop_args A)
@@ -301,7 +402,8 @@ int lf_soil_pf_device(int device, const lf_soil_pf_args *a)
     return LF_OK;
 }
 
-int lf_pixel_aggregates_device(int device, const lf_pixel_args *a)
+// what the single call asks of its argument block (no device touched)
+static int pixel_check(const lf_pixel_args *a)
 {
     if (!a) return lf_set_error(LF_E_INVALID, "null argument");
     // always needed: what the rest of the model step reads, and the inputs behind it
@@ -318,8 +420,12 @@ int lf_pixel_aggregates_device(int device, const lf_pixel_args *a)
         (a->SeepSubToGWPixel && !a->SeepSubToGW) || (a->Theta1aPixel && !a->Theta1a) || (a->Theta1bPixel && !a->Theta1b) ||
         (a->Theta2Pixel && !a->Theta2) || (a->LZAvInflow && !a->LZInflowCUM))
         return lf_set_error(LF_E_INVALID, "pixel aggregates: an output is requested whose input vector is NULL");
-    lf_device_ctx *c;
-    LF_TRY(lf_ctx(device, &c));
+    return LF_OK;
+}
+
+// the launch of a checked block: the single kernel, or with M (members > 1) the member kernel over all (block, member) units
+static int pixel_launch(lf_device_ctx *c, const lf_pixel_args *a, const module_members *M)
+{
     // every optional map reported: the straight-line form with all loads up front (LF_AGG_ALL=0: the block-by-block form)
     const bool all = a->RainSnowmelt && a->EWaterAct && a->InterSealed && a->TASealed && a->TaInterceptionAll && a->TaInterceptionCUM &&
                      a->TaPixel && a->TaCUM && a->ESActPixel && a->ESActCUM && a->PrefFlowPixel && a->InfiltrationPixel && a->Theta &&
@@ -327,7 +433,13 @@ int lf_pixel_aggregates_device(int device, const lf_pixel_args *a)
                      a->Theta1bPixel && a->Theta2Pixel && a->LZOutflow && a->GwPercUZLZPixel && a->GwLossLZ && a->LZInflowCUM &&
                      a->LZAvInflow && a->GwLossCUM;
     const char *e = std::getenv("LF_AGG_ALL");
-    if (a->N > 0) {
+    if (a->N > 0 && M) {
+        const dim3 grid(M->members * M->nblocks);
+        if (all && !(e && e[0] == '0'))
+            hipLaunchKernelGGL(k_pixel_aggregates_members<true>, grid, dim3(kBlock), 0, c->stream, *a, *M);
+        else
+            hipLaunchKernelGGL(k_pixel_aggregates_members<false>, grid, dim3(kBlock), 0, c->stream, *a, *M);
+    } else if (a->N > 0) {
         if (all && !(e && e[0] == '0'))
             hipLaunchKernelGGL(k_pixel_aggregates<true>, dim3(blocks_for(a->N)), dim3(kBlock), 0, c->stream, *a);
         else
@@ -335,6 +447,90 @@ int lf_pixel_aggregates_device(int device, const lf_pixel_args *a)
     }
     LF_HIP(hipGetLastError());
     return LF_OK;
+}
+
+int lf_pixel_aggregates_device(int device, const lf_pixel_args *a)
+{
+    LF_TRY(pixel_check(a));
+    lf_device_ctx *c;
+    LF_TRY(lf_ctx(device, &c));
+    LF_TRY(pixel_launch(c, a, nullptr));
+    c->module_last_form[0] = 1;
+    return LF_OK;
+}
+
+// the member arguments of the two element-wise ensemble calls (forcing_member_stride < 0: the call has none)
+static int module_members_check(const char *what, int64_t N, int members, int64_t member_stride, int64_t pixel_member_stride,
+                                int64_t forcing_member_stride)
+{
+    if (members < 1) return lf_set_error(LF_E_INVALID, "%s: members = %d: at least one member", what, members);
+    if (N < 0) return lf_set_error(LF_E_INVALID, "%s: N = %lld is negative", what, (long long)N);
+    if (member_stride < 3 * N)
+        return lf_set_error(LF_E_INVALID, "%s: member_stride %lld is less than 3 * N = %lld", what, (long long)member_stride, (long long)(3 * N));
+    if (pixel_member_stride < N)
+        return lf_set_error(LF_E_INVALID, "%s: pixel_member_stride %lld is less than N = %lld", what, (long long)pixel_member_stride, (long long)N);
+    if (forcing_member_stride != 0 && forcing_member_stride < N)
+        return lf_set_error(LF_E_INVALID, "%s: forcing_member_stride %lld is neither 0 (shared) nor at least N = %lld", what,
+                            (long long)forcing_member_stride, (long long)N);
+    const unsigned long long nblocks = (unsigned long long)((N + kBlock - 1) / kBlock);
+    if (nblocks * (unsigned long long)members > 0x7fffffffull)
+        return lf_set_error(LF_E_INVALID, "%s: members * blocks = %llu exceeds the 32-bit range of a launch", what,
+                            nblocks * (unsigned long long)members);
+    return LF_OK;
+}
+static bool members_one_launch(const char *name) // LF_PIXEL_MEMBERS / LF_SURFACE_MEMBERS = 0: member after member (A/B)
+{
+    const char *e = std::getenv(name);
+    return !(e && e[0] == '0');
+}
+
+int lf_pixel_aggregates_members_device(int device, const lf_pixel_args *a, int members, int64_t member_stride,
+                                       int64_t pixel_member_stride, int64_t forcing_member_stride)
+{
+    if (!a) return lf_set_error(LF_E_INVALID, "null argument");
+    LF_TRY(module_members_check("pixel aggregates", a->N, members, member_stride, pixel_member_stride, forcing_member_stride));
+    LF_TRY(pixel_check(a));
+    if (members == 1) return lf_pixel_aggregates_device(device, a); // IS the single call
+    lf_device_ctx *c;
+    LF_TRY(lf_ctx(device, &c));
+    if (members_one_launch("LF_PIXEL_MEMBERS")) {
+        const module_members M{(unsigned int)members, (unsigned int)blocks_for(a->N), member_stride, pixel_member_stride, forcing_member_stride};
+        LF_TRY(pixel_launch(c, a, &M));
+        c->module_last_form[0] = 2;
+        return LF_OK;
+    }
+    for (int m = 0; m < members; ++m) {
+        const lf_pixel_args A = pixel_member_view(*a, m * member_stride, m * pixel_member_stride, m * forcing_member_stride);
+        LF_TRY(pixel_launch(c, &A, nullptr));
+    }
+    c->module_last_form[0] = 3;
+    return LF_OK;
+}
+
+// (pixel block, member) of launch position `position` of the element-wise member kernels over nblocks * members units, when
+// the workgroup at position 0 has linear id 0 (host only: the function the kernels call, for the tests)
+int lf_module_members_unit(int64_t nblocks, int members, int64_t position, int64_t *block, int *member)
+{
+    if (!block || !member) return lf_set_error(LF_E_INVALID, "null argument");
+    if (nblocks < 1 || members < 1 || (unsigned long long)nblocks * (unsigned long long)members > 0x7fffffffull)
+        return lf_set_error(LF_E_INVALID, "nblocks and members must be positive and their product within the 32-bit range");
+    if (position < 0 || position >= nblocks * members) return lf_set_error(LF_E_INVALID, "position outside the launch");
+    const module_members M{(unsigned int)members, (unsigned int)nblocks, 0, 0, 0};
+    unsigned int b, m;
+    module_members_unit(M, (unsigned int)position, (unsigned int)position, b, m);
+    *block = b;
+    *member = (int)m;
+    return LF_OK;
+}
+
+// which form the last pixel-aggregates (stage 0) / surface-step (stage 1) call on `device` took: 0 none yet, 1 the single
+// call, 2 the members in one launch, 3 member after member
+int lf_module_last_form(int device, int stage)
+{
+    if (stage < 0 || stage > 1) return lf_set_error(LF_E_INVALID, "stage %d: 0 (pixel aggregates) or 1 (surface step)", stage);
+    lf_device_ctx *c;
+    LF_TRY(lf_ctx(device, &c));
+    return c->module_last_form[stage];
 }
 
 int lf_inloop_structures(int device, const lf_inloop_args *a)
@@ -424,6 +620,48 @@ static int surface_step(lf_router *direct_router, lf_router *other_router, lf_ro
     }
     hipLaunchKernelGGL(k_surface_post, grid, block, 0, c->stream, *a);
     LF_HIP(hipGetLastError());
+    c->module_last_form[1] = 1;
+    return LF_OK;
+}
+
+int lf_surface_step_members(lf_router *direct_router, lf_router *other_router, lf_router *forest_router, const lf_surface_args *a,
+                            int members, int64_t member_stride, int64_t pixel_member_stride)
+{
+    if (!direct_router || !other_router || !forest_router || !a) return lf_set_error(LF_E_INVALID, "null argument");
+    LF_TRY(module_members_check("surface step", a->N, members, member_stride, pixel_member_stride, 0));
+    if (members == 1) return surface_step(direct_router, other_router, forest_router, a, 1); // IS lf_surface_step_ordered
+    const int device = lf_router_device(direct_router);
+    if (lf_router_device(other_router) != device || lf_router_device(forest_router) != device)
+        return lf_set_error(LF_E_INVALID, "the three surface routers must live on one device");
+    lf_device_ctx *c;
+    LF_TRY(lf_ctx(device, &c));
+    const int64_t N = a->N;
+    const bool one_launch = members_one_launch("LF_SURFACE_MEMBERS");
+    if (N == 0) {
+        c->module_last_form[1] = one_launch ? 2 : 3;
+        return LF_OK;
+    }
+    if (!one_launch) { // member after member through the single call, scratch [members][3,N]
+        for (int m = 0; m < members; ++m) {
+            const lf_surface_args A = surface_member_view(*a, m * member_stride, m * pixel_member_stride, m * 3 * N);
+            LF_TRY(surface_step(direct_router, other_router, forest_router, &A, 1));
+        }
+        c->module_last_form[1] = 3;
+        return LF_OK;
+    }
+    const module_members M{(unsigned int)members, (unsigned int)blocks_for(N), member_stride, pixel_member_stride, 0};
+    const dim3 grid(M.members * M.nblocks), block(kBlock);
+    hipLaunchKernelGGL(k_surface_pre_members, grid, block, 0, c->stream, *a, M);
+    {   // ONE member sweep of the three routers: the lateral-inflow row sets have the stride of the discharge rows
+        lf_router *rs[3] = {direct_router, other_router, forest_router};
+        double *q[3] = {a->OFQDirect, a->OFQOther, a->OFQForest};
+        const int64_t set = (int64_t)members * pixel_member_stride;
+        const double *lat[3] = {a->scratch, a->scratch + set, a->scratch + 2 * set};
+        LF_TRY(lf_router_route_ordered_members_multi(3, rs, q, lat, members, pixel_member_stride, LF_SECTION_MAIN));
+    }
+    hipLaunchKernelGGL(k_surface_post_members, grid, block, 0, c->stream, *a, M);
+    LF_HIP(hipGetLastError());
+    c->module_last_form[1] = 2;
     return LF_OK;
 }
 

@@ -540,6 +540,95 @@ int route_members(lf_router *r, double *q_dev, const double *lat_dev, int member
     return LF_OK;
 }
 
+// ---- an ensemble on several routers of one graph (lf_sweep.h: k_*_members_multi) -------------------------------------------
+template <bool FUSED, int STATICS>
+void launch_level_members_multi(int mb, unsigned blocks, int count, int members, hipStream_t s, int first, int cells,
+                                const sweep_args_multi &M, const member_rows &R)
+{
+    const dim3 grid(blocks, (unsigned)(count * ((members + mb - 1) / mb))), block(kLevelBlock);
+    if (mb == 1)
+        hipLaunchKernelGGL((k_level_members_multi<FUSED, true, STATICS, 1>), grid, block, 0, s, first, cells, M, R);
+    else if (mb == 2)
+        hipLaunchKernelGGL((k_level_members_multi<FUSED, true, STATICS, 2>), grid, block, 0, s, first, cells, M, R);
+    else
+        hipLaunchKernelGGL((k_level_members_multi<FUSED, true, STATICS, 4>), grid, block, 0, s, first, cells, M, R);
+}
+
+// `count` routers that may be swept together (the caller's check: the rule of lf_router_route_device_multi), each with its
+// `members` rows of q_dev[i] / lat_dev[i]: enqueue_route_members' schedule on rs[0], every launch once for all
+// count * members units (more than kMaxGridY of them: in slices of members).  Not profiling.
+int enqueue_route_members_multi(int count, lf_router **rs, double *const *q_dev, const double *const *lat_dev, int members,
+                                int64_t stride, int section)
+{
+    lf_router *r = rs[0];
+    hipStream_t s = r->ctx->stream;
+    const int n = (int)r->N;
+    if (!r->fused) {
+        bool grow = false;
+        for (int i = 0; i < count; ++i) grow = grow || rs[i]->constant.n < (size_t)members * (size_t)n;
+        if (grow) LF_HIP(hipStreamSynchronize(s)); // (earlier calls read the buffers that go)
+        for (int i = 0; i < count; ++i)
+            if (rs[i]->constant.n < (size_t)members * (size_t)n) LF_TRY(rs[i]->constant.grow((size_t)members * (size_t)n));
+    }
+    bool blocks = !r->rplan.empty(); // (enqueue_route's condition: one graph object, one plan)
+    for (int i = 1; i < count; ++i)
+        blocks = blocks && rs[i]->graph_serial == r->graph_serial && r->graph_serial != 0 &&
+                 rs[i]->rplan.lmax == r->rplan.lmax && rs[i]->rplan.cw == r->rplan.cw;
+    const int mb = members_per_lane(), slice = kMaxGridY / count;
+    launch_counts c;
+    for (int m0 = 0; m0 < members; m0 += slice) {
+        const int mm = std::min(members - m0, slice), units = count * mm;
+        sweep_args_multi M;
+        for (int i = 0; i < kMaxMulti; ++i) {
+            const int j = i < count ? i : 0;
+            M.r[i] = sweep_args_of(*rs[j], section, q_dev[j] + (int64_t)m0 * stride, nullptr, lat_dev[j] + (int64_t)m0 * stride);
+            if (!r->fused) M.r[i].constant = rs[j]->constant.p + (int64_t)m0 * n;
+        }
+        const member_rows R{(long long)stride, (long long)n, mm};
+        if (!r->fused) {
+            hipLaunchKernelGGL(k_prep_members_multi, dim3(blocks_for(n), units), dim3(kBlock), 0, s, n, M, R);
+            ++c.launches;
+        }
+        auto cones = [&](dim3 grid, const cone_plan_args &C, int64_t) {
+            grid.y = (unsigned)units;
+            pick_flags(r->fused, r->rplan.cw == 64, [&](auto f, auto one_wavefront) {
+                constexpr int CW = one_wavefront ? 64 : kBlock;
+                hipLaunchKernelGGL((k_sweep_cones_members_multi<f, true, CW>), grid, dim3(CW), 0, s, C, M, R);
+            });
+            return (int)LF_OK;
+        };
+        auto level = [&](int first, int cells) {
+            const unsigned nb = (unsigned)level_blocks_for(cells);
+            sweep_args_multi B = M;
+            bool records = r->fused; // the (a, dx) records: for every router or for none
+            for (int i = 0; i < count && records; ++i) records = (B.r[i].adx = level_statics(rs[i], M.r[i])) != nullptr;
+            for (int i = count; i < kMaxMulti; ++i) B.r[i].adx = B.r[0].adx;
+            if (records)
+                launch_level_members_multi<true, 1>(mb, nb, count, mm, s, first, cells, B, R);
+            else if (r->fused)
+                launch_level_members_multi<true, 0>(mb, nb, count, mm, s, first, cells, B, R);
+            else
+                launch_level_members_multi<false, 0>(mb, nb, count, mm, s, first, cells, B, R);
+            return (int)LF_OK;
+        };
+        auto narrow = [&](int k0, int k1) {
+            if (r->fused)
+                hipLaunchKernelGGL((k_levels_narrow_members_multi<true, true>), dim3(units), dim3(kNarrowBlock), 0, s, k0, k1, r->level_start.p, M, R);
+            else
+                hipLaunchKernelGGL((k_levels_narrow_members_multi<false, true>), dim3(units), dim3(kNarrowBlock), 0, s, k0, k1, r->level_start.p, M, R);
+            return (int)LF_OK;
+        };
+        LF_TRY(route_schedule(*r, 0, r->rplan.nblocks(), r->schedule, blocks, c, cones, level, narrow));
+    }
+    for (int i = 0; i < count; ++i) {
+        rs[i]->last_stats[0] = c.launches;
+        rs[i]->last_stats[1] = c.wide;
+        rs[i]->last_stats[2] = c.narrow;
+        rs[i]->last_stats[3] = rs[i]->NL;
+    }
+    return LF_OK;
+}
+
 } // namespace
 
 // Level blocks for the fused sub-step wavefront (k_fused_cones): runs of consecutive levels of at most `wide` cells are
@@ -773,6 +862,44 @@ int lf_router_route_ordered_members(lf_router *r, double *discharge_ord_dev, con
     return route_members(r, discharge_ord_dev, lateral_ord_dev, members, stride, section);
 }
 
+// An ensemble on `count` routers: router i sweeps its own `members` rows of discharge_ord_dev[i] / lateral_ord_dev[i].
+// Routers that lf_router_route_device_multi would sweep together get one launch per wide level, narrow run or level block
+// for all count * members units (enqueue_route_members_multi); others one member call each.  The arguments are checked
+// before a router or a device is touched.
+int lf_router_route_ordered_members_multi(int count, lf_router **routers, double **discharge_ord_dev,
+                                          const double **lateral_ord_dev, int members, int64_t stride, int section)
+{
+    if (count < 1 || count > kMaxMulti) return lf_set_error(LF_E_INVALID, "count must be 1 to %d (got %d)", kMaxMulti, count);
+    if (members < 1) return lf_set_error(LF_E_INVALID, "members must be at least 1 (got %d)", members);
+    if (stride < 0) return lf_set_error(LF_E_INVALID, "stride %lld is less than the router's number of cells", (long long)stride);
+    if (!routers || !discharge_ord_dev || !lateral_ord_dev) return lf_set_error(LF_E_INVALID, "null argument");
+    for (int i = 0; i < count; ++i)
+        if (!routers[i] || !discharge_ord_dev[i] || !lateral_ord_dev[i]) return lf_set_error(LF_E_INVALID, "null argument");
+    for (int i = 0; i < count; ++i) {
+        if (stride < routers[i]->N)
+            return lf_set_error(LF_E_INVALID, "stride %lld is less than the number of cells of router %d (%lld)", (long long)stride, i,
+                                (long long)routers[i]->N);
+    }
+    for (int i = 0; i < count; ++i) LF_TRY(check_plain_call(routers[i], section));
+    bool together = count > 1;
+    for (int i = 0; i < count && together; ++i) {
+        const lf_router *r = routers[i], *r0 = routers[0];
+        together = !r->linked.p && r->device == r0->device && r->ctx == r0->ctx && r->N == r0->N && r->fused == r0->fused &&
+                   r->h_level_start == r0->h_level_start && !r->profile;
+    }
+    if (!together) {
+        for (int i = 0; i < count; ++i)
+            LF_TRY(route_members(routers[i], discharge_ord_dev[i], lateral_ord_dev[i], members, stride, section));
+        return LF_OK;
+    }
+    if (members == 1) return lf_router_route_device_multi(count, routers, discharge_ord_dev, lateral_ord_dev, section, 1);
+    if (routers[0]->N == 0) return LF_OK;
+    LF_HIP(hipSetDevice(routers[0]->device));
+    LF_TRY(enqueue_route_members_multi(count, routers, discharge_ord_dev, lateral_ord_dev, members, stride, section));
+    LF_HIP(hipGetLastError());
+    return LF_OK;
+}
+
 // ... from host arrays in pixel order: up, every row into sweep order, the member call, back (staging kept with r)
 int lf_router_route_members_host(lf_router *r, double *discharge_host, const double *lateral_host, int members, int section)
 {
@@ -812,6 +939,24 @@ int lf_gather_device(int device, int64_t n, const int32_t *index_dev, const doub
     if (n > 0)
         hipLaunchKernelGGL(k_gather, dim3(blocks_for(n)), dim3(kBlock), 0, c->stream, (int)n, (const int *)index_dev, src_dev,
                            dst_dev);
+    LF_HIP(hipGetLastError());
+    return LF_OK;
+}
+
+int lf_gather_rows_device(int device, int64_t n, const int32_t *index_dev, const double *src_dev, int64_t src_stride,
+                          double *dst_dev, int64_t dst_stride, int rows)
+{
+    if (rows < 1) return lf_set_error(LF_E_INVALID, "rows must be at least 1 (got %d)", rows);
+    if (n < 0 || n > 0x7fffffffll) return lf_set_error(LF_E_INVALID, "n = %lld outside the 32-bit range of a launch", (long long)n);
+    if (dst_stride < n) return lf_set_error(LF_E_INVALID, "dst_stride %lld is less than n = %lld", (long long)dst_stride, (long long)n);
+    if (src_stride < 0) return lf_set_error(LF_E_INVALID, "src_stride %lld is negative", (long long)src_stride);
+    if (n > 0 && (!index_dev || !src_dev || !dst_dev)) return lf_set_error(LF_E_INVALID, "null argument");
+    lf_device_ctx *c;
+    LF_TRY(lf_ctx(device, &c));
+    for (int r0 = 0; r0 < rows && n > 0; r0 += kMaxGridY) // (one launch unless there are more rows than a grid has)
+        hipLaunchKernelGGL(k_gather_rows, dim3(blocks_for(n), (unsigned)std::min(rows - r0, kMaxGridY)), dim3(kBlock), 0, c->stream, (int)n,
+                           (const int *)index_dev, src_dev + (int64_t)r0 * src_stride, src_stride, dst_dev + (int64_t)r0 * dst_stride,
+                           dst_stride);
     LF_HIP(hipGetLastError());
     return LF_OK;
 }

@@ -176,10 +176,8 @@ struct soil_tail {
 // to each other on ONE XCD, whose L2 then holds the tile's 176 B per column of statics for all of them (at most 7 tiles
 // straddle two XCDs).  In member-major order a static line's reuse distance is a whole member's traffic and no cache helps.
 // HIP promises no placement: with another dispatch order the result is the same and only the gain is lost.
-// -DLF_LAND_MEMBERS_XCD=0: plain tile-major launch order (A/B, tools/build_variant.sh).
-#ifndef LF_LAND_MEMBERS_XCD
-#define LF_LAND_MEMBERS_XCD 1
-#endif
+// -DLF_LAND_MEMBERS_XCD=0: plain tile-major launch order (A/B, tools/build_variant.sh).  The dealing rule itself,
+// land_members_unit, lives in lf_blocks.h: the element-wise member kernels of lf_modules.hip use the same one.
 template <bool MEMBERS>
 struct soil_members {}; // the single call: nothing
 template <>
@@ -187,14 +185,6 @@ struct soil_members<true> {
     unsigned int members, ntiles; // ntiles: tiles of ONE member (the workspace holds members * ntiles, member-major)
     long long stride, fstride;
 };
-// (tile, member) of the workgroup at `position` of the launch whose linear id is `linear_id`
-__host__ __device__ inline void land_members_unit(unsigned int units, unsigned int members, unsigned int position,
-                                                  unsigned int linear_id, unsigned int &tile, unsigned int &member)
-{
-    const unsigned int u = LF_LAND_MEMBERS_XCD ? (unsigned int)lf_xcd_contiguous((int)position, (int)units, linear_id) : position;
-    tile = u / members;
-    member = u - tile * members;
-}
 
 // phase 3: soilloop.py:313-354 for one column, 18 stores.  mo: the member's offset (0: no members)
 __device__ __forceinline__ void soil_finish(const lf_soil_args &A, long long i, bool drained, const soil_tail &T, double sa,

@@ -1117,6 +1117,68 @@ __global__ void __launch_bounds__(CW) k_sweep_cones_members(cone_plan_args C, sw
     sweep_cone<FUSED, ORDERED, 1, CW>(blockIdx.x, C, M);
 }
 
+// ---- an ensemble on SEVERAL routers of one graph (lf_router_route_ordered_members_multi) ---------------------------------
+// The overland routers of an ensemble: M.r[i] is router i's argument block with member 0's rows, R the rows of every router
+// (same stride, same count).  The unit of work is (router, member), router-major; a unit picks its router's block and then
+// runs the member kernels' code on the member's view of it: sweep_cell_state / sweep_cone<.., 1, ..> on member_view.
+// k_prep for all units: blockIdx.y = router * members + member
+__global__ void __launch_bounds__(kBlock) k_prep_members_multi(int n, sweep_args_multi M, member_rows R)
+{
+    const int p = blockIdx.x * kBlock + threadIdx.x;
+    if (p >= n) return;
+    const int router = (int)blockIdx.y / R.members, m = (int)blockIdx.y - router * R.members;
+    const sweep_args &A = M.r[router];
+    double *__restrict__ constant = const_cast<double *>(A.constant);
+    const long long row = (long long)m * R.stride;
+    const double lateral = A.lat[row + p] * (A.dx ? A.dx[p] : A.dx_scalar); // (k_prep's expression, sweep order)
+    constant[(long long)m * R.cstride + p] = A.a[p] * pow(A.qord[row + p], A.beta) + lateral;
+}
+
+// One wide level: blockIdx.y = router * groups + group of MB members -- a group stays within one router, whose (a, dx) the
+// lane holds across it
+template <bool FUSED, bool ORDERED, int STATICS, int MB>
+__global__ void __launch_bounds__(kLevelBlock) LF_MEMBERS_ATTR(MB) k_level_members_multi(int first, int count, sweep_args_multi M, member_rows R)
+{
+    static_assert(ORDERED && (STATICS == 0 || (STATICS == 1 && FUSED)), "members lie in sweep order; records: (a, dx)");
+    const int i = blockIdx.x * kLevelBlock + threadIdx.x;
+    if (i >= count) return;
+    const int groups = (R.members + MB - 1) / MB;
+    const int router = (int)blockIdx.y / groups, m0 = ((int)blockIdx.y - router * groups) * MB;
+    const sweep_args &A = M.r[router];
+    const int p = first + i;
+    const int u0 = A.ups_ptr[p], u1 = A.ups_ptr[p + 1];
+    double ap, dxp;
+    sweep_cell_statics<FUSED, STATICS>(p, A, ap, dxp);
+#pragma unroll
+    for (int j = 0; j < MB; ++j)
+        if (m0 + j < R.members) sweep_cell_state<FUSED, ORDERED, false, STATICS>(p, p, ap, dxp, u0, u1, 0, member_view(A, R, m0 + j));
+}
+
+// A run of narrow levels: one workgroup per unit (blockIdx.x = router * members + member)
+template <bool FUSED, bool ORDERED>
+__global__ void __launch_bounds__(kNarrowBlock) k_levels_narrow_members_multi(int k0, int k1, const long long *__restrict__ level_start,
+                                                                              sweep_args_multi M, member_rows R)
+{
+    const int router = (int)blockIdx.x / R.members;
+    const sweep_args B = member_view(M.r[router], R, (int)blockIdx.x - router * R.members);
+    for (int k = k0; k < k1; ++k) {
+        const int first = (int)level_start[k], last = (int)level_start[k + 1];
+        for (int p = first + (int)threadIdx.x; p < last; p += kNarrowBlock) sweep_cell<FUSED, ORDERED, false>(p, B);
+        __threadfence_block();
+        __syncthreads();
+    }
+}
+
+// A level block: blockIdx.y = router * members + member
+template <bool FUSED, bool ORDERED, int CW>
+__global__ void __launch_bounds__(CW) k_sweep_cones_members_multi(cone_plan_args C, sweep_args_multi M, member_rows R)
+{
+    const int router = (int)blockIdx.y / R.members;
+    sweep_args_multi U;
+    U.r[0] = member_view(M.r[router], R, (int)blockIdx.y - router * R.members);
+    sweep_cone<FUSED, ORDERED, 1, CW>(blockIdx.x, C, U);
+}
+
 // ================================================================================================
 // Host side: what the single domain's router (lf_router.hip: lf_router) and the row-block partition's (lf_dist.hip:
 // lf_dist_router) have in common -- lf_router_core, its setup and the launch schedule of a plain router call.
@@ -1161,6 +1223,14 @@ __global__ void __launch_bounds__(kBlock) k_gather(int n, const int *__restrict_
 {
     const int p = blockIdx.x * kBlock + threadIdx.x;
     if (p < n) dst_ord[p] = src_pix[perm[p]];
+}
+
+// k_gather for several rows with one index table: blockIdx.y = row (lf_gather_rows_device)
+__global__ void __launch_bounds__(kBlock) k_gather_rows(int n, const int *__restrict__ index, const double *__restrict__ src,
+                                                        long long src_stride, double *__restrict__ dst, long long dst_stride)
+{
+    const int p = blockIdx.x * kBlock + threadIdx.x;
+    if (p < n) dst[(long long)blockIdx.y * dst_stride + p] = src[(long long)blockIdx.y * src_stride + index[p]];
 }
 
 __global__ void __launch_bounds__(kBlock) k_scatter(int n, const int *__restrict__ perm, const double *__restrict__ src_ord,

@@ -24,7 +24,7 @@ _SIGNATURES = {
     "": "version",
     "i": "side_stream_begin side_stream_end side_stream_join lane_fork lane_join device_trim "
          "device_synchronize timer_start soil_last_form",
-    "ii": "upload_begin upload_end upload_wait compute_acquire compute_release lane_select",
+    "ii": "upload_begin upload_end upload_wait compute_acquire compute_release lane_select module_last_form",
     "iippq": "calibration_streams",
     "iiqp": "substep_stage",
     "ip": "device_free host_free timer_stop canopy_device soil_pf_device inloop_structures "
@@ -32,17 +32,20 @@ _SIGNATURES = {
           "soil_columns_device_derived soil_last_deferred",
     "ipi": "soil_substep_histogram",
     "ipiiqq": "soil_columns_members_device",
+    "ipiqqq": "pixel_aggregates_members_device",
     "ipiz": "memset",
     "ippii": "lddrepair_raster_device",
     "ipppi": "land_columns_device",
     "ipppiiqq": "land_columns_members_device",
     "ipppii": "router_route_device_multi upstream_sum_raster_device lddmask_raster_device ldd_raster_host",
     "ipppqq": "scale_rows_device",
+    "ipppiqi": "router_route_ordered_members_multi",
     "ippqi": "calibration_copy",
     "ippz": "memcpy_h2d memcpy_h2d_staged upload_copy upload_copy_f32 memcpy_d2h memcpy_d2d",
     "ipqp": "count_nonfinite",
     "ipz": "device_name",
     "iqppp": "gather_device",
+    "iqppqpqi": "gather_rows_device",
     "iup": "xcd_contiguous_order",
     "izp": "device_alloc host_alloc",
     "p": "struct_sizes device_count graph_max_upstream router_device router_reset_site_cache router_last_fused_form "
@@ -83,11 +86,12 @@ _SIGNATURES = {
     "pppp": "graph_get_lookups graph_get_layout surface_step surface_step_ordered dist_graph_set_ghost_phases "
             "dist_graph_get_csr",
     "ppppiii": "dist_router_route dist_router_compute_part_io",
+    "ppppiqq": "surface_step_members",
     "ppppiiii": "dist_router_route_many",
     "ppppppp": "dist_graph_get_fused_plan",
     "pppppppp": "dist_graph_get_route_plan",
     "qipqpppqppppppp": "site_plan",
-    "qiqpp": "land_members_unit",
+    "qiqpp": "land_members_unit module_members_unit",
     "p>q": "graph_num_pixels graph_num_levels router_num_pixels dist_graph_num_pixels dist_graph_state_size "
            "dist_graph_num_launch_units dist_graph_num_noncontiguous dist_router_state_size "
            "dist_router_last_launches",

@@ -765,3 +765,422 @@ def _structures_on_subdomain(st, ids, N):
         else:
             out[k] = a
     return out
+
+
+class HotPathEnsemble:
+    """HotPathDevice for an ENSEMBLE -- members that share the LDDs, the geometry and the parameters and differ in state and
+    forcing (a forecast ensemble, a calibration batch over the forcing, an EnKF): one model step of every member costs
+    roughly the launches of one member.  Per step:
+
+        lf_land_columns_members_device -> lf_pixel_aggregates_members_device -> lf_surface_step_members
+        -> lf_gather_rows_device -> lf_routing_substeps_fused_members (with structures=: ..._structures_members)
+
+    It takes HotPathDevice's inputs; every member starts from `values`.  The non-channel vectors always live in the sweep
+    order of the overland graph and the land surface is always the fused one.  The [N] / [3,N] statics, LAI and LAITerm exist
+    once; a member's own vectors are rows of one device vector per name: [3,N] rows 3 N + pad elements apart, [N] rows and
+    forcing rows N + pad apart (soilloop._EnsembleVectors, whose layout code this class uses), channel rows Nk + pad apart
+    (routing.routingEnsemble).  Nothing reads or writes the elements between the rows (gaps / set_gaps).  Every member ends
+    up, bit for bit, as a HotPathDevice of its own fed the same forcing.
+    With structures= the channel part is the routing module HotPathDevice builds, on the compact channel domain with the
+    subset already applied, and its routing.ensemble(members).
+    Not in this class (HotPathDevice has them): prefetch / pinned_forcing (the double-buffered upload), step_profile,
+    state_maps / load_state_maps and mass_balance.  The forcing of step(forcing) goes up with blocking copies on the main
+    stream (lf_memcpy_h2d), which wait for the side stream as well: with overlap_channel the channel loop of a step therefore
+    ends before the kernels of the next step start, and the overlap HotPathDevice gets from its second stream is lost; only
+    step(None) -- the forcing rows the device already holds, what the measurement tool times as the device's own work --
+    keeps it."""
+
+    STATE = HotPathDevice.STATE
+    _kept = HotPathDevice._kept
+
+    def __init__(self, values, scalars, land_mask, ldd_to_chan, ldd_kinematic, members, split=True, device=0, structures=None,
+                 compact=True, overlap_channel=True, report=None, pad=0):
+        self.device, self.split, self.members = device, bool(split), int(members)
+        self.overlap_channel = bool(overlap_channel)
+        self._gap = 0.0                      # what lies between the members' rows of the channel part (set_gaps)
+        self.report = None if report is None else set(report)
+        if self.report is not None and not self.report <= set(OPTIONAL_MAPS):
+            raise ValueError("report: not optional maps: %s" % sorted(self.report - set(OPTIONAL_MAPS)))
+        sc = self.sc = dict(scalars)
+        land_mask = np.asarray(land_mask, bool)
+        N = self.N = int(land_mask.sum())
+        M = self.members
+        values = dict(values)
+        kept = self._kept()
+        chan_names = set(RT._STATIC + RT._STATE)
+        # ---- overland routers, and the order of every non-channel vector ------------------------------------------------
+        g_surf = Graph(ldd_to_chan, land_mask)
+        alpha_of = np.asarray(values["OFAlpha"], float)
+        mk = lambda row: kinematicWave(None, None, alpha_of[row], sc["Beta"], sc["PixelLength"], sc["DtSec"],
+                                       device=device, graph=g_surf)
+        self.r_other, self.r_forest, self.r_direct = mk(0), mk(1), mk(2)
+        self.pixel_of_position = g_surf.layout()[0].astype(np.int64)
+        # ---- land surface: the member rows and shared statics of LandSurfaceEnsemble -------------------------------------
+        d = {k: self._ordered(a) for k, a in values.items() if k not in chan_names}
+        d.update(sc)
+        E = self.land = SL.LandSurfaceEnsemble(d, M, device, pad)
+        for k in list(E._member):
+            if k in OPTIONAL_MAPS and k not in kept:           # a soil diagnostic nobody asked for: no vector, not computed
+                E._member.remove(k)
+                E.dev.pop(k).free()
+                setattr(E.soil, k, None)
+        self.stride, self.pstride = E.stride, E.fstride
+        wanted = lambda names: [k for k in names if k not in OPTIONAL_MAPS or k in kept]
+
+        def rows(names, group, shape):
+            for k in names:
+                if k not in E.dev:
+                    group.append(k)
+                    E._put(k, d[k] if k in d else np.zeros(shape))
+
+        def statics(names):
+            for k in names:
+                if k not in E.dev:
+                    E._put_static(k, d[k])
+        # ---- per-pixel aggregates ---------------------------------------------------------------------------------------
+        shared_v, shared_n = ["SoilFraction", "SoilDepthTotal"], PA._N_IN[3:]
+        statics(shared_v + shared_n)
+        rows(wanted(["Theta"]), E._member, (3, N))
+        rows(wanted(PA._STATE + PA._OUT), E._pixel, N)
+        p = self.pixel = PA._PixelArgs()
+        for k in wanted(PA._V_IN + PA._N_IN + PA._STATE + PA._OUT + ["Theta"]):
+            setattr(p, k, E.dev[k].ptr.value)
+        if self.report is not None:        # a [3,N] input that only unreported maps read is not handed to the kernel
+            for src, outs in PA_READERS.items():
+                if not any(o in kept for o in outs):
+                    setattr(p, src, None)
+        p.InvDtDay, p.N = sc["InvDtDay"], N
+        # ---- overland step ----------------------------------------------------------------------------------------------
+        statics(["OFAlpha"])
+        E._static.append("IsChannel")
+        E.dev["IsChannel"] = DeviceArray.from_host(u8(d["IsChannel"]), device)
+        rows(["SurfaceRunSoil"], E._member, (3, N))
+        rows(SR._STATE + SR._OUT, E._pixel, N)
+        E.dev["scratch"] = DeviceArray(3 * M * self.pstride, np.float64, device).zero()
+        f = self.surface = SR._SurfaceArgs()
+        for k in SR._V_IN + SR._N_IN + SR._STATE + SR._OUT + ["SurfaceRunSoil", "scratch"]:
+            setattr(f, k, E.dev[k].ptr.value)
+        f.Beta, f.MMtoM3, f.M3toMM = sc["Beta"], sc["MMtoM3"], sc["M3toMM"]
+        f.PixelLength, f.InvPixelLength = sc["PixelLength"], 1 / sc["PixelLength"]
+        f.DtSec, f.InvDtSec, f.InvNoRoutSteps, f.N = sc["DtSec"], 1 / sc["DtSec"], 1 / sc["NoRoutSteps"], N
+        # ---- channel domain and channel part, as HotPathDevice makes them -------------------------------------------------
+        ldd_kinematic = np.asarray(ldd_kinematic, np.float64)
+        drop = inert_pixels(values, ldd_kinematic, land_mask, self.split, structures) if compact else np.zeros(N, bool)
+        if drop.sum() < 0.1 * N:
+            drop[:] = False
+        self.ids = np.nonzero(~drop)[0]
+        Nk = self.Nk = self.ids.size
+        chan_mask = land_mask
+        if Nk < N:
+            chan_mask = np.zeros(land_mask.shape, bool)
+            chan_mask[land_mask] = ~drop
+            ldd_kinematic = ldd_kinematic[self.ids]
+            if structures is not None:
+                structures = _structures_on_subdomain(structures, self.ids, N)
+        v = types.SimpleNamespace(IsChannelKinematic=np.zeros(Nk, bool))
+        for k in chan_names & set(values):
+            setattr(v, k, np.array(np.broadcast_to(np.asarray(values[k]), (N,))[self.ids], copy=True))
+        v.Beta, v.InvBeta, v.DtRouting, v.InvDtRouting = sc["Beta"], 1 / sc["Beta"], sc["DtRouting"], 1 / sc["DtRouting"]
+        v.DtSec, v.NoRoutSteps, v.InvNoRoutSteps = sc["DtSec"], int(sc["NoRoutSteps"]), 1 / sc["NoRoutSteps"]
+        self.kstride = Nk + int(pad)
+        self.rmod, self._qin_old, self._qin = None, None, {}
+        if structures is None:
+            self.river = kinematicWave(ldd_kinematic, chan_mask, v.ChannelAlpha, sc["Beta"], v.ChanLength, sc["DtRouting"],
+                                       alpha_floodplains=v.ChannelAlpha2 if split else None, device=device)
+            self.chan = RT.routingEnsemble(v, self.river, M, self.split, self.kstride, device)
+        else:
+            v.ToChanM3RunoffDt = np.zeros(Nk)
+            for k, a in structures.items():
+                setattr(v, k, a)
+            opts = dict(SplitRouting=self.split, InitLisflood=False, simulateLakes="LakeIndex" in structures,
+                        simulateReservoirs="ReservoirIndex" in structures, inflow="QInM3Old" in structures,
+                        TransLoss="UpTrans" in structures)
+            m = self.rmod = RT.routing(v, options=opts, device=device, engine_order=True)
+            m.attach_router(ldd_kinematic, chan_mask)
+            m.attach_structures()
+            m.begin_step()
+            m._structures_substep(0, launch=False)
+            m._args.split = 1 if self.split else 0
+            self.river = m.river_router
+            self.chan = m.ensemble(M, self.kstride)
+        self.perm = self.river.graph.layout()[0].astype(np.int64)        # engine position -> channel-domain pixel
+        self.gpix = self.ids[self.perm]                                   # engine position -> land pixel
+        inv = np.empty(N, np.int64)
+        inv[self.pixel_of_position] = np.arange(N)
+        self._gidx = DeviceArray.from_host(inv[self.gpix].astype(np.int32), device)
+        # the sideflow rows of the channel loop: ToChanM3RunoffDt of every member in the channel router's engine order
+        self._side = DeviceArray(M * self.kstride, np.float64, device).zero()
+        if self.rmod is not None:
+            a = self.chan._inloop
+            a.ToChanM3RunoffDt = self._side.ptr.value
+            if "QInM3Old" in structures:       # inflow hydrographs: QInM3Old / QDelta rows with the stride of the sideflow rows
+                self._qin_old = np.broadcast_to(f64(np.broadcast_to(structures["QInM3Old"], (Nk,))), (M, Nk)).copy()
+                for k in ("QInM3Old", "QDelta"):
+                    self._qin[k] = DeviceArray(M * self.kstride, np.float64, device)
+                    self._put_qin(k, np.broadcast_to(m._down(m._st["dev"][k].download()), (M, Nk)))
+                    setattr(a, k, self._qin[k].ptr.value)
+        self.steps_done = 0
+
+    # ---- orders ------------------------------------------------------------------------------------------------------------
+    def _ordered(self, a):
+        a = np.asarray(a)
+        if a.ndim == 0 or a.shape[-1] != self.N:
+            return a
+        return np.ascontiguousarray(a[..., self.pixel_of_position])
+
+    def _pixel_order(self, a):
+        if a.ndim == 0 or a.shape[-1] != self.N:
+            return a
+        out = np.empty_like(a)
+        out[..., self.pixel_of_position] = a
+        return out
+
+    def _put_qin(self, name, rows, staged=False):
+        """[members, Nk] in channel-domain pixel order -> the member rows of QInM3Old / QDelta"""
+        host = np.full((self.members, self.kstride), self._gap)
+        host[:, :self.Nk] = np.asarray(rows)[:, self.perm]
+        self._qin[name].upload(host.reshape(-1), staged=staged)
+
+    # ---- one model step ------------------------------------------------------------------------------------------------------
+    def set_lai(self, LAI, LAITerm):
+        """HotPathDevice.set_lai: the members share the two vectors"""
+        check(lib().lf_device_synchronize(self.device))
+        for k, a in (("LAI", LAI), ("LAITerm", LAITerm)):
+            a = np.asarray(a, np.float64)
+            if a.shape != (3, self.N):
+                raise ValueError("%s must be [3, %d]" % (k, self.N))
+            self.land.dev[k].upload(f64(self._ordered(a)))
+
+    def set_inflow(self, QInM3):
+        """HotPathDevice.set_inflow with QInM3 [N] (every member) or [members, N]"""
+        if self._qin_old is None:
+            raise RuntimeError("inflow hydrographs need structures= with QInM3Old / QDelta (the `inflow` option)")
+        q = np.asarray(QInM3, np.float64)
+        if q.shape not in ((self.N,), (self.members, self.N)):
+            raise ValueError("QInM3 must be [%d] or [%d, %d]" % (self.N, self.members, self.N))
+        q = np.broadcast_to(q, (self.members, self.N))
+        if self.Nk < self.N:
+            rest = np.ones(self.N, bool); rest[self.ids] = False
+            if np.any(q[:, rest] != 0):
+                raise ValueError("inflow at a pixel this object left out of the channel domain; flag the inflow pixels in "
+                                 "structures['InflowPoints'] or build it with compact=False")
+        q = np.ascontiguousarray(q[:, self.ids])
+        delta = (q - self._qin_old) * self.rmod.var.InvNoRoutSteps
+        L, d = lib(), self.device
+        if self.overlap_channel:           # on the channel loop's stream, behind the loop of the step before
+            check(L.lf_side_stream_begin(d))
+        try:
+            self._put_qin("QInM3Old", self._qin_old, staged=True)
+            self._put_qin("QDelta", delta, staged=True)
+        finally:
+            if self.overlap_channel:
+                check(L.lf_side_stream_end(d))
+        self._qin_old = q
+
+    def step(self, forcing, time_since_start=None, QInM3=None):
+        """forcing: dict of Rain, SnowMelt, EWRef, ETRef, ESRef, each [N] (every member) or [members, N], pixel order,
+        float64 -- or None: the forcing rows the device already holds (no PCIe traffic); QInM3 (structures= with inflow
+        hydrographs): [N] or [members, N]"""
+        if QInM3 is not None:
+            self.set_inflow(QInM3)
+        L, dev, E, M = lib(), self.device, self.land, self.members
+        for k in FORCING if forcing is not None else ():
+            a = np.asarray(forcing[k], np.float64)
+            if a.shape not in ((self.N,), (M, self.N)):
+                raise ValueError("forcing vector %s must be [%d] or [%d, %d]" % (k, self.N, M, self.N))
+        E.step(forcing and {k: self._ordered(np.asarray(forcing[k], np.float64)) for k in FORCING})          # dyn.py:114-123
+        self.steps_done += 1
+        self.pixel.TimeSinceStart = float(time_since_start if time_since_start else self.steps_done)
+        check(L.lf_pixel_aggregates_members_device(dev, C.byref(self.pixel), M, self.stride, self.pstride,
+                                                   E.forcing_member_stride()))                              # dyn.py:129-149
+        check(L.lf_surface_step_members(self.r_direct._h, self.r_other._h, self.r_forest._h, C.byref(self.surface), M,
+                                        self.stride, self.pstride))                                         # dyn.py:165
+        check(L.lf_side_stream_join(dev))         # (before the gather overwrites the sideflow of the loop of the step before)
+        check(L.lf_gather_rows_device(dev, self.Nk, self._gidx.ptr, E.dev["ToChanM3RunoffDt"].ptr, self.pstride,
+                                      self._side.ptr, self.kstride, M))
+        if self.overlap_channel:
+            check(L.lf_side_stream_begin(dev))
+        try:
+            sums, nsteps = self.chan.vectors.dev["sumDisDay"], int(self.sc["NoRoutSteps"])
+            for m in range(M):                    # dyn.py:177, row by row: the elements between the rows stay as they are
+                check(L.lf_memset(dev, sums.ptr.value + 8 * m * self.kstride, 0, 8 * self.Nk))
+            if self.rmod is not None:
+                self.river.routing_substeps_structures_members(self.chan.vectors.args, self.chan._inloop, nsteps, M, self.kstride,
+                                                               self.chan.n_lakes, self.chan.n_res, self.kstride)
+            else:
+                args = self.chan.vectors.with_overrides(SideflowChanM3=self._side.ptr.value)
+                self.river.routing_substeps_members(args, nsteps, M, self.kstride, 0, self.kstride)          # dyn.py:179-180
+        finally:
+            if self.overlap_channel:
+                check(L.lf_side_stream_end(dev))
+
+    def last_forms(self):
+        """the form every stage of the last step took: land / pixel_aggregates / overland 1 single call, 2 members in one
+        launch, 3 member after member; channel: the name of the schedule (kinematicWave.last_fused_form)"""
+        out = dict(land=self.land.last_form())
+        for stage, name in enumerate(("pixel_aggregates", "overland")):
+            rc = lib().lf_module_last_form(self.device, stage)
+            if rc < 0:
+                check(rc)
+            out[name] = rc
+        out["channel"] = self.chan.last_fused_form()
+        return out
+
+    # ---- vectors -------------------------------------------------------------------------------------------------------------
+    def _channel_rows(self, name):
+        """(device vector, entries of a row, stride) of a member vector of the channel part, or None"""
+        if name in ("SideflowChanM3", "ToChanM3RunoffDt") and (self.rmod is None or name == "ToChanM3RunoffDt"):
+            return self._side, self.Nk, self.kstride
+        if name in self._qin:
+            return self._qin[name], self.Nk, self.kstride
+        if name in self.chan._groups:
+            count, stride, _ = self.chan._groups[name]
+            return self.chan._inloop_dev[name], count, stride
+        if name in RT._STATE + RT._OUT:
+            return self.chan.vectors.dev[name], self.Nk, self.kstride
+        return None
+
+    def _rows_of(self, name):
+        """[members, width] rows as the device holds them (channel part), and what lies between them"""
+        d, width, stride = self._channel_rows(name)
+        flat = np.full(self.members * stride, np.nan)
+        a = d.download()
+        flat[:min(a.size, flat.size)] = a[:flat.size]
+        rows = flat.reshape(self.members, stride)
+        return rows[:, :width], rows[:, width:]
+
+    def _to_land(self, rows, engine):
+        """[members, Nk] (engine order, or channel-domain pixel order) -> [members, N]; pixels outside the channel domain: 0"""
+        out = np.zeros((rows.shape[0], self.N), rows.dtype)
+        out[:, self.gpix if engine else self.ids] = rows
+        return out
+
+    def download(self, name):
+        """[members, N] / [members, 3, N] in pixel order of a member vector, the array itself of a shared one; channel
+        vectors scattered to the land domain as HotPathDevice.download does"""
+        E = self.land
+        if name in E.dev and name != "scratch":
+            return self._pixel_order(E.get(name))
+        if name in self.chan._groups and self.chan._groups[name][2] or name in RT._STATE + RT._OUT + ["SideflowChanM3"]:
+            return self._to_land(self._rows_of(name)[0], True)
+        if name in RT._STATIC:
+            dev = self.chan.vectors.dev if self.rmod is None else self.rmod._dev
+            out = np.zeros(self.N, dev[name].dtype)
+            out[self.gpix] = dev[name].download()[:self.Nk]
+            return out
+        raise KeyError(name)
+
+    def download_site(self, name):
+        """[members, sites] of a lake / reservoir state vector, [members, N] of a dense in-loop vector; the shared site
+        parameters as they are"""
+        if self.rmod is None:
+            raise RuntimeError("download_site() needs structures=")
+        if self._channel_rows(name) is not None:
+            rows = self._rows_of(name)[0].copy()
+            return self._to_land(rows, True) if rows.shape[1] == self.Nk and name not in RT._LAKE_STATE + RT._RES_STATE else rows
+        a = self.rmod._st["dev"][name].download()
+        if a.size == self.Nk and name not in RT._LAKE_STATE + RT._RES_STATE:      # a dense vector the members share
+            out = np.zeros(self.N)
+            out[self.ids] = self.rmod._down(a)
+            return out
+        return a
+
+    def chan_q_avg(self):
+        """ChanQAvg of every member, [members, N]"""
+        return self.download("sumDisDay") / self.sc["NoRoutSteps"]
+
+    def state_names(self):
+        return [k for k in self.STATE if k in self.land.dev or k in RT._STATE]
+
+    def set_member_state(self, name, rows):
+        """a state vector of every member from [members, N] / [members, 3, N] in pixel order"""
+        if name not in self.state_names():
+            raise ValueError("%s is no state vector of this object" % name)
+        rows = np.asarray(rows, np.float64)
+        if name not in RT._STATE:
+            shape = (self.members, 3, self.N) if name in self.land._member else (self.members, self.N)
+            if rows.shape != shape:
+                raise ValueError("%s must be %s" % (name, list(shape)))
+            return self.land.set(name, self._ordered(rows))
+        if rows.shape != (self.members, self.N):
+            raise ValueError("%s must be [%d, %d]" % (name, self.members, self.N))
+        if self.Nk < self.N:
+            rest = np.ones(self.N, bool); rest[self.ids] = False
+            if np.any(rows[:, rest] != 0):
+                raise ValueError("state file holds water in %s on pixels this object left out of the channel "
+                                 "domain; build it with compact=False" % name)
+        self._set_channel_rows(name, rows[:, self.gpix])
+
+    def _set_channel_rows(self, name, rows):
+        """rows as the device holds them; the elements between them keep the gap value"""
+        d, width, stride = self._channel_rows(name)
+        host = np.full((self.members, stride), self._gap)
+        host[:, :width] = rows
+        d.upload(np.ascontiguousarray(host.reshape(-1)[:d.nbytes // 8]), prefix=False)
+
+    def gaps(self, name):
+        """[members, pad]: the elements between the members' rows of a member vector, which no call reads or writes (the
+        last member's gap of a channel vector may lie beyond the vector: NaN here)"""
+        if name in self.land.dev:
+            return self.land.gaps(name)
+        return self._rows_of(name)[1]
+
+    def gap_names(self):
+        """every vector that holds member rows"""
+        E = self.land
+        dense = [k for k, (_, _, pixels) in self.chan._groups.items() if pixels]      # (site-state rows lie back to back)
+        chan = RT._STATE + RT._OUT + dense + list(self._qin) + ["ToChanM3RunoffDt"]
+        return E._member + E._forcing + E._pixel + list(dict.fromkeys(chan))
+
+    def set_gaps(self, value):
+        """plant `value` between the members' rows of every member vector of every stage"""
+        check(lib().lf_device_synchronize(self.device))
+        self._gap = float(value)
+        self.land.set_gaps(value)
+        for name in self.gap_names():
+            if name not in self.land.dev:
+                self._set_channel_rows(name, self._rows_of(name)[0])
+        scratch = self.land.dev["scratch"]
+        host = scratch.download().reshape(3 * self.members, self.pstride)
+        host[:, self.N:] = self._gap
+        scratch.upload(host.reshape(-1))
+
+    # ---- warm start: HotPathDevice's state file with a leading member axis -------------------------------------------------
+    def save_state(self, path):
+        out = {k: self.download(k) for k in self.state_names()}
+        if self.rmod is not None:
+            for k in RT._LAKE_STATE + RT._RES_STATE + ["TransCum"]:
+                if k in self.chan._groups:
+                    out["site_" + k] = self.download_site(k)
+        out["steps_done"] = np.int64(self.steps_done)
+        if self._qin_old is not None:
+            out["qin_old"] = self._qin_old
+        np.savez(path, **out)
+
+    def load_state(self, path):
+        z = np.load(path)
+        for k in self.state_names():
+            if k not in z.files and k in OPTIONAL_MAPS:
+                continue
+            self.set_member_state(k, z[k])
+        if self.rmod is not None:
+            for k in RT._LAKE_STATE + RT._RES_STATE + ["TransCum"]:
+                if "site_" + k in z.files:
+                    a = z["site_" + k]
+                    self._set_channel_rows(k, a[:, self.gpix] if k == "TransCum" else a)
+        if "qin_old" in z.files and self._qin_old is not None:
+            self._qin_old = np.array(z["qin_old"], np.float64)
+        self.steps_done = int(z["steps_done"])
+
+    def free(self):
+        check(lib().lf_device_synchronize(self.device))
+        self.chan.free()
+        self.land.free()
+        for a in [self._gidx, self._side] + list(self._qin.values()):
+            a.free()
+        if self.rmod is not None:
+            arrays = {id(a): a for a in list(self.rmod._st["dev"].values()) + list(self.rmod._dev.values())}
+            for a in arrays.values():
+                a.free()
+        for r in (self.r_other, self.r_forest, self.r_direct, self.river):
+            r.close()

@@ -314,6 +314,21 @@ class kinematicWave:
         ls = (C.c_void_p * n)(*[x.ptr for x in lateral_devs])
         check(lib().lf_router_route_device_multi(n, hs, qs, ls, sec, 1 if engine_order else 0))
 
+    @staticmethod
+    def route_ordered_members_multi(routers, discharge_ord_devs, lateral_ord_devs, members, stride=None, section="main_channel"):
+        """route_together for an ensemble: router i sweeps the `members` rows (sweep order, `stride` elements apart, default N)
+        of its own two DeviceArrays, every launch once for all (router, member) units --
+        lf_router_route_ordered_members_multi; asynchronous."""
+        n = len(routers)
+        sec = kinematicWave._section(section)
+        stride = routers[0].num_pixels if stride is None else int(stride)
+        for r, q, x in zip(routers, discharge_ord_devs, lateral_ord_devs):
+            members = r._member_rows(members, stride, q, x)
+        hs = (C.c_void_p * n)(*[r._h for r in routers])
+        qs = (C.c_void_p * n)(*[q.ptr for q in discharge_ord_devs])
+        ls = (C.c_void_p * n)(*[x.ptr for x in lateral_ord_devs])
+        check(lib().lf_router_route_ordered_members_multi(n, hs, qs, ls, members, stride, sec))
+
     def _warn(self):
         self.kinematic_wave_warning_printed = True
         warnings.warn(LisfloodWarning("Warning: NaN or Inf values after kinematicRouting module. Suggestion: please "

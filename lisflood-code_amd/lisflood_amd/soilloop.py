@@ -365,7 +365,9 @@ class _EnsembleVectors:
     """The device vectors of an ensemble call (lf_soil_columns_members_device / lf_land_columns_members_device): a member's
     own [V,N] rows `stride` = V*N + pad elements apart, its forcing `fstride` = N + pad elements apart, everything else
     once.  A shared forcing vector is kept in every member's row all the same, so that a later per-member one needs no
-    re-layout; the call passes forcing_member_stride = 0 while every forcing vector is shared."""
+    re-layout; the call passes forcing_member_stride = 0 while every forcing vector is shared.  `_pixel` names a member's own
+    [N] rows, laid out like its forcing rows (fstride apart): none here, the states and outputs of the per-pixel stages
+    behind the land surface in hotpath.HotPathEnsemble."""
 
     def _setup(self, members, V, N, device, pad):
         self.members, self.V, self.N, self.device, self.pad = int(members), V, N, device, int(pad)
@@ -373,7 +375,7 @@ class _EnsembleVectors:
             raise ValueError("members must be at least 1 and pad not negative")
         self.stride, self.fstride = V * N + self.pad, N + self.pad
         self.dev, self.shared = {}, {}
-        self._member, self._forcing, self._static = [], [], []
+        self._member, self._forcing, self._static, self._pixel = [], [], [], []
         self._shared_forcing = {}
         self._gap = 0.0
 
@@ -397,6 +399,8 @@ class _EnsembleVectors:
             value = u8(value) if byte else f64(value)
             self._shared_forcing[name] = value.ndim == 1
             host = self._layout(name, value, self.N, self.fstride, np.uint8 if byte else np.float64)
+        elif name in self._pixel:
+            host = self._layout(name, f64(value), self.N, self.fstride, np.float64)
         else:
             raise ValueError("%s is one of the arrays the members share: it is static" % name
                              if name in self._static else "%s is no vector of this call" % name)
@@ -419,7 +423,7 @@ class _EnsembleVectors:
             return np.ascontiguousarray(out.reshape(self.members, self.stride)[:, :self.N])
         if name in self._member:
             return np.ascontiguousarray(out.reshape(self.members, self.stride)[:, :self.V * self.N]).reshape(self.members, self.V, self.N)
-        if name in self._forcing:
+        if name in self._forcing or name in self._pixel:
             return np.ascontiguousarray(out.reshape(self.members, self.fstride)[:, :self.N])
         return out
 
@@ -437,7 +441,7 @@ class _EnsembleVectors:
     def set_gaps(self, value):
         """plant `value` (GAP_BYTE in byte vectors) between the members' rows of every vector"""
         self._gap = float(value)
-        for name in self._member + self._forcing:
+        for name in self._member + self._forcing + self._pixel:
             host = self.dev[name].download()
             width, stride = (self.V * self.N, self.stride) if name in self._member else (self.N, self.fstride)
             host.reshape(self.members, stride)[:, width:] = GAP_BYTE if host.dtype == np.uint8 else self._gap
