@@ -90,6 +90,17 @@ int lf_upload_copy(int device, void *dst_dev, const void *src_host, size_t bytes
 /* the same for a vector the caller holds as float32 (the reference's meteo files are float32; readnetcdf widens them on the
  * host): half the bytes over PCIe, widened to fp64 on the device behind the copy -- the same exact conversion */
 int lf_upload_copy_f32(int device, double *dst_dev, const float *src_host, size_t count);
+/* the same for the member rows of an ensemble's forcing vector, which the caller holds in PIXEL order: for r < rows, i < n
+ *     dst[r * dst_stride + i] = (double)src[(src_rows == 1 ? 0 : r) * n + (index_dev ? index_dev[i] : i)]
+ * src_host: src_rows x n dense values, float32 if src_f32 = 1, float64 if 0; src_rows is 1 (one row for every member) or
+ * rows.  The raw image goes up by ONE asynchronous copy into a staging buffer kept per destination (grow-only, freed with
+ * the destination and by lf_device_trim; shared with lf_upload_copy_f32); a kernel on the copy stream behind it gathers
+ * through the index table (position -> pixel, on the device; NULL: identity), widens and writes the rows -- no host
+ * permutation, no host widening, no padded host image.  Elements n .. dst_stride - 1 of a row are never written.
+ * LF_E_INVALID, with the argument named, before a device is touched: rows < 1, src_rows not 1 or rows, src_f32 not 0 / 1,
+ * n < 0 or beyond the 32-bit range of a launch, dst_stride < n, dst_dev or src_host NULL with n > 0. */
+int lf_upload_rows(int device, double *dst_dev, int64_t dst_stride, int rows, const void *src_host, int src_rows, int src_f32,
+                   int64_t n, const int32_t *index_dev);
 int lf_upload_end(int device, int set);
 /* host side of the protocol: blocks until the copies of the last lf_upload_begin(set) .. lf_upload_end(set) have finished.
  * Call it before refilling, in place, a page-locked source buffer that was handed to lf_upload_copy for `set` (the copy is

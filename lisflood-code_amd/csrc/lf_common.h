@@ -50,7 +50,8 @@ struct lf_device_ctx {
     // upload stream for double-buffered inputs (lf_upload_*): copies of the NEXT step's forcing overlap the kernels of
     // the current one; per buffer set an event "copy finished" and an event "last kernel reading the set finished"
     hipStream_t copy_stream = nullptr;
-    std::map<void *, std::pair<void *, size_t>> f32_stage; // lf_upload_copy_f32: fp32 staging buffer per destination vector
+    // lf_upload_copy_f32, lf_upload_rows: staging buffer (device pointer, bytes) of the raw host image per destination vector
+    std::map<void *, std::pair<void *, size_t>> upload_stage;
     hipEvent_t copied[2] = {nullptr, nullptr}, consumed[2] = {nullptr, nullptr};
     bool consumed_valid[2] = {false, false}, copied_valid[2] = {false, false};
     // page-locked staging ring of lf_memcpy_h2d_staged: small per-step uploads that must not stall the host

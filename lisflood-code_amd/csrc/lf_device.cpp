@@ -111,12 +111,12 @@ int lf_device_free(int device, void *ptr_dev)
     lf_device_ctx *c = nullptr;
     LF_TRY(lf_ctx(device, &c));
     if (!ptr_dev) return LF_OK;
-    if (c) { // the fp32 staging buffer of lf_upload_copy_f32 for this vector goes with it
-        auto st = c->f32_stage.find(ptr_dev);
-        if (st != c->f32_stage.end()) {
+    if (c) { // the staging buffer of lf_upload_copy_f32 / lf_upload_rows for this vector goes with it
+        auto st = c->upload_stage.find(ptr_dev);
+        if (st != c->upload_stage.end()) {
             if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
             if (st->second.first) (void)hipFree(st->second.first);
-            c->f32_stage.erase(st);
+            c->upload_stage.erase(st);
         }
     }
     void *base = ptr_dev;
@@ -240,24 +240,135 @@ __global__ void k_widen_f32(long long n, const float *__restrict__ src, double *
     if (i < n) dst[i] = (double)src[i];
 }
 
+// The staging buffer of a destination vector (lf_upload_copy_f32, lf_upload_rows), at least `bytes` long: grow-only, one per
+// destination, freed with it (lf_device_free) and by lf_device_trim.  Every user is on the copy stream, so a buffer that
+// is kept is reused in stream order; before one is replaced the stream is drained (a copy into it, or a kernel reading
+// it, may still be in flight).
+static int upload_stage_for(lf_device_ctx *c, void *dst_dev, size_t bytes, void **out)
+{
+    auto &st = c->upload_stage[dst_dev];
+    if (st.second < bytes) {
+        LF_HIP(hipStreamSynchronize(c->copy_stream));
+        if (st.first) (void)hipFree(st.first);
+        st.first = nullptr;
+        st.second = 0;
+        LF_HIP(hipMalloc(&st.first, bytes));
+        st.second = bytes;
+    }
+    *out = st.first;
+    return LF_OK;
+}
+
 int lf_upload_copy_f32(int device, double *dst_dev, const float *src_host, size_t count)
 {
     if (!dst_dev || (!src_host && count)) return lf_set_error(LF_E_INVALID, "null argument");
     lf_device_ctx *c;
     LF_TRY(upload_ctx(device, 0, &c));
     if (!count) return LF_OK;
-    auto &st = c->f32_stage[(void *)dst_dev];
-    if (st.second < count * sizeof(float)) {
-        LF_HIP(hipStreamSynchronize(c->copy_stream)); // (a copy into the old buffer may still be in flight)
-        if (st.first) (void)hipFree(st.first);
-        st.first = nullptr;
-        st.second = 0;
-        LF_HIP(hipMalloc(&st.first, count * sizeof(float)));
-        st.second = count * sizeof(float);
-    }
-    LF_HIP(hipMemcpyAsync(st.first, src_host, count * sizeof(float), hipMemcpyHostToDevice, c->copy_stream));
+    void *stage = nullptr;
+    LF_TRY(upload_stage_for(c, (void *)dst_dev, count * sizeof(float), &stage));
+    LF_HIP(hipMemcpyAsync(stage, src_host, count * sizeof(float), hipMemcpyHostToDevice, c->copy_stream));
     hipLaunchKernelGGL(k_widen_f32, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, c->copy_stream, (long long)count,
-                       (const float *)st.first, dst_dev);
+                       (const float *)stage, dst_dev);
+    LF_HIP(hipGetLastError());
+    return LF_OK;
+}
+
+// Member rows of a forcing vector as the caller holds them -- pixel order, float32 or float64, one row for all members or
+// one each -- into the rows of the device vector: dst[r * dst_stride + i] = (double)src[(ONE ? 0 : r) * n + index[i]].  What
+// the host did before (permute, widen, lay out a padded image) is this kernel behind the raw copy, on the copy stream.
+// blockIdx.x: 256 positions; blockIdx.y: a slice of up to kUploadRowSlice rows.  A lane owns position i of every row of its
+// slice: it reads index[i] once, issues the gather loads of all rows (independent, one wait) and then stores row by row,
+// each store a full line of consecutive positions.  ONE: a single source row, one load and a store per row.
+extern "C++" {
+constexpr int kUploadRowSlice = 8;
+constexpr int kUploadMaxGridY = 65535; // (row slices beyond it: further launches)
+
+// COUNT rows of one lane, straight-line: COUNT loads, then COUNT stores
+template <typename T, int COUNT>
+__device__ __forceinline__ void upload_rows_slice(const T *__restrict__ in, long long n, double *__restrict__ out, long long dst_stride)
+{
+    T v[COUNT];
+#pragma unroll
+    for (int k = 0; k < COUNT; ++k) v[k] = in[k * n];
+#pragma unroll
+    for (int k = 0; k < COUNT; ++k) out[k * dst_stride] = (double)v[k];
+}
+
+template <typename T, bool ONE>
+__global__ void __launch_bounds__(256)
+    k_upload_rows(int n, int rows, const int *__restrict__ index, const T *__restrict__ src, double *__restrict__ dst,
+                  long long dst_stride)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int r0 = (int)blockIdx.y * kUploadRowSlice;
+    const int count = min(rows - r0, kUploadRowSlice); // (the same for every lane of the launch's row slice)
+    const long long j = index ? (long long)index[i] : i;
+    double *out = dst + (long long)r0 * dst_stride + i;
+    if (ONE) {
+        const double v = (double)src[j];
+        for (int k = 0; k < count; ++k) out[k * dst_stride] = v;
+        return;
+    }
+    const T *in = src + (long long)r0 * n + j;
+    static_assert(kUploadRowSlice == 8, "one case per row count of a slice");
+    switch (count) {
+    case 8: return upload_rows_slice<T, 8>(in, n, out, dst_stride);
+    case 7: return upload_rows_slice<T, 7>(in, n, out, dst_stride);
+    case 6: return upload_rows_slice<T, 6>(in, n, out, dst_stride);
+    case 5: return upload_rows_slice<T, 5>(in, n, out, dst_stride);
+    case 4: return upload_rows_slice<T, 4>(in, n, out, dst_stride);
+    case 3: return upload_rows_slice<T, 3>(in, n, out, dst_stride);
+    case 2: return upload_rows_slice<T, 2>(in, n, out, dst_stride);
+    default: return upload_rows_slice<T, 1>(in, n, out, dst_stride);
+    }
+}
+
+template <typename T>
+static void upload_rows_launch(hipStream_t s, int n, int rows, bool one, const int *index, const T *src, double *dst,
+                               int64_t dst_stride)
+{
+    const int slices = (rows + kUploadRowSlice - 1) / kUploadRowSlice;
+    for (int s0 = 0; s0 < slices; s0 += kUploadMaxGridY) { // (one launch unless there are more slices than a grid has)
+        const int r0 = s0 * kUploadRowSlice, rr = std::min(rows - r0, kUploadMaxGridY * kUploadRowSlice);
+        const dim3 grid((unsigned)(((int64_t)n + 255) / 256), (unsigned)std::min(slices - s0, kUploadMaxGridY));
+        double *d = dst + (int64_t)r0 * dst_stride;
+        if (one)
+            hipLaunchKernelGGL((k_upload_rows<T, true>), grid, dim3(256), 0, s, n, rr, index, src, d, (long long)dst_stride);
+        else
+            hipLaunchKernelGGL((k_upload_rows<T, false>), grid, dim3(256), 0, s, n, rr, index, src + (int64_t)r0 * n, d,
+                               (long long)dst_stride);
+    }
+}
+} // extern "C++"
+
+int lf_upload_rows(int device, double *dst_dev, int64_t dst_stride, int rows, const void *src_host, int src_rows, int src_f32,
+                   int64_t n, const int32_t *index_dev)
+{
+    if (rows < 1) return lf_set_error(LF_E_INVALID, "upload rows: rows must be at least 1 (got %d)", rows);
+    if (src_rows != 1 && src_rows != rows)
+        return lf_set_error(LF_E_INVALID, "upload rows: src_rows must be 1 or rows = %d (got %d)", rows, src_rows);
+    if (src_f32 != 0 && src_f32 != 1) return lf_set_error(LF_E_INVALID, "upload rows: src_f32 must be 0 or 1 (got %d)", src_f32);
+    if (n < 0 || n > 0x7fffffffll)
+        return lf_set_error(LF_E_INVALID, "upload rows: n = %lld outside the 32-bit range of a launch", (long long)n);
+    if (dst_stride < n)
+        return lf_set_error(LF_E_INVALID, "upload rows: dst_stride %lld is less than n = %lld", (long long)dst_stride, (long long)n);
+    if (n > 0 && !dst_dev) return lf_set_error(LF_E_INVALID, "upload rows: dst_dev is NULL");
+    if (n > 0 && !src_host) return lf_set_error(LF_E_INVALID, "upload rows: src_host is NULL");
+    lf_device_ctx *c;
+    LF_TRY(upload_ctx(device, 0, &c));
+    if (n == 0) return LF_OK;
+    const size_t bytes = (size_t)src_rows * (size_t)n * (src_f32 ? sizeof(float) : sizeof(double));
+    void *stage = nullptr;
+    LF_TRY(upload_stage_for(c, (void *)dst_dev, bytes, &stage));
+    LF_HIP(hipMemcpyAsync(stage, src_host, bytes, hipMemcpyHostToDevice, c->copy_stream));
+    if (src_f32)
+        upload_rows_launch(c->copy_stream, (int)n, rows, src_rows == 1, (const int *)index_dev, (const float *)stage, dst_dev,
+                           dst_stride);
+    else
+        upload_rows_launch(c->copy_stream, (int)n, rows, src_rows == 1, (const int *)index_dev, (const double *)stage, dst_dev,
+                           dst_stride);
     LF_HIP(hipGetLastError());
     return LF_OK;
 }
@@ -420,8 +531,8 @@ int lf_side_stream_join(int device)
     return side_join(c);
 }
 
-// Releases what the context created on demand and keeps for reuse: the lane streams and their events, the fp32 staging
-// buffers of lf_upload_copy_f32, the staging arena of the *_host entry points.  Waits for the device first; refuses inside
+// Releases what the context created on demand and keeps for reuse: the lane streams and their events, the staging
+// buffers of lf_upload_copy_f32 / lf_upload_rows, the staging arena of the *_host entry points.  Waits for the device first; refuses inside
 // a lane or side section.  Everything is created again on next use.
 int lf_device_trim(int device)
 {
@@ -437,9 +548,9 @@ int lf_device_trim(int device)
     c->lanes.clear();
     c->lane_done.clear();
     c->lane_used.clear();
-    for (auto &kv : c->f32_stage)
+    for (auto &kv : c->upload_stage)
         if (kv.second.first) (void)hipFree(kv.second.first);
-    c->f32_stage.clear();
+    c->upload_stage.clear();
     if (c->stage_base) (void)hipFree(c->stage_base);
     c->stage_base = nullptr;
     c->stage_bytes = 0;

@@ -42,6 +42,7 @@ _SIGNATURES = {
     "ipppiqi": "router_route_ordered_members_multi",
     "ippqi": "calibration_copy",
     "ippz": "memcpy_h2d memcpy_h2d_staged upload_copy upload_copy_f32 memcpy_d2h memcpy_d2d",
+    "ipqipiiqp": "upload_rows",
     "ipqp": "count_nonfinite",
     "ipz": "device_name",
     "iqppp": "gather_device",

@@ -783,12 +783,16 @@ class HotPathEnsemble:
     up, bit for bit, as a HotPathDevice of its own fed the same forcing.
     With structures= the channel part is the routing module HotPathDevice builds, on the compact channel domain with the
     subset already applied, and its routing.ensemble(members).
-    Not in this class (HotPathDevice has them): prefetch / pinned_forcing (the double-buffered upload), step_profile,
-    state_maps / load_state_maps and mass_balance.  The forcing of step(forcing) goes up with blocking copies on the main
-    stream (lf_memcpy_h2d), which wait for the side stream as well: with overlap_channel the channel loop of a step therefore
-    ends before the kernels of the next step start, and the overlap HotPathDevice gets from its second stream is lost; only
-    step(None) -- the forcing rows the device already holds, what the measurement tool times as the device's own work --
-    keeps it."""
+    Forcing: there are two sets of member rows of Rain, SnowMelt, EWRef, ETRef and ESRef.  step(forcing) and
+    prefetch(forcing) hand the vectors over as the caller holds them -- pixel order, [N] or [members, N], float32 or float64,
+    any mix -- with one lf_upload_rows per vector into the set that is NOT in use: one asynchronous copy of the raw image on
+    the copy stream and, behind it, a kernel that gathers into sweep order, widens and writes every member's row.  Nothing
+    is permuted, widened or laid out on the host, and nothing waits for the main or the side stream: with overlap_channel the
+    channel loop of a step runs beside the upload and the land surface of the step after it.  The step then switches to
+    that set (lf_compute_acquire .. lf_compute_release around the kernels that read forcing); step(None) stays on the set
+    in use, i.e. repeats the forcing of the step before.  pinned_forcing() gives page-locked arrays to fill in place,
+    upload_wait() says when they may be refilled -- HotPathDevice's protocol.
+    Not in this class (HotPathDevice has them): step_profile, state_maps / load_state_maps and mass_balance."""
 
     STATE = HotPathDevice.STATE
     _kept = HotPathDevice._kept
@@ -919,6 +923,14 @@ class HotPathEnsemble:
                     self._qin[k] = DeviceArray(M * self.kstride, np.float64, device)
                     self._put_qin(k, np.broadcast_to(m._down(m._st["dev"][k].download()), (M, Nk)))
                     setattr(a, k, self._qin[k].ptr.value)
+        # ---- forcing: two sets of member rows; set 0 is the land surface's own vectors (see prefetch) -------------------
+        self.force = [{k: E.dev[k] for k in FORCING},
+                      {k: DeviceArray(M * self.pstride, np.float64, device).zero() for k in FORCING}]
+        self._shared = [{k: E._shared_forcing[k] for k in FORCING}, {k: True for k in FORCING}]
+        self._cur, self._prefetched, self._keep, self._pinned = 0, None, [None, None], []
+        # position -> pixel, for the upload (a blocking copy on the main stream: the memsets of set 1 have ended with it,
+        # before the copy stream can write the set)
+        self._pidx = DeviceArray.from_host(self.pixel_of_position.astype(np.int32), device)
         self.steps_done = 0
 
     # ---- orders ------------------------------------------------------------------------------------------------------------
@@ -977,24 +989,84 @@ class HotPathEnsemble:
                 check(L.lf_side_stream_end(d))
         self._qin_old = q
 
+    # ---- forcing: two sets of member rows, uploaded on the copy stream and ordered on the device ----------------------------
+    def _upload(self, b, forcing):
+        """the five vectors as the caller holds them into set b: one lf_upload_rows each (raw copy + gather / widen kernel on
+        the copy stream, behind the kernels that last read set b); the host arrays stay alive until the set is uploaded again"""
+        L, dev, M, N = lib(), self.device, self.members, self.N
+        host = []
+        for k in FORCING:
+            a = np.asarray(forcing[k])
+            if a.shape not in ((N,), (M, N)):
+                raise ValueError("forcing vector %s must be [%d] or [%d, %d]" % (k, N, M, N))
+            host.append(np.ascontiguousarray(a) if a.dtype == np.float32 else f64(a))
+        check(L.lf_upload_begin(dev, b))
+        try:
+            for k, a in zip(FORCING, host):
+                check(L.lf_upload_rows(dev, self.force[b][k].ptr, self.pstride, M, a.ctypes.data_as(C.c_void_p),
+                                       1 if a.ndim == 1 else M, 1 if a.dtype == np.float32 else 0, N, self._pidx.ptr))
+                self._shared[b][k] = a.ndim == 1
+        finally:
+            check(L.lf_upload_end(dev, b))
+        self._keep[b] = host
+
+    def _use_set(self, b):
+        """point the argument blocks of the stages that read forcing, and the land surface's own table, at set b"""
+        E = self.land
+        for k in FORCING:
+            E.dev[k] = self.force[b][k]
+            for st in (E.canopy, E.soil, self.pixel):
+                if hasattr(type(st), k):
+                    setattr(st, k, self.force[b][k].ptr.value)
+        E._shared_forcing.update(self._shared[b])
+        self._cur = b
+
+    def forcing_member_stride(self):
+        """0 exactly when every forcing vector of the set in use (and isFrozenSoil) is one row for all members"""
+        return self.land.forcing_member_stride()
+
+    def pinned_forcing(self, dtype=np.float64, per_member=True):
+        """HotPathDevice.pinned_forcing for the ensemble: a forcing dict of page-locked [members, N] arrays ([N] with
+        per_member=False) in pixel order, to be filled in place and passed to prefetch() / step().  The DMA reads them after
+        the call has returned: upload_wait() before refilling a set that was handed over (or alternate between two sets)."""
+        shape = (self.members, self.N) if per_member else (self.N,)
+        bufs = {k: PinnedArray(shape, dtype, self.device) for k in FORCING}
+        self._pinned.append(bufs)
+        return {k: b.a for k, b in bufs.items()}
+
+    upload_wait = HotPathDevice.upload_wait
+
+    def prefetch(self, forcing):
+        """Start uploading the forcing of the NEXT step(forcing) call now, into the set that is not in use: the copy and the
+        ordering kernel run on the copy stream while the kernels of the step just enqueued are still executing.  Pass the
+        same dict object to that step(); a step(None) in between stays on the set in use and leaves the prefetch pending."""
+        self._upload(1 - self._cur, forcing)
+        self._prefetched = forcing
+
     def step(self, forcing, time_since_start=None, QInM3=None):
         """forcing: dict of Rain, SnowMelt, EWRef, ETRef, ESRef, each [N] (every member) or [members, N], pixel order,
-        float64 -- or None: the forcing rows the device already holds (no PCIe traffic); QInM3 (structures= with inflow
+        float32 or float64 -- or None: the forcing rows of the step before (no PCIe traffic); QInM3 (structures= with inflow
         hydrographs): [N] or [members, N]"""
         if QInM3 is not None:
             self.set_inflow(QInM3)
         L, dev, E, M = lib(), self.device, self.land, self.members
-        for k in FORCING if forcing is not None else ():
-            a = np.asarray(forcing[k], np.float64)
-            if a.shape not in ((self.N,), (M, self.N)):
-                raise ValueError("forcing vector %s must be [%d] or [%d, %d]" % (k, self.N, M, self.N))
-        E.step(forcing and {k: self._ordered(np.asarray(forcing[k], np.float64)) for k in FORCING})          # dyn.py:114-123
-        self.steps_done += 1
-        self.pixel.TimeSinceStart = float(time_since_start if time_since_start else self.steps_done)
-        check(L.lf_pixel_aggregates_members_device(dev, C.byref(self.pixel), M, self.stride, self.pstride,
-                                                   E.forcing_member_stride()))                              # dyn.py:129-149
-        check(L.lf_surface_step_members(self.r_direct._h, self.r_other._h, self.r_forest._h, C.byref(self.surface), M,
-                                        self.stride, self.pstride))                                         # dyn.py:165
+        if forcing is not None:
+            if self._prefetched is not forcing:
+                self._upload(1 - self._cur, forcing)
+            self._prefetched = None
+            self._use_set(1 - self._cur)
+        b = self._cur
+        check(L.lf_compute_acquire(dev, b))
+        try:
+            E.step()                                                                                        # dyn.py:114-123
+            self.steps_done += 1
+            self.pixel.TimeSinceStart = float(time_since_start if time_since_start else self.steps_done)
+            check(L.lf_pixel_aggregates_members_device(dev, C.byref(self.pixel), M, self.stride, self.pstride,
+                                                       E.forcing_member_stride()))                          # dyn.py:129-149
+            check(L.lf_surface_step_members(self.r_direct._h, self.r_other._h, self.r_forest._h, C.byref(self.surface), M,
+                                            self.stride, self.pstride))                                     # dyn.py:165
+        finally:                                  # (nothing behind this point reads forcing: set b may be uploaded again)
+            check(L.lf_compute_release(dev, b))
         check(L.lf_side_stream_join(dev))         # (before the gather overwrites the sideflow of the loop of the step before)
         check(L.lf_gather_rows_device(dev, self.Nk, self._gidx.ptr, E.dev["ToChanM3RunoffDt"].ptr, self.pstride,
                                       self._side.ptr, self.kstride, M))
@@ -1118,9 +1190,14 @@ class HotPathEnsemble:
         host[:, :width] = rows
         d.upload(np.ascontiguousarray(host.reshape(-1)[:d.nbytes // 8]), prefix=False)
 
-    def gaps(self, name):
+    def gaps(self, name, buffer_set=None):
         """[members, pad]: the elements between the members' rows of a member vector, which no call reads or writes (the
-        last member's gap of a channel vector may lie beyond the vector: NaN here)"""
+        last member's gap of a channel vector may lie beyond the vector: NaN here).  A forcing vector: of the set in use,
+        or of buffer_set 0 / 1 (waits for an upload into that set)"""
+        if buffer_set is not None:
+            self.upload_wait(buffer_set)
+            rows = self.force[int(buffer_set)][name].download().reshape(self.members, self.pstride)
+            return rows[:, self.N:]
         if name in self.land.dev:
             return self.land.gaps(name)
         return self._rows_of(name)[1]
@@ -1137,6 +1214,10 @@ class HotPathEnsemble:
         check(lib().lf_device_synchronize(self.device))
         self._gap = float(value)
         self.land.set_gaps(value)
+        for d in self.force[1 - self._cur].values():          # (the land surface has planted it in the set in use)
+            host = d.download().reshape(self.members, self.pstride)
+            host[:, self.N:] = self._gap
+            d.upload(host.reshape(-1))
         for name in self.gap_names():
             if name not in self.land.dev:
                 self._set_channel_rows(name, self._rows_of(name)[0])
@@ -1176,8 +1257,12 @@ class HotPathEnsemble:
         check(lib().lf_device_synchronize(self.device))
         self.chan.free()
         self.land.free()
-        for a in [self._gidx, self._side] + list(self._qin.values()):
+        for a in [self._gidx, self._side, self._pidx] + list(self._qin.values()) + list(self.force[1 - self._cur].values()):
             a.free()
+        for bufs in self._pinned:                 # (after the synchronize: no upload is still reading them)
+            for b in bufs.values():
+                b.free()
+        self._pinned = []
         if self.rmod is not None:
             arrays = {id(a): a for a in list(self.rmod._st["dev"].values()) + list(self.rmod._dev.values())}
             for a in arrays.values():
