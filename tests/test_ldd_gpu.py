@@ -70,9 +70,9 @@ def test_downstream_catchment_totals_vs_walks(amd):
 
 @pytest.mark.parametrize("family,seed", [("deep", 2), ("river", 7), ("shallow", 1)])
 def test_accuflux_on_level_blocks_equals_the_level_schedule(amd, family, seed, monkeypatch):
-    """accuflux runs on the router's block plan (blocks of up to 64 levels cone by cone through LDS, k_accu_cones): the
-    same additions in the same order as one launch per level (LF_ROUTE_CONES=0) -- bit-identical, and equal to the
-    brute-force sum over every cell's upstream tree"""
+    """accuflux runs on the router's block plan (blocks of up to 256 levels, the default of plain router calls, cone by cone
+    through LDS in chunks of up to 48 levels, k_accu_cones): the same additions in the same order as one launch per level
+    (LF_ROUTE_CONES=0) -- bit-identical, and equal to the brute-force sum over every cell's upstream tree"""
     from lisflood_amd import synthetic as syn
     from lisflood_amd.kinematic_wave_parallel import Graph, kinematicWave
     H, W = 700, 600
@@ -81,7 +81,7 @@ def test_accuflux_on_level_blocks_equals_the_level_schedule(amd, family, seed, m
     kw = kinematicWave(None, None, np.ones(N), 0.6, 1.0, 1.0, graph=Graph(ldd_raster=codes))
     x = np.random.default_rng(8).uniform(0, 3, N)
     got = kw.accuflux(x)
-    assert kw.last_launches()["launches"] <= kw.graph.num_levels // 32 + 8      # blocks of up to 64 levels, not levels
+    assert kw.last_launches()["launches"] <= kw.graph.num_levels // 32 + 8      # a launch per block of levels, not per level
     monkeypatch.setenv("LF_ROUTE_CONES", "0")
     ref = kw.accuflux(x)
     assert np.array_equal(got, ref)
