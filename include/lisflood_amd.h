@@ -750,6 +750,9 @@ int lf_dist_router_create(const lf_dist_graph *g, const double *alpha, double be
 void lf_dist_router_destroy(lf_dist_router *r);
 int64_t lf_dist_router_state_size(const lf_dist_router *r);
 int64_t lf_dist_router_last_launches(const lf_dist_router *r);
+/* schedule of the last fused phase that had cells on this router, as lf_router_last_fused_form: 1 time-major, 2 level
+ * blocks, 3 levels (0: none yet) */
+int lf_dist_router_last_fused_form(const lf_dist_router *r);
 int lf_dist_router_to_engine_order(lf_dist_router *r, const double *src_pix_dev, double *dst_ord_dev);
 int lf_dist_router_from_engine_order(lf_dist_router *r, const double *src_ord_dev, double *dst_pix_dev);
 /* one kinematicWaveRouting call; q_ord_dev has lf_dist_router_state_size entries (local cells in engine
@@ -798,6 +801,9 @@ int lf_dist_fused_exchange(lf_dist_router *r, lf_comm *comm, int round, int spli
  * bottom, [5] first slot of the local cells that feed a later phase; and the tables by position (tests) */
 int lf_dist_graph_slab_layout(const lf_dist_graph *g, int64_t out[6]);
 int lf_dist_graph_get_fused_tables(const lf_dist_graph *g, int32_t *out_slot, int32_t *ups_idx_f);
+/* ups_base[N] by position, as the routers upload it: >= 0 = the cell's upstream cells are the consecutive run that starts
+ * there, all of them ghost slots or local cells of the cell's own phase; -1 = they come from its list */
+int lf_dist_graph_get_ups_base(const lf_dist_graph *g, int32_t *ups_base);
 /* level blocks of the fused path (per phase, cone by cone): out = {blocks, blocks of more than one level, cones, entries
  * of the cone table}; all 0 when no block holds more than one level (then: one launch per level and sub-step wave) */
 int lf_dist_graph_block_stats(const lf_dist_graph *g, int64_t out[4]);

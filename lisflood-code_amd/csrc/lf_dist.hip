@@ -387,14 +387,17 @@ int lf_dist_graph_finalize(lf_dist_graph *g, int nphases)
             g->ups_idx[cursor[g->ghost_target[1][i]]++] = (int32_t)(n + ghost_slot[1][i]);
     }
     // the (phase, level, breadth-first rank) order leaves the upstream positions of nearly every cell consecutive:
-    // those cells read their inflow as a coalesced run, only the others (ghost or cross-phase inflow) go through the list
+    // those cells read their inflow as a coalesced run, only the others (ghost or cross-phase inflow) go through the list.
+    // A run that holds a local cell of ANOTHER phase is not one, consecutive or not (the last cell of a phase and the first
+    // of the next are neighbours in the layout): the fused sub-step kernels read a run from where only the cell's own phase
+    // has its values (parity buffers, LDS, the history); plain calls merely take the list, the same addends in the same order
     g->ups_base.assign(n, 0);
     g->n_noncontiguous = 0;
     for (int64_t p = 0; p < n; ++p) {
-        const int32_t a = g->ups_ptr[p], b = g->ups_ptr[p + 1];
+        const int32_t a = g->ups_ptr[p], b = g->ups_ptr[p + 1], ph = g->phase[g->perm[p]];
         int32_t base = (b > a) ? g->ups_idx[a] : 0;
         for (int32_t k = a; k < b; ++k)
-            if (g->ups_idx[k] != base + (k - a)) {
+            if (g->ups_idx[k] != base + (k - a) || (g->ups_idx[k] < n && g->phase[g->perm[g->ups_idx[k]]] != ph)) {
                 base = -1;
                 break;
             }
@@ -614,6 +617,14 @@ int lf_dist_graph_get_fused_tables(const lf_dist_graph *g, int32_t *out_slot, in
     if (!g || !g->finalized) return lf_set_error(LF_E_INVALID, "graph not finalized");
     if (out_slot) std::memcpy(out_slot, g->out_slot.data(), sizeof(int32_t) * g->out_slot.size());
     if (ups_idx_f) std::memcpy(ups_idx_f, g->ups_idx_f.data(), sizeof(int32_t) * g->ups_idx_f.size());
+    return LF_OK;
+}
+// ups_base[N] by position, the table the routers upload: a cell whose entry is >= 0 reads its upstream cells as the run
+// [entry, entry + count) -- the fused kernels only when the run ends inside the N local cells -- and from its list otherwise
+int lf_dist_graph_get_ups_base(const lf_dist_graph *g, int32_t *ups_base)
+{
+    if (!g || !g->finalized || !ups_base) return lf_set_error(LF_E_INVALID, "graph not finalized");
+    std::memcpy(ups_base, g->ups_base.data(), sizeof(int32_t) * g->ups_base.size());
     return LF_OK;
 }
 
@@ -927,6 +938,8 @@ void lf_dist_router_destroy(lf_dist_router *r)
 
 int64_t lf_dist_router_state_size(const lf_dist_router *r) { return r ? r->state_size : -1; }
 int64_t lf_dist_router_last_launches(const lf_dist_router *r) { return r ? r->last_launches : -1; }
+// schedule of the last fused phase on this router, as lf_router_last_fused_form: 1 time-major, 2 level blocks, 3 levels
+int lf_dist_router_last_fused_form(const lf_dist_router *r) { return r ? r->last_fused_form : -1; }
 
 // local pixel order -> engine order (first N entries of the state vector; ghost slots untouched) and back
 int lf_dist_router_to_engine_order(lf_dist_router *r, const double *src_pix_dev, double *dst_ord_dev)

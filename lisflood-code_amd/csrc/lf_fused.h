@@ -433,7 +433,8 @@ __global__ void __launch_bounds__(kBlock) k_fused_substeps(fused_args F)
         return;
     }
     // ups_base also marks runs of GHOST slots (positions >= N of the per-call state vector) as consecutive: here those
-    // come from the slabs, so only a run inside the local cells -- then: same phase, previous level -- takes the short way
+    // come from the slabs, so only a run inside the local cells takes the short way.  Such a run is of the cell's own phase,
+    // previous level: lf_dist_graph_finalize gives a run that holds a local cell of another phase no base
     const int base_raw = F.d_ups_base[p];
     const int base = (base_raw >= 0 && (long long)base_raw + (u1 - u0) <= F.n) ? base_raw : -1;
     const int kmax = F.kmax;
@@ -1146,8 +1147,9 @@ __global__ void __launch_bounds__(CW) __attribute__((amdgpu_waves_per_eu(LF_CONE
         if (!cone_skip<SPLIT>(cur)) {
             double ups1, ups2 = 0.0;
             // row-block partition: the upstream cells are the consecutive local run [base, base + count) -- a run of ghost
-            // slots is not one, see k_fused_substeps<DIST> -- or come from the list: same-phase cells (level before: LDS,
-            // or the parity buffers for the block's first level) and slab slots (earlier phases, other ranks)
+            // slots is not one, a run with a cell of another phase has no base, see k_fused_substeps<DIST> -- or come from the
+            // list: same-phase cells (level before: LDS, or the parity buffers for the block's first level) and slab slots
+            // (earlier phases, other ranks)
             const int cu0 = DIST ? cur.base : cur.u0, cu1 = DIST ? cur.base + (cur.u1 - cur.u0) : cur.u1;
             if (DIST && (cur.base < 0 || (long long)cu1 > F.n)) {
                 const double *y1 = &x1[(j - 1) & 1][0], *y2 = &x2[SPLIT ? (j - 1) & 1 : 0][0];

@@ -17,7 +17,9 @@
     int base = u0;
     long long slot = -1;
     if (DIST) {
-        const int base_raw = F.d_ups_base[p]; // (a run of ghost slots is not a local run: see k_fused_substeps<DIST>)
+        // (a run of ghost slots is not a local run, and a local run with a cell of another phase has no base: see
+        // k_fused_substeps<DIST>)
+        const int base_raw = F.d_ups_base[p];
         base = (base_raw >= 0 && (long long)base_raw + (u1 - u0) <= n) ? base_raw : -1;
         slot = F.d_out_slot[p];
     }

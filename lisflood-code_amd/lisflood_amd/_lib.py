@@ -50,7 +50,7 @@ _SIGNATURES = {
     "iup": "xcd_contiguous_order",
     "izp": "device_alloc host_alloc",
     "p": "struct_sizes device_count graph_max_upstream router_device router_reset_site_cache router_last_fused_form "
-         "dist_graph_local_num_phases dist_graph_num_phases comm_unique_id comm_close",
+         "dist_router_last_fused_form dist_graph_local_num_phases dist_graph_num_phases comm_unique_id comm_close",
     "pi": "router_profile_enable dist_graph_finalize",
     "piiip": "comm_create",
     "piip": "dist_graph_round_send_positions dist_fused_halo_block dist_graph_part_range",
@@ -59,7 +59,7 @@ _SIGNATURES = {
             "dist_router_recv_slots",
     "piqip": "graph_block_plan_stats graph_block_plan_check",
     "pp": "graph_get_links router_last_launches router_route_plan_stats routing_substep dist_graph_counts "
-          "dist_graph_slab_layout dist_graph_block_stats",
+          "dist_graph_slab_layout dist_graph_block_stats dist_graph_get_ups_base",
     "ppdpddpip": "router_create dist_router_create",
     "ppi": "router_profile_read dist_fused_prepare",
     "ppiiii": "dist_fused_exchange",

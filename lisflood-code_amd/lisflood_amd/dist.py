@@ -159,6 +159,13 @@ class DistGraph:
         check(lib().lf_dist_graph_get_fused_tables(self._h, ptr(out_slot), ptr(idx)))
         return out_slot, idx
 
+    def ups_base(self):
+        """[N] by position, the table the routers upload (lf_dist_graph_get_ups_base): >= 0 = the upstream cells are the
+        consecutive run starting there, -1 = they come from the list"""
+        base = np.empty(self.num_pixels, np.int32)
+        check(lib().lf_dist_graph_get_ups_base(self._h, ptr(base)))
+        return base
+
     def close(self):
         if self._h:
             lib().lf_dist_graph_destroy(self._h)
@@ -612,6 +619,15 @@ class DistRouter:
     def last_launches(self):
         return int(lib().lf_dist_router_last_launches(self._h))
 
+    def last_fused_form(self):
+        """Which schedule the last fused phase that had cells on this router took (lf_dist_router_last_fused_form), named as
+        kinematicWave.last_fused_form(): "time-major", "level blocks" or "levels"; None before the first one."""
+        from .kinematic_wave_parallel import kinematicWave
+        form = int(lib().lf_dist_router_last_fused_form(self._h))
+        if form < 0:
+            raise RuntimeError("router is closed")
+        return kinematicWave.FUSED_FORMS[form]
+
     def close(self):
         if getattr(self, "_h", None):
             lib().lf_dist_router_destroy(self._h)
@@ -648,17 +664,28 @@ class DistRoutingStep:
         check(lib().lf_substep_stage(self.device, i, self.N, C.byref(self.args)))
 
     # --- a whole model step: every sub-step of a phase as one wavefront, one halo exchange per phase -----------------
-    def substeps_fused(self, nsteps):
+    def _substep_args(self, sideflow_stride, sideflows):
+        """the argument block of a fused call: sideflow_stride 0 = the resident sideflow vector in every sub-step, N = one
+        vector per sub-step from `sideflows`, a device array [nsteps, N] in the rank's engine order"""
+        if sideflow_stride == 0:
+            assert sideflows is None
+            return self.args
+        assert sideflow_stride == self.N and sideflows is not None, (sideflow_stride, self.N)
+        return self.vectors.with_overrides(SideflowChanM3=sideflows.ptr.value)
+
+    def substeps_fused(self, nsteps, sideflow_stride=0, sideflows=None):
         """nsteps x routing.dynamic() = lf_routing_substeps_fused on the whole raster (lf_dist_routing_substeps_fused)"""
         r = self.router
-        check(lib().lf_dist_routing_substeps_fused(r._h, r._ch, C.byref(self.args), nsteps, 0, r.rank_top,
+        a = self._substep_args(sideflow_stride, sideflows)
+        check(lib().lf_dist_routing_substeps_fused(r._h, r._ch, C.byref(a), nsteps, sideflow_stride, r.rank_top,
                                                    r.rank_bottom))
 
     def fused_prepare(self, nsteps):
         check(lib().lf_dist_fused_prepare(self.router._h, C.byref(self.args), nsteps))
 
-    def fused_phase(self, nsteps, phase):
-        check(lib().lf_dist_fused_phase(self.router._h, C.byref(self.args), nsteps, 0, phase))
+    def fused_phase(self, nsteps, phase, sideflow_stride=0, sideflows=None):
+        a = self._substep_args(sideflow_stride, sideflows)
+        check(lib().lf_dist_fused_phase(self.router._h, C.byref(a), nsteps, sideflow_stride, phase))
 
     # --- several model steps per call: the sub-steps of all of them as one wavefront per phase, one halo block per phase ----
     def _model_step_args(self, sums, sideflows):
@@ -714,11 +741,13 @@ def loopback_substep(steps):
             s.stage(2)
 
 
-def loopback_substeps_fused(steps, nsteps, lanes=False):
+def loopback_substeps_fused(steps, nsteps, lanes=False, sideflow_stride=0, sideflows=None):
     """A whole model step (nsteps sub-steps) over blocks that all live on one GPU: lf_dist_fused_phase per block and phase,
     the per-phase halo of the slabs as device-to-device copies -- the kernels and the plan of
     lf_dist_routing_substeps_fused, only the transport differs.  lanes: the blocks of a phase on separate streams (see
-    loopback_model_steps_fused)."""
+    loopback_model_steps_fused).  sideflow_stride: 0 = every block's resident sideflow vector in every sub-step; anything
+    else = one vector per sub-step, block k with its own stride N_k from sideflows[k], its [nsteps, N_k] device array in its
+    engine order."""
     dev = steps[0].device
     nph = steps[0].router.graph.num_phases
     L = lib()
@@ -731,7 +760,7 @@ def loopback_substeps_fused(steps, nsteps, lanes=False):
             for k, s in enumerate(steps):
                 if lanes:
                     check(L.lf_lane_select(dev, k + 1))
-                s.fused_phase(nsteps, j)
+                s.fused_phase(nsteps, j, s.N if sideflow_stride else 0, sideflows[k] if sideflow_stride else None)
         finally:
             if lanes:
                 check(L.lf_lane_select(dev, 0))

@@ -28,7 +28,7 @@ import math
 
 import numpy as np
 
-from module_edges import spots
+from module_edges import same_bits, spots
 
 H, W = 96, 80
 N = H * W
@@ -43,6 +43,7 @@ STATIC = ("ChanLength InvChanLength ChannelAlpha InvChannelAlpha ChannelAlpha2 I
 OUT = "FlowVelocity TravelDistance".split()
 INERT_TESTED = "ChanQKin ChanM3Kin ChanQ Chan2QKin Chan2M3Kin CrossSection2Area Sideflow1Chan".split()  # fused_cell's test
 SIDE_TIE = 1e-7
+RTOL, ATOL = 1e-9, 1e-12          # device against oracle: the routing tolerance of test_gpu_parity.py
 HUGE_Q = 2.0 ** 170               # a discharge whose router constant a q^0.6 (~2^101) is beyond lf_fast_range (1e30)
 _SHIFT = {2: (1, 0), 3: (1, 1), 6: (0, 1), 9: (-1, 1), 8: (-1, 0), 7: (-1, -1), 4: (0, -1), 1: (1, -1)}  # synthetic.IX_ADDS
 
@@ -474,3 +475,32 @@ def census_mid(d, vals, step, mid, beta=BETA):
             ups = np.bincount(down[link], weights=qr[link], minlength=N)
             mid["c%d" % (i + 1)] = ups + alpha * vals["ChanLength"] / DT * old ** beta + s * vals["ChanLength"]
     return mid
+
+
+# ---- what the device files assert on these inputs --------------------------------------------------------------------
+def close_to_oracle(got, want, names, vals, what):
+    """device vectors against the oracle's: NaN exactly where the oracle has it, rtol 1e-9, atol 1e-12 (CrossSection2Area, a
+    difference: 1e-9 max|Chan2M3Start / ChanLength|)"""
+    for k in names:
+        g, w = got[k], want[k]
+        assert np.array_equal(np.isnan(g), np.isnan(w)), "%s, %s: NaN at %s / %s" % (what, k, np.flatnonzero(np.isnan(g))[:8],
+                                                                                    np.flatnonzero(np.isnan(w))[:8])
+        atol = RTOL * float(np.max(np.abs(vals["Chan2M3Start"] / vals["ChanLength"]))) if k == "CrossSection2Area" else ATOL
+        np.testing.assert_allclose(g, w, rtol=RTOL, atol=atol, equal_nan=True, err_msg="%s, %s" % (what, k))
+
+
+def inert_cells_are_left_alone(d, got, want, split):
+    """the all-+0.0 candidates are still all +0.0; every other candidate holds what the sequential engine left (-0.0 has
+    become +0.0 where the arithmetic says so).  (What this can see is a sub-step skipped on a state that still moves: a
+    discharge, or the last sub-step.  An inert test that took -0.0 for +0.0 leaves the same bits, because the last sub-step
+    of a call always runs and maps -0.0 to +0.0 as the skipped ones would have.)"""
+    tested = INERT_TESTED if split else ["ChanQKin", "ChanM3Kin", "ChanQ"]
+    plus = d["inert_cells"]["plus"]
+    for k in tested:
+        assert (np.ascontiguousarray(got[k][plus]).view(np.uint64) == 0).all(), k
+    for name, cells in d["inert_cells"].items():
+        for k in got:
+            assert same_bits(got[k][cells], want[k][cells]), (name, k)
+    minus = d["inert_cells"]["minus"]
+    for k in tested:
+        assert (got[k][minus] == 0).all() and not np.signbit(got[k][minus]).any(), k

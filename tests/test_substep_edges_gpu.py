@@ -19,7 +19,6 @@ import substep_edges as S
 
 pytestmark = pytest.mark.gpu
 
-RTOL, ATOL = 1e-9, 1e-12        # test_gpu_parity.py
 SEED = 5
 SENTINEL, PAD = -777.25, 37
 FORM_SWITCHES = ("LF_FUSED_TIME_MAJOR", "LF_FUSED_SPLIT", "LF_FUSED_LEVELS", "LF_FUSED_CONE_WIDTH", "LF_NO_INERT_SKIP",
@@ -114,15 +113,6 @@ def sequential(amd, family, split, irregular, general, sideflows=None):
 # ======================================================================================================================
 # 1. the stage kernels against the oracle
 # ======================================================================================================================
-def _close_to_oracle(got, want, names, vals, what):
-    for k in names:
-        g, w = got[k], want[k]
-        assert np.array_equal(np.isnan(g), np.isnan(w)), "%s, %s: NaN at %s / %s" % (what, k, np.flatnonzero(np.isnan(g))[:8],
-                                                                                    np.flatnonzero(np.isnan(w))[:8])
-        atol = RTOL * float(np.max(np.abs(vals["Chan2M3Start"] / vals["ChanLength"]))) if k == "CrossSection2Area" else ATOL
-        np.testing.assert_allclose(g, w, rtol=RTOL, atol=atol, equal_nan=True, err_msg="%s, %s" % (what, k))
-
-
 def _sequential_against_oracle(amd, oracle, family, split, irregular, engine_order, beta=S.BETA):
     from lisflood_amd.routing import SubstepVectors, result_names, substep_host_vectors
     d = inputs(family)
@@ -145,7 +135,7 @@ def _sequential_against_oracle(amd, oracle, family, split, irregular, engine_ord
         sv.upload("SideflowChanM3", np.ascontiguousarray(side if perm is None else side[perm]))
         amd.lib.check(amd.lib.lib().lf_routing_substep(kw._h, C.byref(sv.args)))
         got = {k: download(k) for k in names}
-        _close_to_oracle(got, step["after"], names, vals, (family, s))
+        S.close_to_oracle(got, step["after"], names, vals, (family, s))
         if s == 0:
             # the ties, on the vectors that involve no pow: the split of the sideflow (cases d, e, and f, a beside them) ...
             if split:
@@ -196,23 +186,6 @@ FORMS = {
 FORM_CASES = [(form, general) for form in FORMS for general in (False, True) if not (general and form == "chain_supply")]
 
 
-def _inert_cells_are_left_alone(d, got, want, split):
-    """the all-+0.0 candidates are still all +0.0; every other candidate holds what the sequential engine left (-0.0 has
-    become +0.0 where the arithmetic says so).  (What this can see is a sub-step skipped on a state that still moves: a
-    discharge, or the last sub-step.  An inert test that took -0.0 for +0.0 leaves the same bits, because the last sub-step
-    of a call always runs and maps -0.0 to +0.0 as the skipped ones would have.)"""
-    tested = S.INERT_TESTED if split else ["ChanQKin", "ChanM3Kin", "ChanQ"]
-    plus = d["inert_cells"]["plus"]
-    for k in tested:
-        assert (np.ascontiguousarray(got[k][plus]).view(np.uint64) == 0).all(), k
-    for name, cells in d["inert_cells"].items():
-        for k in got:
-            assert E.same_bits(got[k][cells], want[k][cells]), (name, k)
-    minus = d["inert_cells"]["minus"]
-    for k in tested:
-        assert (got[k][minus] == 0).all() and not np.signbit(got[k][minus]).any(), k
-
-
 @pytest.mark.parametrize("irregular", [False, True], ids=["regular", "irregular"])
 @pytest.mark.parametrize("split", [False, True], ids=["single", "split"])
 @pytest.mark.parametrize("form, general", FORM_CASES, ids=["%s-%s" % (f, "general_pow" if g else "fused_beta_3_5") for f, g in FORM_CASES])
@@ -247,7 +220,7 @@ def test_fused_form_equals_sequential(amd, switches, form, general, split, irreg
         r.free()
         assert kw.last_fused_form() == expect, (form, kw.last_fused_form())
         assert_same(got, want, (form, "LF_NO_INERT_SKIP", inert_skip, "LF_NO_RECOMPUTE", no_recompute))
-        _inert_cells_are_left_alone(d, got, want, split)
+        S.inert_cells_are_left_alone(d, got, want, split)
     kw.close()
 
 
