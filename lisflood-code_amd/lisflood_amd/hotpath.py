@@ -22,6 +22,7 @@ from . import routing as RT
 from . import soilloop as SL
 from . import surface_routing as SR
 from ._lib import DeviceArray, PinnedArray, check, f64, lib, timer_start, timer_stop, u8
+from .channel_domain import _structures_on_subdomain, channel_domain, inert_pixels  # noqa: F401 (inert_pixels: read from here)
 from .kinematic_wave_parallel import Graph, kinematicWave
 
 FORCING = ("Rain", "SnowMelt", "EWRef", "ETRef", "ESRef")
@@ -43,7 +44,220 @@ PA_READERS = dict(TaInterception=("TaInterceptionAll", "TaInterceptionCUM"), Ta=
                   W2=("Theta", "ThetaAll"), SoilDepthTotal=("Theta", "ThetaAll"))
 
 
-class HotPathDevice:
+class _HotPath:
+    """What HotPathDevice and HotPathEnsemble are both made of: the `report` set, the three overland routers and the order
+    of the non-channel vectors, the channel domain (channel_domain.channel_domain) with the channel router on it -- or,
+    with structures=, the resident routing module (_routing_module) --, the engine-order index vectors, the scalar half of
+    the argument blocks, and the host side of set_lai / set_inflow / state files / free().  The constructors call the
+    pieces in their own order, which is the order of their device allocations."""
+
+    # everything a stage reads back from the previous step (the reference writes its state maps as end / state files,
+    # default_options.py:131-160): the in/out vectors of the canopy and soil kernels, the accumulators of the per-pixel
+    # aggregates, the overland and channel router states
+    STATE = tuple(dict.fromkeys(SL._CANOPY_IO + list(SL._V_IO) + PA._STATE + SR._STATE +
+                                ["OFM3Direct", "OFM3Other", "OFM3Forest"] + RT._STATE))
+
+    def _begin(self, scalars, land_mask, split, device, overlap_channel, report):
+        self.device, self.split = device, bool(split)
+        # overlap_channel: the channel wavefront of a step on a second HIP stream, beside the canopy / soil / overland kernels
+        # of the step after it (same kernels, same results; False: one stream, as rounds 1-3).  Read at every call.
+        self.overlap_channel = bool(overlap_channel)
+        # report: which of the OPTIONAL maps (OPTIONAL_MAPS: diagnostics and cumulative sums nothing else on the hot
+        # path reads) are wanted.  None: all of them, as the reference computes them every step; an iterable of names: only
+        # those -- the others get no device vector, are not computed, and the [3,N] vectors only they read are not streamed
+        # (the reference writes the maps its rep* options name; what is not reported need not exist).  `dis`, the state
+        # maps and everything another stage reads are always there.
+        self.report = None if report is None else set(report)
+        if self.report is not None and not self.report <= set(OPTIONAL_MAPS):
+            raise ValueError("report: not optional maps: %s" % sorted(self.report - set(OPTIONAL_MAPS)))
+        self.sc = dict(scalars)
+        land_mask = np.asarray(land_mask, bool)
+        self.N = int(land_mask.sum())
+        self.rmod, self._qin_old, self._pinned, self.steps_done = None, None, [], 0
+        return land_mask
+
+    def _kept(self):
+        """the optional maps that exist in this object: the reported ones plus what they are made of (the per-pixel Theta
+        averages read the soil kernel's Theta1a / Theta1b / Theta2)"""
+        if self.report is None:
+            return set(OPTIONAL_MAPS)
+        keep = set(self.report)
+        for pix, col in (("Theta1aPixel", "Theta1a"), ("Theta1bPixel", "Theta1b"), ("Theta2Pixel", "Theta2"),
+                         ("LZAvInflow", "LZInflowCUM")):
+            if pix in keep:
+                keep.add(col)
+        return keep
+
+    def _wanted(self, names):
+        kept = self._kept()
+        return [k for k in names if k not in OPTIONAL_MAPS or k in kept]
+
+    def _overland(self, values, ldd_to_chan, land_mask, surface_order=True):
+        """the three overland routers on one graph, and position -> pixel of that graph's sweep order (None: the non-channel
+        vectors stay in pixel order)"""
+        sc = self.sc
+        g_surf = Graph(ldd_to_chan, land_mask)
+        alpha_of = np.asarray(values["OFAlpha"], float)
+        mk = lambda row: kinematicWave(None, None, alpha_of[row], sc["Beta"], sc["PixelLength"], sc["DtSec"],
+                                       device=self.device, graph=g_surf)
+        self.r_other, self.r_forest, self.r_direct = mk(0), mk(1), mk(2)
+        self.pixel_of_position = g_surf.layout()[0].astype(np.int64) if surface_order else None
+
+    def _channel(self, values, ldd_kinematic, land_mask, structures, compact):
+        """The channel domain -- all land pixels, or only the ones whose routing sub-step is not the identity -- and the
+        channel router on it: `river` alone, or with structures the routing module `rmod` that owns it.
+        -> (v, structures): the namespace of the channel values and scalars, and the structures, both on the domain."""
+        N, sc = self.N, self.sc
+        ldd_kinematic = np.asarray(ldd_kinematic, np.float64)
+        self.ids, chan_mask = channel_domain(values, ldd_kinematic, land_mask, self.split, structures, compact)
+        Nk = self.Nk = self.ids.size                          # ids: channel-domain pixel -> land pixel
+        self._outside = np.setdiff1d(np.arange(N), self.ids)
+        if Nk < N and structures is not None:
+            structures = _structures_on_subdomain(structures, self.ids, N)
+        v = types.SimpleNamespace(IsChannelKinematic=np.zeros(Nk, bool))     # (not given: no pixel is a channel pixel)
+        for k in set(RT._STATIC + RT._STATE) & set(values):
+            setattr(v, k, np.array(np.broadcast_to(np.asarray(values[k]), (N,))[self.ids], copy=True))
+        v.Beta, v.InvBeta, v.DtRouting, v.InvDtRouting = sc["Beta"], 1 / sc["Beta"], sc["DtRouting"], 1 / sc["DtRouting"]
+        v.DtSec, v.NoRoutSteps, v.InvNoRoutSteps = sc["DtSec"], int(sc["NoRoutSteps"]), 1 / sc["NoRoutSteps"]
+        if structures is None:
+            self.river = kinematicWave(ldd_kinematic[self.ids], chan_mask, v.ChannelAlpha, sc["Beta"], v.ChanLength,
+                                       sc["DtRouting"], alpha_floodplains=v.ChannelAlpha2 if self.split else None,
+                                       device=self.device)
+        else:
+            self.rmod = self._routing_module(v, structures, ldd_kinematic[self.ids], chan_mask)
+            self.river = self.rmod.river_router
+        return v, structures
+
+    def _routing_module(self, v, structures, ldd_kinematic, chan_mask):
+        """the channel part as a resident, engine-order routing module with its structures attached"""
+        v.ToChanM3RunoffDt = np.zeros(self.Nk)
+        for k, a in structures.items():
+            setattr(v, k, a)
+        opts = dict(SplitRouting=self.split, InitLisflood=False, simulateLakes="LakeIndex" in structures,
+                    simulateReservoirs="ReservoirIndex" in structures, inflow="QInM3Old" in structures,
+                    TransLoss="UpTrans" in structures)
+        m = RT.routing(v, options=opts, device=self.device, engine_order=True)
+        m.attach_router(ldd_kinematic, chan_mask)
+        m.attach_structures()
+        m.begin_step()                              # uploads the channel state once; it stays resident
+        m._structures_substep(0, launch=False)      # site state from the dense maps, once
+        m._args.split = 1 if self.split else 0
+        return m
+
+    def _engine_order(self):
+        self.perm = self.river.graph.layout()[0].astype(np.int64)        # engine position -> channel-domain pixel
+        self.gpix = src = self.ids[self.perm]                             # engine position -> land pixel
+        if self.pixel_of_position is not None:
+            inv = np.empty(self.N, np.int64)
+            inv[self.pixel_of_position] = np.arange(self.N)
+            src = inv[self.gpix]                                          # where a channel cell's land pixel sits in those vectors
+        self._gidx = DeviceArray.from_host(src.astype(np.int32), self.device)
+
+    def _finish_args(self, p, f):
+        """what the blocks of the per-pixel aggregates and of the overland step hold beside pointers to vectors"""
+        sc, N, kept = self.sc, self.N, self._kept()
+        if self.report is not None:        # a [3,N] input that only unreported maps read is not handed to the kernel
+            for src, outs in PA_READERS.items():
+                if not any(o in kept for o in outs):
+                    setattr(p, src, None)
+        p.InvDtDay, p.N = sc["InvDtDay"], N
+        f.Beta, f.MMtoM3, f.M3toMM = sc["Beta"], sc["MMtoM3"], sc["M3toMM"]
+        f.PixelLength, f.InvPixelLength = sc["PixelLength"], 1 / sc["PixelLength"]
+        f.DtSec, f.InvDtSec, f.InvNoRoutSteps, f.N = sc["DtSec"], 1 / sc["DtSec"], 1 / sc["NoRoutSteps"], N
+
+    def _ordered(self, a):
+        """a per-pixel array ([N] or [..., N], pixel order) in the order the non-channel device vectors are kept in"""
+        a = np.asarray(a)
+        if self.pixel_of_position is None or a.ndim == 0 or a.shape[-1] != self.N:
+            return a
+        return np.ascontiguousarray(a[..., self.pixel_of_position])
+
+    def _pixel_order(self, a):
+        """inverse of _ordered"""
+        if self.pixel_of_position is None or a.ndim == 0 or a.shape[-1] != self.N:
+            return a
+        out = np.empty_like(a)
+        out[..., self.pixel_of_position] = a
+        return out
+
+    def _check_inside(self, a, message):
+        """ValueError(message) if `a` ([..., N], pixel order) is not zero on the pixels left out of the channel domain"""
+        if self._outside.size and np.any(a[..., self._outside] != 0):
+            raise ValueError(message)
+
+    def _side_begin(self, side=True):
+        """From here to _side_end(what this returns), in a try / finally, the calls go to the channel loop's stream (the side
+        stream, behind the loop of the step before) -- if overlap_channel says so now, else they stay where they are."""
+        side = side and self.overlap_channel
+        if side:
+            check(lib().lf_side_stream_begin(self.device))
+        return side
+
+    def _side_end(self, side):
+        if side:
+            check(lib().lf_side_stream_end(self.device))
+
+    def set_lai(self, LAI, LAITerm):
+        """The prescribed leaf area index of the coming steps: what leafarea.dynamic sets once per ten-day interval
+        (leafarea.py:80-91: LAI of the interval, LAITerm = exp(-kgb * LAI)), [3, N] each, pixel order (an ensemble's
+        members share the two vectors).  Waits for the step in flight (its canopy kernel reads the vectors)."""
+        check(lib().lf_device_synchronize(self.device))
+        for k, a in (("LAI", LAI), ("LAITerm", LAITerm)):
+            a = np.asarray(a, np.float64)
+            if a.shape != (3, self.N):
+                raise ValueError("%s must be [3, %d]" % (k, self.N))
+            self._lai_vectors()[k].upload(f64(self._ordered(a)))
+
+    def _inflow(self, QInM3):
+        """The host half of set_inflow: QInM3 in pixel order, [N] -- for an ensemble every member's, or [members, N] --
+        -> (q, delta) on the channel domain, shaped like _qin_old: the volumes, and QDelta = (QInM3 - QInM3Old) *
+        InvNoRoutSteps (inflow.py:108-125)."""
+        if self._qin_old is None:
+            raise RuntimeError("inflow hydrographs need structures= with QInM3Old / QDelta (the `inflow` option)")
+        q, lead = np.asarray(QInM3, np.float64), self._qin_old.shape[:-1]
+        if lead and q.shape not in ((self.N,), lead + (self.N,)):
+            raise ValueError("QInM3 must be [%d] or [%d, %d]" % (self.N, lead[0], self.N))
+        q = np.broadcast_to(q, lead + (self.N,))
+        self._check_inside(q, "inflow at a pixel this object left out of the channel domain; flag the inflow pixels in "
+                              "structures['InflowPoints'] or build it with compact=False")
+        q = np.ascontiguousarray(q[..., self.ids])
+        return q, (q - self._qin_old) * self.rmod.var.InvNoRoutSteps
+
+    def _pinned_set(self, shape, dtype):
+        """a forcing dict of page-locked host arrays that belong to this object (freed by free())"""
+        bufs = {k: PinnedArray(shape, dtype, self.device) for k in FORCING}
+        self._pinned.append(bufs)
+        return {k: b.a for k, b in bufs.items()}
+
+    def upload_wait(self, buffer_set=None):
+        """Block until the forcing uploads started by prefetch() / step() have left the host arrays (lf_upload_wait):
+        after it the arrays of pinned_forcing() may be refilled in place.  buffer_set: 0 / 1, default both."""
+        for b in ((0, 1) if buffer_set is None else (int(buffer_set),)):
+            check(lib().lf_upload_wait(self.device, b))
+
+    def chan_q_avg(self):
+        """ChanQAvg = sumDisDay / NoRoutSteps (Lisflood_dynamic.py:209): the `dis` output of the reference ([members, N]
+        of an ensemble)."""
+        return self.download("sumDisDay") / self.sc["NoRoutSteps"]
+
+    def _free_shared(self, arrays):
+        """`arrays`: the device arrays of the class, which may include the routing module's (each is freed once); then the
+        four routers, and -- once no upload can still be reading them -- the page-locked buffers"""
+        arrays = {id(a): a for a in arrays}
+        if self.rmod is not None:
+            arrays.update({id(a): a for a in list(self.rmod._st["dev"].values()) + list(self.rmod._dev.values())})
+        for a in arrays.values():
+            a.free()
+        for r in (self.r_other, self.r_forest, self.r_direct, self.river):
+            r.close()
+        check(lib().lf_device_synchronize(self.device))
+        for bufs in self._pinned:
+            for b in bufs.values():
+                b.free()
+        self._pinned = []
+
+
+class HotPathDevice(_HotPath):
     def __init__(self, values, scalars, land_mask, ldd_to_chan, ldd_kinematic, split=True, device=0, structures=None,
                  compact=True, overlap_channel=True, surface_order=True, land_fused=None, report=None):
         """values: name -> host array in pixel order ([N], [3,N]) for every vector of the stages (reference
@@ -55,98 +269,32 @@ class HotPathDevice:
         (structures.py:44-61) and the sub-step loop runs with the structures inside the wavefront.
         compact: leave inert pixels out of the channel router's domain (see inert_pixels): on real domains most land
         pixels are not channel pixels, and the channel wavefront then touches only the ones that are."""
-        self.device, self.split = device, bool(split)
+        # overlap_channel, report: see _HotPath._begin
+        land_mask = self._begin(scalars, land_mask, split, device, overlap_channel, report)
+        N, sc = self.N, self.sc
         # surface_order: every per-pixel vector that is not a channel vector lives in the sweep order of the OVERLAND
         # routers' graph (the canopy / soil / aggregate kernels are element-wise and do not care; the three overland routers
         # then stream their vectors instead of going through the position -> pixel table: lf_surface_step_ordered).
         # Vectors come in and go out in pixel order all the same (constructor, step(), download(), state files); a caller
         # whose forcing is already in that order (`pixel_of_position`) says step(..., ordered=True) and saves the gather.
-        # overlap_channel: the channel wavefront of a step on a second HIP stream, beside the canopy / soil / overland kernels
-        # of the step after it (same kernels, same results; False: one stream, as rounds 1-3)
-        self.overlap_channel = bool(overlap_channel)
-        self.rmod = None
         # the ten derived soil parameter arrays recomputed instead of read where they are what soil.py:180-228 makes them
         self.soil_derived = SL.derived_parameters_hold(values)
         # land_fused: canopy + ESMax + soil columns as ONE pass over the columns (lf_land_columns_device; the three prescribed
         # fractions map to their own land-use rows, which is what it needs).  None: on, unless LF_LAND_FUSED=0 (A/B switch);
         # False: the three separate launches of rounds 1-5 -- same bits either way
         self.land_fused = (os.environ.get("LF_LAND_FUSED", "1") != "0") if land_fused is None else bool(land_fused)
-        # report: which of the OPTIONAL maps (OPTIONAL_MAPS below: diagnostics and cumulative sums nothing else on the hot
-        # path reads) are wanted.  None: all of them, as the reference computes them every step; an iterable of names: only
-        # those -- the others get no device vector, are not computed, and the [3,N] vectors only they read are not streamed
-        # (the reference writes the maps its rep* options name; what is not reported need not exist).  `dis`, the state
-        # maps and everything another stage reads are always there.
-        self.report = None if report is None else set(report)
-        if self.report is not None and not self.report <= set(OPTIONAL_MAPS):
-            raise ValueError("report: not optional maps: %s" % sorted(self.report - set(OPTIONAL_MAPS)))
-        self.sc = dict(scalars)
-        land_mask = np.asarray(land_mask, bool)
-        self.N = N = int(land_mask.sum())
-        sc = self.sc
-        # ---- channel domain: all land pixels, or only the ones whose routing sub-step is not the identity ----------
-        values = dict(values)
-        ldd_kinematic = np.asarray(ldd_kinematic, np.float64)
-        drop = inert_pixels(values, ldd_kinematic, land_mask, self.split, structures) if compact else np.zeros(N, bool)
-        if drop.sum() < 0.1 * N:
-            drop[:] = False
-        self.ids = np.nonzero(~drop)[0]                       # channel-domain pixel -> land pixel
-        Nk = self.Nk = self.ids.size
-        chan_mask = land_mask
-        if Nk < N:
-            chan_mask = np.zeros(land_mask.shape, bool)
-            chan_mask[land_mask] = ~drop
-            ldd_kinematic = ldd_kinematic[self.ids]
-            for k in set(RT._STATIC + RT._STATE) & set(values):
-                values[k] = np.broadcast_to(np.asarray(values[k]), (N,))[self.ids]
-            if structures is not None:
-                structures = _structures_on_subdomain(structures, self.ids, N)
-        # ---- routers -------------------------------------------------------------------------------
-        g_surf = Graph(ldd_to_chan, land_mask)
-        alpha_of = np.asarray(values["OFAlpha"], float)
-        mk = lambda row: kinematicWave(None, None, alpha_of[row], sc["Beta"], sc["PixelLength"], sc["DtSec"],
-                                       device=device, graph=g_surf)
-        self.r_other, self.r_forest, self.r_direct = mk(0), mk(1), mk(2)
+        # ---- routers, channel domain ------------------------------------------------------------------
+        self._overland(values, ldd_to_chan, land_mask, surface_order)
+        v, structures = self._channel(values, ldd_kinematic, land_mask, structures, compact)
+        Nk = self.Nk
+        if structures is not None and "QInM3Old" in structures:      # inflow hydrographs: QInM3 of the previous model step
+            self._qin_old = f64(np.broadcast_to(structures["QInM3Old"], (Nk,))).copy()
+        self._engine_order()
         chan_names = set(RT._STATIC + RT._STATE)
         self.d = {}
-        if structures is None:
-            self.river = kinematicWave(ldd_kinematic, chan_mask, values["ChannelAlpha"], sc["Beta"], values["ChanLength"],
-                                       sc["DtRouting"], alpha_floodplains=values["ChannelAlpha2"] if split else None,
-                                       device=device)
-        else:       # the channel part is a resident, engine-order routing module with its structures attached
-            v = types.SimpleNamespace(**{k: np.array(values[k], copy=True) for k in chan_names if k in values})
-            v.Beta, v.InvBeta, v.DtRouting, v.InvDtRouting = sc["Beta"], 1 / sc["Beta"], sc["DtRouting"], 1 / sc["DtRouting"]
-            v.DtSec, v.NoRoutSteps, v.InvNoRoutSteps = sc["DtSec"], int(sc["NoRoutSteps"]), 1 / sc["NoRoutSteps"]
-            v.ToChanM3RunoffDt = np.zeros(Nk)
-            for k, a in structures.items():
-                setattr(v, k, a)
-            opts = dict(SplitRouting=self.split, InitLisflood=False, simulateLakes="LakeIndex" in structures,
-                        simulateReservoirs="ReservoirIndex" in structures, inflow="QInM3Old" in structures,
-                        TransLoss="UpTrans" in structures)
-            m = self.rmod = RT.routing(v, options=opts, device=device, engine_order=True)
-            m.attach_router(ldd_kinematic, chan_mask)
-            m.attach_structures()
-            m.begin_step()                              # uploads the channel state once; it stays resident
-            m._structures_substep(0, launch=False)      # site state from the dense maps, once
-            m._args.split = 1 if self.split else 0
-            self.river = m.river_router
-            if "QInM3Old" in structures:       # inflow hydrographs: QInM3 of the previous model step, channel domain
-                self._qin_old = f64(np.broadcast_to(structures["QInM3Old"], (Nk,))).copy()
-        self.perm = self.river.graph.layout()[0].astype(np.int64)        # engine position -> channel-domain pixel
-        self.gpix = self.ids[self.perm]                                   # engine position -> land pixel
-        # position -> pixel of the overland graph's sweep order (None: the non-channel vectors stay in pixel order)
-        self.pixel_of_position = g_surf.layout()[0].astype(np.int64) if surface_order else None
-        if self.pixel_of_position is not None:
-            inv = np.empty(N, np.int64)
-            inv[self.pixel_of_position] = np.arange(N)
-            src = inv[self.gpix]                                          # where a channel cell's land pixel sits in those vectors
-        else:
-            src = self.gpix
-        self._gidx = DeviceArray.from_host(src.astype(np.int32), device)
         # ---- device vectors ------------------------------------------------------------------------
         if self.rmod is None:       # the channel vectors, in the engine order of the river router, and their argument block
-            chan = {"IsChannelKinematic": np.zeros(Nk, bool)}     # (where it is not given, no pixel is a channel pixel)
-            chan.update({k: values[k] for k in chan_names if k in values})
-            vec = RT.SubstepVectors(RT.substep_host_vectors(chan, Nk, self.perm), Nk, sc["Beta"], 1 / sc["DtRouting"],
+            vec = RT.SubstepVectors(RT.substep_host_vectors(v, Nk, self.perm), Nk, sc["Beta"], 1 / sc["DtRouting"],
                                     sc["DtSec"], self.split, True, device, order=RT._STATIC + RT._STATE)
         else:       # self.d and self.rout alias the routing module's own vectors and block (free() frees each array once)
             vec = self.rmod._vectors
@@ -192,7 +340,7 @@ class HotPathDevice:
         a.V, a.L, a.N = 3, 3, N
         zeros("LAITerm", (3, N)); zeros("ESMax", (3, N))
         s = self.soil = SL._SoilArgs()
-        wanted = lambda names: [k for k in names if self.report is None or k not in OPTIONAL_MAPS or k in self._kept()]
+        wanted = self._wanted
         fill(s, wanted(SL._L_FIELDS + SL._V_IN + SL._V_IO), vn)
         fill(s, SL._N_FIELDS, n1)
         self._irr = np.array([0, 0, 1], np.uint8)
@@ -205,34 +353,17 @@ class HotPathDevice:
         p = self.pixel = PA._PixelArgs()
         fill(p, wanted(PA._V_IN + ["Theta"]), vn)
         fill(p, wanted(PA._N_IN + PA._STATE + PA._OUT), n1)
-        if self.report is not None:        # a [3,N] input that only unreported maps read is not handed to the kernel
-            for src, outs in PA_READERS.items():
-                if not any(o in self._kept() for o in outs):
-                    setattr(p, src, None)
-        p.InvDtDay, p.N = sc["InvDtDay"], N
         f = self.surface = SR._SurfaceArgs()
         fill(f, SR._V_IN + ["SurfaceRunSoil", "scratch"], vn)
         fill(f, SR._N_IN + SR._STATE + SR._OUT, n1)
-        f.Beta, f.MMtoM3, f.M3toMM = sc["Beta"], sc["MMtoM3"], sc["M3toMM"]
-        f.PixelLength, f.InvPixelLength = sc["PixelLength"], 1 / sc["PixelLength"]
-        f.DtSec, f.InvDtSec, f.InvNoRoutSteps, f.N = sc["DtSec"], 1 / sc["DtSec"], 1 / sc["NoRoutSteps"], N
+        self._finish_args(p, f)
         if self.rmod is None:       # outputs, scratch and sideflow come last, where they always were allocated
             vec.allocate(["SideflowChanM3"] + RT._OUT + ["scratch0", "scratch1"])
             self.d.update(vec.dev)
         self.rout = vec.args
-        self.steps_done = 0
 
-    def _kept(self):
-        """the optional maps that exist in this object: the reported ones plus what they are made of (the per-pixel Theta
-        averages read the soil kernel's Theta1a / Theta1b / Theta2)"""
-        if self.report is None:
-            return set(OPTIONAL_MAPS)
-        keep = set(self.report)
-        for pix, col in (("Theta1aPixel", "Theta1a"), ("Theta1bPixel", "Theta1b"), ("Theta2Pixel", "Theta2"),
-                         ("LZAvInflow", "LZInflowCUM")):
-            if pix in keep:
-                keep.add(col)
-        return keep
+    def _lai_vectors(self):
+        return self.d
 
     def _upload_ordered(self, a):
         """fp64 [N] or [R, N] host array in pixel order -> device array in the order of pixel_of_position: every row is
@@ -247,21 +378,6 @@ class HotPathDevice:
             self._perm_tmp.upload(np.ascontiguousarray(rows[r]))
             check(L.lf_gather_device(dev, N, self._perm_idx.ptr, self._perm_tmp.ptr, dst.ptr.value + r * N * 8))
         return dst
-
-    def _ordered(self, a):
-        """a per-pixel array ([N] or [..., N], pixel order) in the order the non-channel device vectors are kept in"""
-        a = np.asarray(a)
-        if self.pixel_of_position is None or a.ndim == 0 or a.shape[-1] != self.N:
-            return a
-        return np.ascontiguousarray(a[..., self.pixel_of_position])
-
-    def _pixel_order(self, a):
-        """inverse of _ordered"""
-        if self.pixel_of_position is None or a.ndim == 0 or a.shape[-1] != self.N:
-            return a
-        out = np.empty_like(a)
-        out[..., self.pixel_of_position] = a
-        return out
 
     def _upload(self, b, forcing, ordered=False):
         """float32 vectors (meteo as the netCDF files store it) go up as float32 and are widened on the device -- exactly
@@ -286,15 +402,7 @@ class HotPathDevice:
         PCIe rate instead of a staged, blocking copy.  The arrays belong to this object (freed by free()).
         The DMA reads the arrays AFTER prefetch() / step() has returned: call upload_wait() before writing the next
         time step into a set that was handed over (or alternate between two pinned sets and wait before reuse)."""
-        bufs = {k: PinnedArray(self.N, dtype, self.device) for k in FORCING}
-        self.__dict__.setdefault("_pinned", []).append(bufs)
-        return {k: b.a for k, b in bufs.items()}
-
-    def upload_wait(self, buffer_set=None):
-        """Block until the forcing uploads started by prefetch() / step() have left the host arrays (lf_upload_wait):
-        after it the arrays of pinned_forcing() may be refilled in place.  buffer_set: 0 / 1, default both."""
-        for b in ((0, 1) if buffer_set is None else (int(buffer_set),)):
-            check(lib().lf_upload_wait(self.device, b))
+        return self._pinned_set(self.N, dtype)
 
     def prefetch(self, forcing, ordered=False):
         """Start uploading the forcing of the NEXT step() call now: the copies run on a second stream while the kernels
@@ -312,45 +420,21 @@ class HotPathDevice:
                 if hasattr(type(st), k):
                     setattr(st, k, self.force[b][k].ptr.value)
 
-    def set_lai(self, LAI, LAITerm):
-        """The prescribed leaf area index of the coming steps: what leafarea.dynamic sets once per ten-day interval
-        (leafarea.py:80-91: LAI of the interval, LAITerm = exp(-kgb * LAI)), [3, N] each, pixel order.  Waits for the
-        step in flight (its canopy kernel reads the vectors)."""
-        check(lib().lf_device_synchronize(self.device))
-        for k, a in (("LAI", LAI), ("LAITerm", LAITerm)):
-            a = np.asarray(a, np.float64)
-            if a.shape != (3, self.N):
-                raise ValueError("%s must be [3, %d]" % (k, self.N))
-            self.d[k].upload(f64(self._ordered(a)))
-
     def set_inflow(self, QInM3):
         """inflow.dynamic + dynamic_init (inflow.py:108-125) for the coming step: QInM3 [N] is the hydrograph volume of
         the model step [m3]; QDelta = (QInM3 - QInM3Old) * InvNoRoutSteps goes to the device next to QInM3Old, and
         QInM3 becomes QInM3Old once the step is enqueued (Lisflood_dynamic.py:185)."""
-        if self.rmod is None or getattr(self, "_qin_old", None) is None:
-            raise RuntimeError("inflow hydrographs need structures= with QInM3Old / QDelta (the `inflow` option)")
-        q = f64(np.broadcast_to(np.asarray(QInM3, np.float64), (self.N,)))
-        if self.Nk < self.N:
-            rest = np.ones(self.N, bool); rest[self.ids] = False
-            if np.any(q[rest] != 0):
-                raise ValueError("inflow at a pixel this object left out of the channel domain; flag the inflow pixels in "
-                                 "structures['InflowPoints'] or build it with compact=False")
-        q = np.ascontiguousarray(q[self.ids])
+        q, delta = self._inflow(QInM3)
         m, dev = self.rmod, self.rmod._st["dev"]
-        delta = (q - self._qin_old) * m.var.InvNoRoutSteps
         # Only the channel wavefront reads the two vectors: they go up on ITS stream (the side stream when the wavefront
         # runs there), behind the wavefront of the step before and ahead of the next one, without a host wait and without
         # making the main stream wait for the side stream (lf_memcpy_h2d would do both)
-        L, d = lib(), self.device
-        side = self.overlap_channel
-        if side:
-            check(L.lf_side_stream_begin(d))
+        side = self._side_begin()
         try:
             dev["QInM3Old"].upload(f64(m._up(self._qin_old)), staged=True)
             dev["QDelta"].upload(f64(m._up(delta)), staged=True)
         finally:
-            if side:
-                check(L.lf_side_stream_end(d))
+            self._side_end(side)
         self._qin_old = q
 
     def step(self, forcing, time_since_start=None, QInM3=None, ordered=False):
@@ -425,9 +509,7 @@ class HotPathDevice:
             else:
                 check(L.lf_gather_device(dev, self.Nk, self._gidx.ptr, d["ToChanM3RunoffDt"].ptr,
                                          d["SideflowChanM3"].ptr))
-        side = self.overlap_channel and stage_ms is None
-        if side:
-            check(L.lf_side_stream_begin(dev))
+        side = self._side_begin(stage_ms is None)
         try:
             with stage("channel_wavefront"):
                 d["sumDisDay"].zero()                                                                   # dyn.py:177
@@ -438,8 +520,7 @@ class HotPathDevice:
                 else:
                     check(L.lf_routing_substeps_fused(self.river._h, C.byref(self.rout), int(self.sc["NoRoutSteps"]), 0))
         finally:
-            if side:
-                check(L.lf_side_stream_end(dev))
+            self._side_end(side)
 
     def step_profile(self, forcing, time_since_start=None, ordered=False):
         """step() with every stage timed on its own (synchronising; no overlap between the stages) -> {stage: ms}"""
@@ -494,12 +575,7 @@ class HotPathDevice:
             return out
         return a
 
-    # ---- warm start (the reference writes its state maps as end / state files, default_options.py:131-160) --------
-    # everything a stage reads back from the previous step: the in/out vectors of the canopy and soil kernels, the
-    # accumulators of the per-pixel aggregates, the overland and channel router states
-    STATE = tuple(dict.fromkeys(SL._CANOPY_IO + list(SL._V_IO) + PA._STATE + SR._STATE +
-                                ["OFM3Direct", "OFM3Other", "OFM3Forest"] + RT._STATE))
-
+    # ---- warm start (_HotPath.STATE) -----------------------------------------------------------------------------
     def state_names(self):
         return [k for k in self.STATE if k in self.d]
 
@@ -520,11 +596,8 @@ class HotPathDevice:
                 continue                              # a state file written by an object that did not report this map
             a = z[k]
             if k in _CHANNEL_NAMES:
-                if self.Nk < self.N:
-                    rest = np.ones(self.N, bool); rest[self.ids] = False
-                    if np.any(a[rest] != 0):
-                        raise ValueError("state file holds water in %s on pixels this object left out of the channel "
-                                         "domain; build it with compact=False" % k)
+                self._check_inside(a, "state file holds water in %s on pixels this object left out of the channel "
+                                      "domain; build it with compact=False" % k)
                 a = a[self.gpix]
             else:
                 a = self._ordered(a)
@@ -694,80 +767,11 @@ class HotPathDevice:
         m.mbts_after_fused()
         return m.var.MBErrorSplitRoutingM3, m.var.OutletDischargeErrorSplitRouting
 
-    def chan_q_avg(self):
-        """ChanQAvg = sumDisDay / NoRoutSteps (Lisflood_dynamic.py:209): the `dis` output of the reference."""
-        return self.download("sumDisDay") / self.sc["NoRoutSteps"]
-
     def free(self):
-        arrays = {id(a): a for a in list(self.d.values()) + [self._gidx]}
-        arrays.update({id(a): a for fs in self.force for a in fs.values()})
-        if self.rmod is not None:
-            arrays.update({id(a): a for a in list(self.rmod._st["dev"].values()) + list(self.rmod._dev.values())})
-        for a in arrays.values():
-            a.free()
-        for r in (self.r_other, self.r_forest, self.r_direct, self.river):
-            r.close()
-        check(lib().lf_device_synchronize(self.device))       # no upload may still be reading the page-locked buffers
-        for bufs in self.__dict__.pop("_pinned", []):
-            for b in bufs.values():
-                b.free()
+        self._free_shared(list(self.d.values()) + [self._gidx] + [a for fs in self.force for a in fs.values()])
 
 
-def inert_pixels(values, ldd_kinematic, land_mask, split, structures=None):
-    """Land pixels whose routing sub-step is the identity for the whole run: no upstream and no downstream pixel in the
-    kinematic LDD, not a channel pixel (so no sideflow, routing.py:512), regular parameters (0 * inf would turn the
-    zero state into NaN, as it does in the reference), zero split-routing thresholds, an all-zero state, and no part
-    in a structure.  Host mirror of k_inert_flags + the state test of the cell kernel (csrc/lf_router.hip)."""
-    from . import ldd as L
-    N = int(np.asarray(land_mask, bool).sum())
-    get = lambda k, default=0.0: np.broadcast_to(np.asarray(values.get(k, default), dtype=np.float64), (N,))
-    plus0 = lambda a: np.ascontiguousarray(a).view(np.int64) == 0
-    down = L.downstream_index(ldd_kinematic, land_mask)
-    has_up = np.bincount(down[down >= 0], minlength=N) > 0
-    ok = (down < 0) & ~has_up & ~np.broadcast_to(np.asarray(values["IsChannelKinematic"], bool), (N,))
-    with np.errstate(all="ignore"):
-        t = get("InvChanLength") * get("ChanLength") * get("ChannelAlpha") * get("InvChannelAlpha")
-        ok &= np.isfinite(t) & (get("InvChanLength") >= 0)
-        names = ["ChanQKin", "ChanM3Kin", "ChanQ"]
-        if split:
-            ok &= np.isfinite(get("ChannelAlpha2") * get("InvChannelAlpha2"))
-            names += ["QLimit", "Chan2QStart", "Chan2M3Start", "Chan2QKin", "Chan2M3Kin", "CrossSection2Area",
-                      "Sideflow1Chan"]
-    for k in names:
-        ok &= plus0(get(k))
-    if structures is not None:
-        for k in ("LakeIndex", "ReservoirIndex"):
-            if k in structures:
-                ok[np.asarray(structures[k]).astype(np.int64)] = False
-        for k in ("QInM3Old", "QDelta", "TransCum"):
-            if k in structures:
-                ok &= np.broadcast_to(np.asarray(structures[k], np.float64), (N,)) == 0
-        if "InflowPoints" in structures:      # pixels that receive a hydrograph in later steps
-            ok &= ~np.broadcast_to(np.asarray(structures["InflowPoints"], bool), (N,))
-    return ok
-
-
-def _structures_on_subdomain(st, ids, N):
-    """The structure attributes (routing.attach_structures) renumbered for the channel domain `ids` of an N-pixel one."""
-    Nk = ids.size
-    new_id = np.full(N + 1, Nk, np.int64)
-    new_id[ids] = np.arange(Nk)
-    out = {}
-    for k, a in st.items():
-        if k in ("LakeIndex", "ReservoirIndex"):
-            out[k] = new_id[np.asarray(a).astype(np.int64)]
-            if (out[k] == Nk).any():
-                raise ValueError("a structure sits on a pixel outside the channel domain")
-        elif k == "downstruct":
-            out[k] = new_id[np.minimum(np.asarray(a).astype(np.int64), N)][ids].astype(np.int32)
-        elif isinstance(a, np.ndarray) and a.shape == (N,):
-            out[k] = a[ids]
-        else:
-            out[k] = a
-    return out
-
-
-class HotPathEnsemble:
+class HotPathEnsemble(_HotPath):
     """HotPathDevice for an ENSEMBLE -- members that share the LDDs, the geometry and the parameters and differ in state and
     forcing (a forecast ensemble, a calibration batch over the forcing, an EnKF): one model step of every member costs
     roughly the launches of one member.  Per step:
@@ -781,8 +785,9 @@ class HotPathEnsemble:
     forcing rows N + pad apart (soilloop._EnsembleVectors, whose layout code this class uses), channel rows Nk + pad apart
     (routing.routingEnsemble).  Nothing reads or writes the elements between the rows (gaps / set_gaps).  Every member ends
     up, bit for bit, as a HotPathDevice of its own fed the same forcing.
-    With structures= the channel part is the routing module HotPathDevice builds, on the compact channel domain with the
-    subset already applied, and its routing.ensemble(members).
+    Both classes are a _HotPath: the overland routers, the channel domain and the channel router or routing module on it
+    come from the same code.  With structures= the channel part is that routing module (_HotPath._routing_module), on the
+    compact channel domain with the subset already applied, and its routing.ensemble(members).
     Forcing: there are two sets of member rows of Rain, SnowMelt, EWRef, ETRef and ESRef.  step(forcing) and
     prefetch(forcing) hand the vectors over as the caller holds them -- pixel order, [N] or [members, N], float32 or float64,
     any mix -- with one lf_upload_rows per vector into the set that is NOT in use: one asynchronous copy of the raw image on
@@ -794,31 +799,16 @@ class HotPathEnsemble:
     upload_wait() says when they may be refilled -- HotPathDevice's protocol.
     Not in this class (HotPathDevice has them): step_profile, state_maps / load_state_maps and mass_balance."""
 
-    STATE = HotPathDevice.STATE
-    _kept = HotPathDevice._kept
-
     def __init__(self, values, scalars, land_mask, ldd_to_chan, ldd_kinematic, members, split=True, device=0, structures=None,
                  compact=True, overlap_channel=True, report=None, pad=0):
-        self.device, self.split, self.members = device, bool(split), int(members)
-        self.overlap_channel = bool(overlap_channel)
+        land_mask = self._begin(scalars, land_mask, split, device, overlap_channel, report)
+        M = self.members = int(members)
         self._gap = 0.0                      # what lies between the members' rows of the channel part (set_gaps)
-        self.report = None if report is None else set(report)
-        if self.report is not None and not self.report <= set(OPTIONAL_MAPS):
-            raise ValueError("report: not optional maps: %s" % sorted(self.report - set(OPTIONAL_MAPS)))
-        sc = self.sc = dict(scalars)
-        land_mask = np.asarray(land_mask, bool)
-        N = self.N = int(land_mask.sum())
-        M = self.members
-        values = dict(values)
-        kept = self._kept()
+        N, sc = self.N, self.sc
+        kept, wanted = self._kept(), self._wanted
         chan_names = set(RT._STATIC + RT._STATE)
         # ---- overland routers, and the order of every non-channel vector ------------------------------------------------
-        g_surf = Graph(ldd_to_chan, land_mask)
-        alpha_of = np.asarray(values["OFAlpha"], float)
-        mk = lambda row: kinematicWave(None, None, alpha_of[row], sc["Beta"], sc["PixelLength"], sc["DtSec"],
-                                       device=device, graph=g_surf)
-        self.r_other, self.r_forest, self.r_direct = mk(0), mk(1), mk(2)
-        self.pixel_of_position = g_surf.layout()[0].astype(np.int64)
+        self._overland(values, ldd_to_chan, land_mask)
         # ---- land surface: the member rows and shared statics of LandSurfaceEnsemble -------------------------------------
         d = {k: self._ordered(a) for k, a in values.items() if k not in chan_names}
         d.update(sc)
@@ -829,7 +819,6 @@ class HotPathEnsemble:
                 E.dev.pop(k).free()
                 setattr(E.soil, k, None)
         self.stride, self.pstride = E.stride, E.fstride
-        wanted = lambda names: [k for k in names if k not in OPTIONAL_MAPS or k in kept]
 
         def rows(names, group, shape):
             for k in names:
@@ -849,11 +838,6 @@ class HotPathEnsemble:
         p = self.pixel = PA._PixelArgs()
         for k in wanted(PA._V_IN + PA._N_IN + PA._STATE + PA._OUT + ["Theta"]):
             setattr(p, k, E.dev[k].ptr.value)
-        if self.report is not None:        # a [3,N] input that only unreported maps read is not handed to the kernel
-            for src, outs in PA_READERS.items():
-                if not any(o in kept for o in outs):
-                    setattr(p, src, None)
-        p.InvDtDay, p.N = sc["InvDtDay"], N
         # ---- overland step ----------------------------------------------------------------------------------------------
         statics(["OFAlpha"])
         E._static.append("IsChannel")
@@ -864,54 +848,16 @@ class HotPathEnsemble:
         f = self.surface = SR._SurfaceArgs()
         for k in SR._V_IN + SR._N_IN + SR._STATE + SR._OUT + ["SurfaceRunSoil", "scratch"]:
             setattr(f, k, E.dev[k].ptr.value)
-        f.Beta, f.MMtoM3, f.M3toMM = sc["Beta"], sc["MMtoM3"], sc["M3toMM"]
-        f.PixelLength, f.InvPixelLength = sc["PixelLength"], 1 / sc["PixelLength"]
-        f.DtSec, f.InvDtSec, f.InvNoRoutSteps, f.N = sc["DtSec"], 1 / sc["DtSec"], 1 / sc["NoRoutSteps"], N
-        # ---- channel domain and channel part, as HotPathDevice makes them -------------------------------------------------
-        ldd_kinematic = np.asarray(ldd_kinematic, np.float64)
-        drop = inert_pixels(values, ldd_kinematic, land_mask, self.split, structures) if compact else np.zeros(N, bool)
-        if drop.sum() < 0.1 * N:
-            drop[:] = False
-        self.ids = np.nonzero(~drop)[0]
-        Nk = self.Nk = self.ids.size
-        chan_mask = land_mask
-        if Nk < N:
-            chan_mask = np.zeros(land_mask.shape, bool)
-            chan_mask[land_mask] = ~drop
-            ldd_kinematic = ldd_kinematic[self.ids]
-            if structures is not None:
-                structures = _structures_on_subdomain(structures, self.ids, N)
-        v = types.SimpleNamespace(IsChannelKinematic=np.zeros(Nk, bool))
-        for k in chan_names & set(values):
-            setattr(v, k, np.array(np.broadcast_to(np.asarray(values[k]), (N,))[self.ids], copy=True))
-        v.Beta, v.InvBeta, v.DtRouting, v.InvDtRouting = sc["Beta"], 1 / sc["Beta"], sc["DtRouting"], 1 / sc["DtRouting"]
-        v.DtSec, v.NoRoutSteps, v.InvNoRoutSteps = sc["DtSec"], int(sc["NoRoutSteps"]), 1 / sc["NoRoutSteps"]
-        self.kstride = Nk + int(pad)
-        self.rmod, self._qin_old, self._qin = None, None, {}
-        if structures is None:
-            self.river = kinematicWave(ldd_kinematic, chan_mask, v.ChannelAlpha, sc["Beta"], v.ChanLength, sc["DtRouting"],
-                                       alpha_floodplains=v.ChannelAlpha2 if split else None, device=device)
+        self._finish_args(p, f)
+        # ---- channel domain and channel part; the members' channel rows ---------------------------------------------------
+        v, structures = self._channel(values, ldd_kinematic, land_mask, structures, compact)
+        m, Nk = self.rmod, self.Nk
+        self.kstride, self._qin = Nk + int(pad), {}
+        if m is None:
             self.chan = RT.routingEnsemble(v, self.river, M, self.split, self.kstride, device)
         else:
-            v.ToChanM3RunoffDt = np.zeros(Nk)
-            for k, a in structures.items():
-                setattr(v, k, a)
-            opts = dict(SplitRouting=self.split, InitLisflood=False, simulateLakes="LakeIndex" in structures,
-                        simulateReservoirs="ReservoirIndex" in structures, inflow="QInM3Old" in structures,
-                        TransLoss="UpTrans" in structures)
-            m = self.rmod = RT.routing(v, options=opts, device=device, engine_order=True)
-            m.attach_router(ldd_kinematic, chan_mask)
-            m.attach_structures()
-            m.begin_step()
-            m._structures_substep(0, launch=False)
-            m._args.split = 1 if self.split else 0
-            self.river = m.river_router
             self.chan = m.ensemble(M, self.kstride)
-        self.perm = self.river.graph.layout()[0].astype(np.int64)        # engine position -> channel-domain pixel
-        self.gpix = self.ids[self.perm]                                   # engine position -> land pixel
-        inv = np.empty(N, np.int64)
-        inv[self.pixel_of_position] = np.arange(N)
-        self._gidx = DeviceArray.from_host(inv[self.gpix].astype(np.int32), device)
+        self._engine_order()
         # the sideflow rows of the channel loop: ToChanM3RunoffDt of every member in the channel router's engine order
         self._side = DeviceArray(M * self.kstride, np.float64, device).zero()
         if self.rmod is not None:
@@ -927,25 +873,13 @@ class HotPathEnsemble:
         self.force = [{k: E.dev[k] for k in FORCING},
                       {k: DeviceArray(M * self.pstride, np.float64, device).zero() for k in FORCING}]
         self._shared = [{k: E._shared_forcing[k] for k in FORCING}, {k: True for k in FORCING}]
-        self._cur, self._prefetched, self._keep, self._pinned = 0, None, [None, None], []
+        self._cur, self._prefetched, self._keep = 0, None, [None, None]
         # position -> pixel, for the upload (a blocking copy on the main stream: the memsets of set 1 have ended with it,
         # before the copy stream can write the set)
         self._pidx = DeviceArray.from_host(self.pixel_of_position.astype(np.int32), device)
-        self.steps_done = 0
 
-    # ---- orders ------------------------------------------------------------------------------------------------------------
-    def _ordered(self, a):
-        a = np.asarray(a)
-        if a.ndim == 0 or a.shape[-1] != self.N:
-            return a
-        return np.ascontiguousarray(a[..., self.pixel_of_position])
-
-    def _pixel_order(self, a):
-        if a.ndim == 0 or a.shape[-1] != self.N:
-            return a
-        out = np.empty_like(a)
-        out[..., self.pixel_of_position] = a
-        return out
+    def _lai_vectors(self):
+        return self.land.dev
 
     def _put_qin(self, name, rows, staged=False):
         """[members, Nk] in channel-domain pixel order -> the member rows of QInM3Old / QDelta"""
@@ -954,39 +888,15 @@ class HotPathEnsemble:
         self._qin[name].upload(host.reshape(-1), staged=staged)
 
     # ---- one model step ------------------------------------------------------------------------------------------------------
-    def set_lai(self, LAI, LAITerm):
-        """HotPathDevice.set_lai: the members share the two vectors"""
-        check(lib().lf_device_synchronize(self.device))
-        for k, a in (("LAI", LAI), ("LAITerm", LAITerm)):
-            a = np.asarray(a, np.float64)
-            if a.shape != (3, self.N):
-                raise ValueError("%s must be [3, %d]" % (k, self.N))
-            self.land.dev[k].upload(f64(self._ordered(a)))
-
     def set_inflow(self, QInM3):
         """HotPathDevice.set_inflow with QInM3 [N] (every member) or [members, N]"""
-        if self._qin_old is None:
-            raise RuntimeError("inflow hydrographs need structures= with QInM3Old / QDelta (the `inflow` option)")
-        q = np.asarray(QInM3, np.float64)
-        if q.shape not in ((self.N,), (self.members, self.N)):
-            raise ValueError("QInM3 must be [%d] or [%d, %d]" % (self.N, self.members, self.N))
-        q = np.broadcast_to(q, (self.members, self.N))
-        if self.Nk < self.N:
-            rest = np.ones(self.N, bool); rest[self.ids] = False
-            if np.any(q[:, rest] != 0):
-                raise ValueError("inflow at a pixel this object left out of the channel domain; flag the inflow pixels in "
-                                 "structures['InflowPoints'] or build it with compact=False")
-        q = np.ascontiguousarray(q[:, self.ids])
-        delta = (q - self._qin_old) * self.rmod.var.InvNoRoutSteps
-        L, d = lib(), self.device
-        if self.overlap_channel:           # on the channel loop's stream, behind the loop of the step before
-            check(L.lf_side_stream_begin(d))
+        q, delta = self._inflow(QInM3)
+        side = self._side_begin()          # on the channel loop's stream, behind the loop of the step before
         try:
             self._put_qin("QInM3Old", self._qin_old, staged=True)
             self._put_qin("QDelta", delta, staged=True)
         finally:
-            if self.overlap_channel:
-                check(L.lf_side_stream_end(d))
+            self._side_end(side)
         self._qin_old = q
 
     # ---- forcing: two sets of member rows, uploaded on the copy stream and ordered on the device ----------------------------
@@ -1029,12 +939,7 @@ class HotPathEnsemble:
         """HotPathDevice.pinned_forcing for the ensemble: a forcing dict of page-locked [members, N] arrays ([N] with
         per_member=False) in pixel order, to be filled in place and passed to prefetch() / step().  The DMA reads them after
         the call has returned: upload_wait() before refilling a set that was handed over (or alternate between two sets)."""
-        shape = (self.members, self.N) if per_member else (self.N,)
-        bufs = {k: PinnedArray(shape, dtype, self.device) for k in FORCING}
-        self._pinned.append(bufs)
-        return {k: b.a for k, b in bufs.items()}
-
-    upload_wait = HotPathDevice.upload_wait
+        return self._pinned_set((self.members, self.N) if per_member else (self.N,), dtype)
 
     def prefetch(self, forcing):
         """Start uploading the forcing of the NEXT step(forcing) call now, into the set that is not in use: the copy and the
@@ -1070,8 +975,7 @@ class HotPathEnsemble:
         check(L.lf_side_stream_join(dev))         # (before the gather overwrites the sideflow of the loop of the step before)
         check(L.lf_gather_rows_device(dev, self.Nk, self._gidx.ptr, E.dev["ToChanM3RunoffDt"].ptr, self.pstride,
                                       self._side.ptr, self.kstride, M))
-        if self.overlap_channel:
-            check(L.lf_side_stream_begin(dev))
+        side = self._side_begin()
         try:
             sums, nsteps = self.chan.vectors.dev["sumDisDay"], int(self.sc["NoRoutSteps"])
             for m in range(M):                    # dyn.py:177, row by row: the elements between the rows stay as they are
@@ -1083,8 +987,7 @@ class HotPathEnsemble:
                 args = self.chan.vectors.with_overrides(SideflowChanM3=self._side.ptr.value)
                 self.river.routing_substeps_members(args, nsteps, M, self.kstride, 0, self.kstride)          # dyn.py:179-180
         finally:
-            if self.overlap_channel:
-                check(L.lf_side_stream_end(dev))
+            self._side_end(side)
 
     def last_forms(self):
         """the form every stage of the last step took: land / pixel_aggregates / overland 1 single call, 2 members in one
@@ -1157,10 +1060,6 @@ class HotPathEnsemble:
             return out
         return a
 
-    def chan_q_avg(self):
-        """ChanQAvg of every member, [members, N]"""
-        return self.download("sumDisDay") / self.sc["NoRoutSteps"]
-
     def state_names(self):
         return [k for k in self.STATE if k in self.land.dev or k in RT._STATE]
 
@@ -1176,10 +1075,7 @@ class HotPathEnsemble:
             return self.land.set(name, self._ordered(rows))
         if rows.shape != (self.members, self.N):
             raise ValueError("%s must be [%d, %d]" % (name, self.members, self.N))
-        if self.Nk < self.N:
-            rest = np.ones(self.N, bool); rest[self.ids] = False
-            if np.any(rows[:, rest] != 0):
-                raise ValueError("state file holds water in %s on pixels this object left out of the channel "
+        self._check_inside(rows, "state file holds water in %s on pixels this object left out of the channel "
                                  "domain; build it with compact=False" % name)
         self._set_channel_rows(name, rows[:, self.gpix])
 
@@ -1257,15 +1153,5 @@ class HotPathEnsemble:
         check(lib().lf_device_synchronize(self.device))
         self.chan.free()
         self.land.free()
-        for a in [self._gidx, self._side, self._pidx] + list(self._qin.values()) + list(self.force[1 - self._cur].values()):
-            a.free()
-        for bufs in self._pinned:                 # (after the synchronize: no upload is still reading them)
-            for b in bufs.values():
-                b.free()
-        self._pinned = []
-        if self.rmod is not None:
-            arrays = {id(a): a for a in list(self.rmod._st["dev"].values()) + list(self.rmod._dev.values())}
-            for a in arrays.values():
-                a.free()
-        for r in (self.r_other, self.r_forest, self.r_direct, self.river):
-            r.close()
+        self._free_shared([self._gidx, self._side, self._pidx] + list(self._qin.values()) +
+                          list(self.force[1 - self._cur].values()))

@@ -20,6 +20,7 @@ import types
 import numpy as np
 
 from ._lib import DeviceArray, check, f64, lib, u8
+from .channel_domain import channel_domain
 from .hydro_module import HydroModule
 from .kinematic_wave_parallel import kinematicWave
 
@@ -150,7 +151,7 @@ class routing(HydroModule):
         contiguous upstream reads; results are bit-identical.  engine_order=False: device vectors in pixel order, two
         router calls per sub-step that gather / scatter through the permutation (2.3 x slower per call at 10000^2)."""
         self.engine_order = bool(engine_order)
-        # compact (engine order only): pixels whose sub-step is the identity for the whole run (hotpath.inert_pixels:
+        # compact (engine order only): pixels whose sub-step is the identity for the whole run (channel_domain.inert_pixels:
         # isolated, not a channel pixel, regular parameters, zero thresholds and state, no structure) are left out of
         # the router's domain; their vectors stay zero.  Decided in attach_router from the state `var` holds then.
         self.compact = bool(compact) and self.engine_order
@@ -287,24 +288,15 @@ class routing(HydroModule):
         N = self._nfull = int(land_mask.sum())
         structures = not o.get("InitLisflood") and (o.get("simulateLakes") or o.get("simulateReservoirs")) and \
             hasattr(v, "downstruct")
-        ids = np.arange(N)
+        ids, mask = np.arange(N), land_mask
         if self.compact and all(hasattr(v, k) for k in _STATE[:-1]):
-            from .hotpath import inert_pixels
             vals = {k: getattr(v, k) for k in _STATIC + _STATE if hasattr(v, k)}
             st = {k: getattr(v, k) for k, opt in (("LakeIndex", "simulateLakes"), ("ReservoirIndex", "simulateReservoirs"),
                                                   ("QInM3Old", "inflow"), ("QDelta", "inflow"), ("TransCum", "TransLoss"))
                   if o.get(opt) and hasattr(v, k)}
-            drop = inert_pixels(vals, codes, land_mask, self._split(), st or None)
-            if drop.sum() >= 0.1 * N:
-                ids = np.nonzero(~drop)[0]
+            ids, mask = channel_domain(vals, codes, land_mask, self._split(), st or None)
         self._ids = ids
         sub = lambda a: np.broadcast_to(np.asarray(a), (N,))[ids]
-        mask = land_mask
-        if ids.size < N:
-            keep = np.zeros(N, bool)
-            keep[ids] = True
-            mask = np.zeros(land_mask.shape, bool)
-            mask[land_mask] = keep
         graph = None
         if self.engine_order and structures:
             from .kinematic_wave_parallel import Graph

@@ -426,6 +426,84 @@ def test_inert_pixels_and_subdomain_renumbering():
     assert sub["QInM3Old"].size == ids.size and sub["QInM3Old"].sum() == 5.0
 
 
+def _strip_with_pits(k, n=20):
+    """1 x n land strip for the channel-domain rule: pixels 0 .. k-1 are pits nothing flows into (inert), pixels k .. n-2
+    flow east into the pit n-1 (one chain); no channel pixel, regular parameters, all-zero state"""
+    kin = np.full(n, 6.0)
+    kin[:k] = kin[-1] = 5.0
+    values = dict(IsChannelKinematic=np.zeros(n, bool), ChanLength=np.full(n, 1000.0), InvChanLength=np.full(n, 1e-3),
+                  ChannelAlpha=np.full(n, 2.0), InvChannelAlpha=np.full(n, 0.5), ChannelAlpha2=np.full(n, 4.0),
+                  InvChannelAlpha2=np.full(n, 0.25))
+    values.update({s: np.zeros(n) for s in ("ChanQKin", "ChanM3Kin", "Chan2QKin", "Chan2M3Kin", "CrossSection2Area",
+                                            "Sideflow1Chan", "ChanQ", "QLimit", "Chan2QStart", "Chan2M3Start")})
+    return values, kin, np.ones((1, n), bool)
+
+
+def test_channel_domain_drops_from_a_tenth_of_the_pixels_on():
+    """channel_domain.channel_domain, the one owner of the rule: inert pixels leave the channel domain exactly when
+    `compact` is set and they are >= 0.1 * N of the land pixels.  1 of 20 stays, 2 of 20 (the edge itself) go."""
+    from lisflood_amd import channel_domain as CD
+    for k in (1, 2):
+        values, kin, mask = _strip_with_pits(k)
+        assert np.array_equal(np.nonzero(CD.inert_pixels(values, kin, mask, True))[0], np.arange(k))
+    values, kin, mask = _strip_with_pits(1)
+    ids, chan_mask = CD.channel_domain(values, kin, mask, True, None, True)
+    assert np.array_equal(ids, np.arange(20)) and chan_mask is mask
+    values, kin, mask = _strip_with_pits(2)
+    ids, chan_mask = CD.channel_domain(values, kin, mask, True, None, True)
+    assert ids.size == 18 and np.array_equal(ids, np.arange(2, 20))
+    want = np.zeros(20, bool)
+    want[ids] = True
+    assert chan_mask.shape == mask.shape and np.array_equal(chan_mask[mask], want)
+    ids, chan_mask = CD.channel_domain(values, kin, mask, True, None, False)
+    assert np.array_equal(ids, np.arange(20)) and chan_mask is mask
+
+
+def test_every_channel_domain_comes_from_the_one_function(monkeypatch):
+    """HotPathDevice, HotPathEnsemble (through the _channel method of their base, which neither overrides) and
+    routing.attach_router(compact=True) ask channel_domain.channel_domain -- driven here up to the router construction
+    with a stub kinematicWave -- and build their router on the pixels and the mask it returned."""
+    import inspect
+    import types
+    from lisflood_amd import channel_domain as CD, hotpath as HP, routing as RT
+    assert HP.channel_domain is CD.channel_domain and RT.channel_domain is CD.channel_domain
+    assert HP.inert_pixels is CD.inert_pixels and HP._structures_on_subdomain is CD._structures_on_subdomain
+    for mod in (HP, RT):                   # neither restates the rule or asks for the inert pixels itself
+        src = inspect.getsource(mod)
+        assert "0.1 *" not in src and "inert_pixels(" not in src and "def channel_domain" not in src
+    values, kin, mask = _strip_with_pits(2)
+    asked, built = [], []
+
+    def recorder(*a, **kw):
+        asked.append((a, kw))
+        return CD.channel_domain(*a, **kw)
+
+    class router:
+        def __init__(self, codes, land_mask, *a, **kw):
+            built.append((np.array(codes), land_mask))
+            n = int(land_mask.sum())
+            self.graph = types.SimpleNamespace(layout=lambda: (np.arange(n),))
+    for mod in (HP, RT):
+        monkeypatch.setattr(mod, "channel_domain", recorder)
+        monkeypatch.setattr(mod, "kinematicWave", router)
+    sc = dict(Beta=0.6, DtSec=86400.0, DtRouting=3600.0, NoRoutSteps=24)
+    for cls in (HP.HotPathDevice, HP.HotPathEnsemble):
+        assert cls._channel is HP._HotPath._channel and "self._channel(" in inspect.getsource(cls.__init__)
+        hp = object.__new__(cls)
+        land = hp._begin(sc, mask, True, 0, True, None)
+        hp._channel(values, kin, land, None, True)
+        assert hp.Nk == 18 and np.array_equal(hp.ids, np.arange(2, 20)) and isinstance(hp.river, router)
+    v = types.SimpleNamespace(Beta=0.6, DtRouting=3600.0, **values)
+    m = RT.routing(v, options=dict(SplitRouting=True, InitLisflood=False), engine_order=True, compact=True)
+    m.attach_router(kin, mask)
+    assert np.array_equal(m._ids, np.arange(2, 20)) and isinstance(m.river_router, router)
+    assert len(asked) == 3 and len(built) == 3
+    for (a, kw), (codes, chan_mask) in zip(asked, built):
+        assert a[3] is True and np.array_equal(a[1], kin) and a[2] is not None and not kw
+        assert np.array_equal(codes, kin[2:]) and np.array_equal(chan_mask[0], np.arange(20) >= 2)
+    assert [len(a) < 6 or a[5] for a, _ in asked] == [True] * 3
+
+
 def test_root_floor_constant_is_the_exact_threshold_of_the_fifth_power():
     """lf_math.h decides `root^5 > 1e-12` (kinematic_wave_parallel_tools.py:77,81-82) on the root itself:
     LF_ROOT_FLOOR must be the smallest double whose fifth power -- rounded product by product as the kernel forms it --
