@@ -244,6 +244,32 @@ int lf_router_route_ordered_members_multi(int count, lf_router **routers, double
  * dst_stride >= n; the elements between the rows of dst are not written. */
 int lf_gather_rows_device(int device, int64_t n, const int32_t *index_dev, const double *src_dev, int64_t src_stride,
                           double *dst_dev, int64_t dst_stride, int rows);
+/* Products over the members of an ensemble, element by element (lf_members.hip).  Both calls read `members` rows of n
+ * doubles, `stride` elements apart (elements between n and stride are never read); the value of (m, i) is
+ * rows_dev[m * stride + i] / divisor, an IEEE division (divisor = NoRoutSteps on sumDisDay: the bits of ChanQAvg; 1.0: the
+ * element itself).  The results of element i go to index dst_index_dev ? dst_index_dev[i] : i of outputs dst_n long
+ * (dst_index_dev: int32 in device memory, injective -- the caller's word); what no i maps to is not written.  Asynchronous
+ * on the device's library stream, like lf_gather_rows_device.
+ * lf_members_summary_device, in ONE pass over the members in ascending order, every output that is not NULL:
+ *   mean   ((x0 + x1) + x2) + ... in that order, divided by (double)members;
+ *   min / max  folds with the accumulator first (np.minimum / np.maximum): a NaN sticks, on a tie (-0.0 against +0.0 too)
+ *          the earlier member stays;
+ *   exceed [n_thresholds][dst_n] int32: the members with x > thresholds_dev[t * threshold_stride + i] (a NaN on either side
+ *          does not count), for up to 4 threshold rows in the order of the source rows.
+ * lf_members_order_statistics_device: out_dev[r * dst_n + .] is the value with exactly ranks_host[r] values before it when
+ * a goes before b if a < b or b is a NaN and a is none, and otherwise the lower member goes first -- np.sort(x, axis=0,
+ * kind="stable")[rank]; the value itself, so the sign of a zero survives.  Up to 8 ranks (a host array), up to 128 members:
+ * an element's column sits in LDS, 256 lanes per workgroup up to 32 members, 128 up to 64, 64 up to 128.
+ * LF_E_INVALID, with the argument named, before a device is touched: members < 1, n < 0 or beyond the 32-bit range of a
+ * launch, stride < n, dst_n != n without a dst_index_dev, dst_n < n, n_thresholds outside 0..4, thresholds without
+ * thresholds_dev and exceed_dev or with threshold_stride < n, no output at all, n_ranks outside 1..8, a rank outside
+ * [0, members), members > 128 (order statistics), rows_dev or out_dev NULL with n > 0.  n == 0: LF_OK, nothing is launched. */
+int lf_members_summary_device(int device, const double *rows_dev, int members, int64_t stride, int64_t n, double divisor,
+                              const int32_t *dst_index_dev, int64_t dst_n, double *mean_dev, double *min_dev, double *max_dev,
+                              int n_thresholds, const double *thresholds_dev, int64_t threshold_stride, int32_t *exceed_dev);
+int lf_members_order_statistics_device(int device, const double *rows_dev, int members, int64_t stride, int64_t n,
+                                       double divisor, const int32_t *dst_index_dev, int64_t dst_n, int n_ranks,
+                                       const int32_t *ranks_host, double *out_dev);
 /* host form: discharge_host[members][N] in PIXEL order updated in place, lateral_host[members][N] */
 int lf_router_route_members_host(lf_router *r, double *discharge_host, const double *lateral_host,
                                  int members, int section);

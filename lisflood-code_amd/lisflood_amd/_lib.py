@@ -32,6 +32,8 @@ _SIGNATURES = {
           "soil_columns_device_derived soil_last_deferred",
     "ipi": "soil_substep_histogram",
     "ipiiqq": "soil_columns_members_device",
+    "ipiqqdpqipp": "members_order_statistics_device",
+    "ipiqqdpqpppipqp": "members_summary_device",
     "ipiqqq": "pixel_aggregates_members_device",
     "ipiz": "memset",
     "ippii": "lddrepair_raster_device",

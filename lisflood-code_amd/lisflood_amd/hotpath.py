@@ -797,6 +797,11 @@ class HotPathEnsemble(_HotPath):
     that set (lf_compute_acquire .. lf_compute_release around the kernels that read forcing); step(None) stays on the set
     in use, i.e. repeats the forcing of the step before.  pinned_forcing() gives page-locked arrays to fill in place,
     upload_wait() says when they may be refilled -- HotPathDevice's protocol.
+    Results: download(name) brings every member's full vector to the host.  What an ensemble is run for is smaller and is
+    made on the device, behind the channel loop of the last step: summary(name, ...) -- per pixel the mean, minimum and
+    maximum over the members, the members above up to four threshold maps and order statistics (lf_members_summary_device,
+    lf_members_order_statistics_device: one pass over the member rows as they lie, only the product maps cross PCIe) -- and
+    sample(name, pixels), every member at a few gauges (lf_gather_rows_device), whose rows output.TssWriter.append takes.
     Not in this class (HotPathDevice has them): step_profile, state_maps / load_state_maps and mass_balance."""
 
     def __init__(self, values, scalars, land_mask, ldd_to_chan, ldd_kinematic, members, split=True, device=0, structures=None,
@@ -877,6 +882,9 @@ class HotPathEnsemble(_HotPath):
         # position -> pixel, for the upload (a blocking copy on the main stream: the memsets of set 1 have ended with it,
         # before the copy stream can write the set)
         self._pidx = DeviceArray.from_host(self.pixel_of_position.astype(np.int32), device)
+        # summary() / sample(): engine position -> land pixel on the device (made on first use), the product maps, and the
+        # threshold rows and gauge tables by the array object they were made from
+        self._gpix_dev, self._row_of_pixel, self._products, self._thresholds, self._gauges = None, {}, {}, {}, {}
 
     def _lai_vectors(self):
         return self.land.dev
@@ -1060,6 +1068,139 @@ class HotPathEnsemble(_HotPath):
             return out
         return a
 
+    # ---- products over the members, made on the device --------------------------------------------------------------------
+    _CACHED = 8            # threshold sets / gauge tables kept per object (the oldest goes first)
+
+    def _product_rows(self, name):
+        """(device vector, entries of a row, stride, divisor, channel row?) of a vector summary() and sample() take"""
+        if name == "ChanQAvg":                     # Lisflood_dynamic.py:209, as chan_q_avg() divides
+            return self.chan.vectors.dev["sumDisDay"], self.Nk, self.kstride, float(self.sc["NoRoutSteps"]), True
+        if name in RT._STATE + RT._OUT:
+            return self.chan.vectors.dev[name], self.Nk, self.kstride, 1.0, True
+        if name in self.land._pixel and name in self.land.dev:
+            return self.land.dev[name], self.N, self.pstride, 1.0, False
+        raise ValueError("%s is neither a channel row (%s, ChanQAvg) nor an [N] member row of the land part"
+                         % (name, ", ".join(RT._STATE + RT._OUT)))
+
+    def _row_index(self, channel):
+        """device int32: row position -> land pixel (gpix of the channel rows, made once; _pidx of the land rows)"""
+        if not channel:
+            return self._pidx
+        if self._gpix_dev is None:
+            self._gpix_dev = DeviceArray.from_host(self.gpix.astype(np.int32), self.device)
+        return self._gpix_dev
+
+    def _product(self, key, shape, dtype=np.float64):
+        d = self._products.get(key)
+        if d is None or d.shape != tuple(np.atleast_1d(shape).tolist()) or d.dtype != np.dtype(dtype):
+            if d is not None:
+                d.free()
+            d = self._products[key] = DeviceArray(shape, dtype, self.device)
+        return d
+
+    def _cached(self, cache, obj, channel, make):
+        """make(obj, channel) once per distinct object: the entry holds the object, so its id stays its own"""
+        key = (id(obj), channel)
+        hit = cache.get(key)
+        if hit is None or hit[0] is not obj:
+            while len(cache) >= self._CACHED:
+                for d in cache.pop(next(iter(cache)))[1:]:
+                    if isinstance(d, DeviceArray):
+                        d.free()
+            hit = cache[key] = (obj,) + tuple(make(obj, channel))
+        return hit[1:]
+
+    def _upload_thresholds(self, thresholds, channel):
+        """[T, N] or [N] in pixel order -> (device rows in row order, T, what `exceed` is on the pixels outside the channel
+        domain, where every member is 0.0).  Everything summary() needs of the host array: it is not looked at again."""
+        a = np.asarray(thresholds, np.float64)
+        a = a[None] if a.ndim == 1 else a
+        if a.ndim != 2 or a.shape[1] != self.N or not 1 <= a.shape[0] <= 4:
+            raise ValueError("thresholds must be [%d] or [T, %d] with T from 1 to 4" % (self.N, self.N))
+        rows = np.ascontiguousarray(a[:, self.gpix if channel else self.pixel_of_position])
+        fill = (self.members * (0.0 > a[:, self._outside])).astype(np.int32) if channel else None
+        return DeviceArray.from_host(rows, self.device), a.shape[0], fill
+
+    def summary(self, name, mean=True, minimum=True, maximum=True, thresholds=None, ranks=None):
+        """Per-pixel products over the members of one member vector, made on the device in one pass over the rows
+        (lf_members_summary_device; the order statistics: lf_members_order_statistics_device): only the product maps cross
+        PCIe.  -> dict of arrays in pixel order over the land domain:
+            "mean", "min", "max"  [N]: ((x0 + x1) + ...) / members in member order; np.minimum / np.maximum folded in member
+                                  order (a NaN sticks, the earlier member wins a tie);
+            "exceed"  [T, N] int32 with thresholds= ([T, N] or [N], pixel order, T <= 4): the members above each map (a NaN on
+                      either side does not count).  The maps go to the device once per distinct array object: pass the SAME
+                      array every step (a changed copy of it is a new array);
+            "order"   [R, N] with ranks= (up to 8 of 0 .. members - 1; at most 128 members):
+                      np.sort(x, axis=0, kind="stable")[ranks].
+        name: a channel row (RT._STATE + RT._OUT), "ChanQAvg" (sumDisDay / NoRoutSteps, the bits of chan_q_avg()) or an [N]
+        member row of the land part.  Pixels outside the channel domain are what download() gives there, 0.0 in every member.
+        Runs behind the channel loop of the last step (joins the side stream)."""
+        L, dev, M, N = lib(), self.device, self.members, self.N
+        src, n, stride, divisor, channel = self._product_rows(name)
+        want = [k for k, on in (("mean", mean), ("min", minimum), ("max", maximum)) if on]
+        if ranks is not None:
+            ranks = np.ascontiguousarray(np.atleast_1d(ranks), np.int32)
+            if ranks.ndim != 1 or not 1 <= ranks.size <= 8 or ranks.min() < 0 or ranks.max() >= M:
+                raise ValueError("ranks must be 1 to 8 values from 0 to members - 1 = %d" % (M - 1))
+            if M > 128:
+                raise ValueError("order statistics take at most 128 members (%d)" % M)
+        if not want and thresholds is None and ranks is None:
+            raise ValueError("summary(): nothing requested")
+        thr, T, fill = self._cached(self._thresholds, thresholds, channel, self._upload_thresholds) if thresholds is not None \
+            else (None, 0, None)
+        index = self._row_index(channel)
+        check(L.lf_side_stream_join(dev))
+        maps = {k: self._product(k, N) for k in want}
+        if T:
+            maps["exceed"] = self._product("exceed", (T, N), np.int32)
+        if maps:
+            ptr_of = lambda k: maps[k].ptr if k in maps else None
+            check(L.lf_members_summary_device(dev, src.ptr, M, stride, n, divisor, index.ptr, N, ptr_of("mean"), ptr_of("min"),
+                                              ptr_of("max"), T, thr.ptr if T else None, n, ptr_of("exceed")))
+        if ranks is not None:
+            maps["order"] = self._product("order", (ranks.size, N))
+            check(L.lf_members_order_statistics_device(dev, src.ptr, M, stride, n, divisor, index.ptr, N, ranks.size,
+                                                       ranks.ctypes.data_as(C.c_void_p), maps["order"].ptr))
+        out = {k: d.download() for k, d in maps.items()}
+        if channel and self._outside.size:           # the kernels wrote the channel domain's pixels only
+            for k, a in out.items():
+                a[..., self._outside] = fill if k == "exceed" else 0.0
+        return out
+
+    def _gauge_table(self, pixels, channel):
+        """compressed land indices -> (device index in row positions, device [members, gauges] rows, gauges inside the
+        rows' domain); a gauge outside it reads position 0 and is set to 0.0 afterwards"""
+        pix = np.asarray(pixels, np.int64).reshape(-1)
+        if pix.size and (pix.min() < 0 or pix.max() >= self.N):
+            raise ValueError("pixels must be compressed land indices 0 .. %d" % (self.N - 1))
+        if channel not in self._row_of_pixel:
+            row = np.full(self.N, -1, np.int64)
+            row[self.gpix if channel else self.pixel_of_position] = np.arange(self.Nk if channel else self.N)
+            self._row_of_pixel[channel] = row
+        row = self._row_of_pixel[channel][pix]
+        inside = row >= 0
+        if not pix.size:
+            return None, None, inside
+        return (DeviceArray.from_host(np.where(inside, row, 0).astype(np.int32), self.device),
+                DeviceArray(self.members * pix.size, np.float64, self.device), inside)
+
+    def sample(self, name, pixels):
+        """[members, len(pixels)]: the vectors summary() takes at compressed land indices (gauges) -- download(name)[:, pixels]
+        without the full vectors: one lf_gather_rows_device and members * len(pixels) doubles over PCIe.  A gauge outside
+        the channel domain gives 0.0 for a channel row; "ChanQAvg" divides on the host.  The index table is kept per
+        `pixels` array object: pass the same array every step."""
+        L, dev, M = lib(), self.device, self.members
+        src, n, stride, divisor, channel = self._product_rows(name)
+        idx, dst, inside = self._cached(self._gauges, pixels, channel, self._gauge_table)
+        G = inside.size
+        if G == 0 or n == 0:
+            return np.zeros((M, G))
+        check(L.lf_side_stream_join(dev))
+        check(L.lf_gather_rows_device(dev, G, idx.ptr, src.ptr, stride, dst.ptr, G, M))
+        rows = dst.download().reshape(M, G)
+        rows[:, ~inside] = 0.0
+        return rows / self.sc["NoRoutSteps"] if name == "ChanQAvg" else rows
+
     def state_names(self):
         return [k for k in self.STATE if k in self.land.dev or k in RT._STATE]
 
@@ -1153,5 +1294,8 @@ class HotPathEnsemble(_HotPath):
         check(lib().lf_device_synchronize(self.device))
         self.chan.free()
         self.land.free()
+        products = [d for cache in (self._thresholds, self._gauges) for hit in cache.values() for d in hit
+                    if isinstance(d, DeviceArray)] + list(self._products.values()) + [self._gpix_dev]
+        self._thresholds, self._gauges, self._products, self._gpix_dev = {}, {}, {}, None
         self._free_shared([self._gidx, self._side, self._pidx] + list(self._qin.values()) +
-                          list(self.force[1 - self._cur].values()))
+                          list(self.force[1 - self._cur].values()) + [d for d in products if d is not None])

@@ -89,6 +89,17 @@ class TssWriter:
             v = self.router.accuflux(v * self.pixel_area) * self.inv_up_area
         self.rows.append(sample(v, self.pix))
 
+    def append(self, values):
+        """a row that is sampled already: [len(ids)] values in id order, e.g. one member's row of
+        hotpath.HotPathEnsemble.sample(name, pixel_index) -- a gauge series without the full vector on the host.  Only for
+        how="": the other operations need the whole map."""
+        if self.how:
+            raise ValueError("append() takes sampled values; how=%r needs the whole map (sample())" % (self.how,))
+        v = np.array(values, dtype=np.float64).reshape(-1)
+        if v.size != len(self.ids):
+            raise ValueError("append() needs one value per id (%d), got %d" % (len(self.ids), v.size))
+        self.rows.append(v)
+
     def close(self):
         write_tss(self.path, self.ids, self.first, np.array(self.rows).reshape(len(self.rows), len(self.ids)),
                   **self.header_kw)
