@@ -108,6 +108,24 @@ int lf_upload_end(int device, int set);
 int lf_upload_wait(int device, int set);
 int lf_compute_acquire(int device, int set);
 int lf_compute_release(int device, int set);
+/* The mirror image for results: double-buffered downloads on a stream of their own (not the upload stream: both DMA
+ * directions run at once), so that a report map leaves the device beside the kernels of the NEXT step.  For set b in {0, 1}:
+ *     lf_report_acquire(b)   -- the stream the library calls currently go to waits until the last download out of set b's
+ *                               device staging has finished: a kernel enqueued next may overwrite that staging
+ *     <lf_pack_rasters_device into set b's staging>
+ *     lf_download_begin(b)   -- the download stream waits for everything issued so far on the main and on the side stream
+ *     lf_download_copy(dst_host, src_dev, bytes) ...   -- asynchronous device-to-host copies; dst_host from lf_host_alloc
+ *     lf_download_end(b)     -- records the set's event
+ *     lf_download_wait(b)    -- the host blocks until that event; returns at once if the set was never downloaded
+ * Only lf_download_wait blocks the host.  lf_device_synchronize waits for the download stream too; lf_device_trim releases
+ * the stream and its events (made again on next use).  LF_E_INVALID with a message: a set other than 0 or 1, _begin while a
+ * set is open or between lf_lane_fork and lf_lane_join, _copy or _end outside a _begin / _end pair, _end of another set than
+ * the open one, _copy with a NULL pointer and bytes > 0. */
+int lf_report_acquire(int device, int set);
+int lf_download_begin(int device, int set);
+int lf_download_copy(int device, void *dst_host, const void *src_dev, size_t bytes);
+int lf_download_end(int device, int set);
+int lf_download_wait(int device, int set);
 /* A second compute stream for a part of a step that the first kernels of the NEXT step do not depend on (the channel
  * wavefront of a model step beside the canopy / soil / overland kernels of the step after it): between _begin and _end every
  * library call of this device goes to the side stream, behind what the main stream holds so far; after _end the side work
@@ -123,7 +141,8 @@ int lf_side_stream_join(int device);
 int lf_lane_fork(int device);
 int lf_lane_select(int device, int lane);
 int lf_lane_join(int device);
-/* releases what the context keeps for reuse (lane streams, fp32 staging buffers, the staging arena of the *_host forms);
+/* releases what the context keeps for reuse (lane streams, fp32 staging buffers, the staging arena of the *_host forms, the
+ * download stream and its events);
  * waits for the device first, refuses between lf_lane_fork and lf_lane_join or inside a side section */
 int lf_device_trim(int device);
 int lf_memcpy_d2h(int device, void *dst_host, const void *src_dev, size_t bytes);
@@ -270,6 +289,28 @@ int lf_members_summary_device(int device, const double *rows_dev, int members, i
 int lf_members_order_statistics_device(int device, const double *rows_dev, int members, int64_t stride, int64_t n,
                                        double divisor, const int32_t *dst_index_dev, int64_t dst_n, int n_ranks,
                                        const int32_t *ranks_host, double *out_dev);
+/* Report maps in the form a map writer takes (lf_report.hip): for up to 16 sources in ONE launch, source k < nmaps,
+ * row r < rows_host[k] and cell < cells = H * W,  dst_dev[k][r * cells + cell] =
+ *     idx_dev[cell] >= 0 : convert(src_dev[k][r * stride_host[k] + idx_dev[cell]] / divisor_host[k])
+ *     idx_dev[cell] == -1: the fill (the cell is not land)
+ *     idx_dev[cell] == -2: zero of the destination type (a land pixel the source's domain leaves out)
+ * idx_dev: int32 [cells] on the device, one table for every source of the call (the caller's word that its entries stay
+ * inside the rows).  The seven *_host arrays are host arrays of nmaps entries, read before the call returns.  Kinds:
+ * LF_PACK_F64 sources go to LF_PACK_F64 or LF_PACK_F32 (round to nearest even, subnormal results kept, overflow to +-inf, a
+ * NaN stays a NaN, -0.0 keeps its sign: numpy's astype(float32)), LF_PACK_I32 sources to LF_PACK_I32 with the fill (int32_t)fill
+ * and divisor 1.  A divisor of 1.0 skips the division; any other gives the IEEE fp64 quotient.  Elements between the rows
+ * of a source are never read, nothing but the rows_host[k] * cells elements of a destination is written.  A lane owns four
+ * consecutive cells and stores 16 bytes at a time where the destinations allow it (16-byte aligned, rows a multiple of
+ * four cells apart or a single row), one cell otherwise (LF_PACK_CELLS=1 in the environment: always; A/B switch).  Asynchronous on the stream the library calls currently go to.
+ * LF_E_INVALID, with the argument named, before a device is touched: nmaps outside 1..16, cells < 0 or beyond the 32-bit
+ * range of a launch, a NULL array, rows < 1, stride < 0, an unknown kind or pair of kinds, an int32 source with a divisor
+ * other than 1, idx_dev or a source or destination NULL with cells > 0.  cells == 0: LF_OK, nothing is launched. */
+#define LF_PACK_F64 0
+#define LF_PACK_F32 1
+#define LF_PACK_I32 2
+int lf_pack_rasters_device(int device, int nmaps, const void *const *src_dev, void *const *dst_dev, const int32_t *rows_host,
+                           const int64_t *stride_host, const int32_t *src_kind_host, const int32_t *dst_kind_host,
+                           const double *divisor_host, const int32_t *idx_dev, int64_t cells, double fill);
 /* host form: discharge_host[members][N] in PIXEL order updated in place, lateral_host[members][N] */
 int lf_router_route_members_host(lf_router *r, double *discharge_host, const double *lateral_host,
                                  int members, int section);

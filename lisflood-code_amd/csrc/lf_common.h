@@ -54,6 +54,14 @@ struct lf_device_ctx {
     std::map<void *, std::pair<void *, size_t>> upload_stage;
     hipEvent_t copied[2] = {nullptr, nullptr}, consumed[2] = {nullptr, nullptr};
     bool consumed_valid[2] = {false, false}, copied_valid[2] = {false, false};
+    // download stream for double-buffered results (lf_report_acquire, lf_download_*): the copy of a step's report maps runs
+    // beside the kernels of the step after it; per set an event "copy finished", and two events that carry what the main
+    // and the side stream held at lf_download_begin over to the download stream.  All five are made and released together
+    bool down_ready = false;
+    hipStream_t down_stream = nullptr;
+    hipEvent_t downloaded[2] = {nullptr, nullptr}, down_after[2] = {nullptr, nullptr};
+    bool downloaded_valid[2] = {false, false};
+    int down_open = -1; // the set between lf_download_begin and lf_download_end, -1: none
     // page-locked staging ring of lf_memcpy_h2d_staged: small per-step uploads that must not stall the host
     struct staged_slot {
         void *host = nullptr;

@@ -411,6 +411,107 @@ int lf_compute_release(int device, int set)
     return LF_OK;
 }
 
+// ---- double-buffered downloads on a third stream ------------------------------------------------------------------------
+// Protocol for set b in {0, 1}:   lf_report_acquire(b); <kernels writing set b's device staging>;
+//                                 lf_download_begin(b); lf_download_copy(...) x n; lf_download_end(b)   ...   lf_download_wait(b)
+// The kernels wait for the last copy out of set b, the copies wait for the kernels; only lf_download_wait blocks the host.
+static void download_release(lf_device_ctx *c)
+{
+    if (c->down_stream) (void)hipStreamDestroy(c->down_stream);
+    c->down_stream = nullptr;
+    for (int b = 0; b < 2; ++b) {
+        if (c->downloaded[b]) (void)hipEventDestroy(c->downloaded[b]);
+        if (c->down_after[b]) (void)hipEventDestroy(c->down_after[b]);
+        c->downloaded[b] = c->down_after[b] = nullptr;
+        c->downloaded_valid[b] = false;
+    }
+    c->down_open = -1;
+    c->down_ready = false;
+}
+
+static int download_create(lf_device_ctx *c)
+{
+    LF_HIP(hipStreamCreateWithFlags(&c->down_stream, hipStreamNonBlocking));
+    for (int b = 0; b < 2; ++b) {
+        LF_HIP(hipEventCreateWithFlags(&c->downloaded[b], hipEventDisableTiming));
+        LF_HIP(hipEventCreateWithFlags(&c->down_after[b], hipEventDisableTiming));
+    }
+    return LF_OK;
+}
+
+static int download_ctx(int device, int set, lf_device_ctx **out)
+{
+    if (set < 0 || set > 1) return lf_set_error(LF_E_INVALID, "download set must be 0 or 1 (got %d)", set);
+    lf_device_ctx *c;
+    LF_TRY(lf_ctx(device, &c));
+    if (!c->down_ready) {
+        const int rc = download_create(c);
+        if (rc != LF_OK) { // (whatever was made before the failure goes again: nothing half-made stays in the context)
+            download_release(c);
+            return rc;
+        }
+        c->down_ready = true;
+    }
+    *out = c;
+    return LF_OK;
+}
+
+int lf_report_acquire(int device, int set)
+{
+    lf_device_ctx *c;
+    LF_TRY(download_ctx(device, set, &c));
+    if (c->downloaded_valid[set]) LF_HIP(hipStreamWaitEvent(c->stream, c->downloaded[set], 0));
+    return LF_OK;
+}
+
+int lf_download_begin(int device, int set)
+{
+    lf_device_ctx *c;
+    LF_TRY(download_ctx(device, set, &c));
+    if (c->down_open >= 0) return lf_set_error(LF_E_INVALID, "lf_download_begin: set %d is still open (lf_download_end)", c->down_open);
+    if (c->lane_current != 0 || c->lane_forked) return lf_set_error(LF_E_INVALID, "lf_download_begin between lf_lane_fork and lf_lane_join");
+    // behind everything the main stream and the side stream hold now (inside a side section c->stream IS the side stream)
+    LF_HIP(hipEventRecord(c->down_after[0], c->side_active ? c->main_stream : c->stream));
+    LF_HIP(hipStreamWaitEvent(c->down_stream, c->down_after[0], 0));
+    if (c->side_stream) {
+        LF_HIP(hipEventRecord(c->down_after[1], c->side_stream));
+        LF_HIP(hipStreamWaitEvent(c->down_stream, c->down_after[1], 0));
+    }
+    c->down_open = set;
+    return LF_OK;
+}
+
+int lf_download_copy(int device, void *dst_host, const void *src_dev, size_t bytes)
+{
+    if (bytes && (!dst_host || !src_dev)) return lf_set_error(LF_E_INVALID, "lf_download_copy: null argument with bytes > 0");
+    lf_device_ctx *c;
+    LF_TRY(download_ctx(device, 0, &c));
+    if (c->down_open < 0) return lf_set_error(LF_E_INVALID, "lf_download_copy outside lf_download_begin .. lf_download_end");
+    if (bytes) LF_HIP(hipMemcpyAsync(dst_host, src_dev, bytes, hipMemcpyDeviceToHost, c->down_stream));
+    return LF_OK;
+}
+
+int lf_download_end(int device, int set)
+{
+    lf_device_ctx *c;
+    LF_TRY(download_ctx(device, set, &c));
+    if (c->down_open != set)
+        return lf_set_error(LF_E_INVALID, c->down_open < 0 ? "lf_download_end(%d) without lf_download_begin"
+                                                           : "lf_download_end(%d): the open set is the other one", set);
+    c->down_open = -1; // (closed whatever the record says: a failed record must not leave the set open for ever)
+    LF_HIP(hipEventRecord(c->downloaded[set], c->down_stream));
+    c->downloaded_valid[set] = true;
+    return LF_OK;
+}
+
+int lf_download_wait(int device, int set)
+{
+    lf_device_ctx *c;
+    LF_TRY(download_ctx(device, set, &c));
+    if (c->downloaded_valid[set]) LF_HIP(hipEventSynchronize(c->downloaded[set]));
+    return LF_OK;
+}
+
 // ---- lanes: several streams of one device, for work items that do not depend on one another ------------------------------
 // The blocks of a row-block partition that live on ONE GPU (the loopback form of the multi-GPU path) are independent inside a
 // phase -- on real hardware every block has its own GPU.  lf_lane_select(i > 0) sends the library calls that follow to lane
@@ -532,7 +633,7 @@ int lf_side_stream_join(int device)
 }
 
 // Releases what the context created on demand and keeps for reuse: the lane streams and their events, the staging
-// buffers of lf_upload_copy_f32 / lf_upload_rows, the staging arena of the *_host entry points.  Waits for the device first; refuses inside
+// buffers of lf_upload_copy_f32 / lf_upload_rows, the download stream with its events, the staging arena of the *_host entry points.  Waits for the device first; refuses inside
 // a lane or side section.  Everything is created again on next use.
 int lf_device_trim(int device)
 {
@@ -551,6 +652,7 @@ int lf_device_trim(int device)
     for (auto &kv : c->upload_stage)
         if (kv.second.first) (void)hipFree(kv.second.first);
     c->upload_stage.clear();
+    download_release(c); // (synchronised above: no copy is in flight)
     if (c->stage_base) (void)hipFree(c->stage_base);
     c->stage_base = nullptr;
     c->stage_bytes = 0;
@@ -596,6 +698,7 @@ int lf_device_synchronize(int device)
     lf_device_ctx *c;
     LF_TRY(lf_ctx(device, &c));
     LF_HIP(hipStreamSynchronize(c->stream));
+    if (c->down_stream) LF_HIP(hipStreamSynchronize(c->down_stream));
     LF_HIP(hipDeviceSynchronize());
     if (!c->side_active) c->side_pending = false;
     return LF_OK;

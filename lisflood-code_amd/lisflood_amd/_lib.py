@@ -24,7 +24,9 @@ _SIGNATURES = {
     "": "version",
     "i": "side_stream_begin side_stream_end side_stream_join lane_fork lane_join device_trim "
          "device_synchronize timer_start soil_last_form",
-    "ii": "upload_begin upload_end upload_wait compute_acquire compute_release lane_select module_last_form",
+    "ii": "upload_begin upload_end upload_wait compute_acquire compute_release lane_select module_last_form "
+          "report_acquire download_begin download_end download_wait",
+    "iippppppppqd": "pack_rasters_device",
     "iippq": "calibration_streams",
     "iiqp": "substep_stage",
     "ip": "device_free host_free timer_stop canopy_device soil_pf_device inloop_structures "
@@ -43,7 +45,7 @@ _SIGNATURES = {
     "ipppqq": "scale_rows_device",
     "ipppiqi": "router_route_ordered_members_multi",
     "ippqi": "calibration_copy",
-    "ippz": "memcpy_h2d memcpy_h2d_staged upload_copy upload_copy_f32 memcpy_d2h memcpy_d2d",
+    "ippz": "memcpy_h2d memcpy_h2d_staged upload_copy upload_copy_f32 memcpy_d2h memcpy_d2d download_copy",
     "ipqipiiqp": "upload_rows",
     "ipqp": "count_nonfinite",
     "ipz": "device_name",

@@ -17,6 +17,7 @@ import types
 
 import numpy as np
 
+from . import output
 from . import pixel_aggregates as PA
 from . import routing as RT
 from . import soilloop as SL
@@ -42,6 +43,25 @@ PA_READERS = dict(TaInterception=("TaInterceptionAll", "TaInterceptionCUM"), Ta=
                   SeepTopToSubB=("SeepTopToSubPixelB",), SeepSubToGW=("SeepSubToGWPixel",), Theta1a=("Theta1aPixel",),
                   Theta1b=("Theta1bPixel",), Theta2=("Theta2Pixel",), W1a=("Theta", "ThetaAll"), W1b=("Theta", "ThetaAll"),
                   W2=("Theta", "ThetaAll"), SoilDepthTotal=("Theta", "ThetaAll"))
+
+
+class PendingRasters:
+    """Report maps on their way to the host (summary_rasters() / rasters()): the pack kernel and the asynchronous copy into
+    page-locked memory are enqueued, nothing has been waited for.  wait() blocks until the copy has landed (an event, not
+    the device) and returns name -> array: views of the page-locked buffers of the request's buffer set, valid until that set
+    is used again -- the request after the next one.  From then on wait() raises instead of handing out overwritten memory."""
+
+    def __init__(self, owner, buffer_set, serial, views):
+        self._owner, self.buffer_set, self.serial, self._views = owner, buffer_set, serial, views
+
+    def wait(self):
+        o = self._owner
+        if o._report_serial[self.buffer_set] != self.serial:
+            raise RuntimeError("stale PendingRasters handle: request %d used buffer set %d, which a later request has taken "
+                               "over (or free() has released); copy what wait() returns before the request after the next"
+                               % (self.serial, self.buffer_set))
+        check(lib().lf_download_wait(o.device, self.buffer_set))
+        return dict(self._views)
 
 
 class _HotPath:
@@ -74,6 +94,10 @@ class _HotPath:
         land_mask = np.asarray(land_mask, bool)
         self.N = int(land_mask.sum())
         self.rmod, self._qin_old, self._pinned, self.steps_done = None, None, [], 0
+        # rasters() / summary_rasters(): the mask the rasters are laid out on, the index tables of the pack kernel (made on
+        # first use), two buffer sets (device staging, page-locked host image) and which request holds each of them
+        self.land_mask = land_mask
+        self._report_tables, self._report_sets, self._report_serial, self._report_count = {}, [None, None], [0, 0], 0
         return land_mask
 
     def _kept(self):
@@ -240,9 +264,108 @@ class _HotPath:
         of an ensemble)."""
         return self.download("sumDisDay") / self.sc["NoRoutSteps"]
 
+    # ---- report maps as [H, W] rasters, packed on the device and downloaded beside the next step --------------------------
+    _PACK_KIND = {np.dtype(np.float64): 0, np.dtype(np.float32): 1, np.dtype(np.int32): 2}      # LF_PACK_F64 / _F32 / _I32
+    _PACK_MAX = 16                                                                              # sources of one launch
+
+    def _raster_table(self, which):
+        """device int32 [H * W] (output.raster_index), made once: where a raster cell's value sits in "land" rows (the order
+        of pixel_of_position), in "channel" rows (engine order of the channel router; a land pixel outside the channel
+        domain: -2, zero) or in a map in "pixel" order (the product maps)"""
+        d = self._report_tables.get(which)
+        if d is None:
+            row = None
+            if which == "channel":
+                row = np.full(self.N, -1, np.int64)
+                row[self.gpix] = np.arange(self.Nk)
+            elif which == "land" and self.pixel_of_position is not None:
+                row = np.empty(self.N, np.int64)
+                row[self.pixel_of_position] = np.arange(self.N)
+            d = self._report_tables[which] = DeviceArray.from_host(output.raster_index(self.land_mask, row), self.device)
+        return d
+
+    def _report_buffers(self, b, nbytes):
+        """(device staging, page-locked image) of set b, at least nbytes long: grow-only, replaced only once the set's last
+        copy has landed (the caller has waited)"""
+        st = self._report_sets[b]
+        if st is None or st[0].nbytes < nbytes:
+            if st is not None:
+                st[0].free(); st[1].free()
+            st = self._report_sets[b] = (DeviceArray(nbytes, np.uint8, self.device), PinnedArray(nbytes, np.uint8, self.device))
+        return st
+
+    def _report_rasters(self, groups, dtype, fill, side, produce=None):
+        """groups: [(table name, [(key, device vector, rows, stride, divisor, stack)])] -- every source of a group is packed
+        in one launch through the group's table, fp64 sources as `dtype`, int32 sources as int32; a key comes out as [H, W],
+        or as [rows, H, W] if `stack` (rows is 1 without it).  side: the work may go to the channel loop's stream (nothing but
+        that stream writes the sources).  produce(): enqueues what makes the sources, on the stream the pack follows.  -> PendingRasters"""
+        L, dev = lib(), self.device
+        dtype = np.dtype(dtype)
+        if dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+            raise ValueError("dtype must be float32 or float64 (got %s)" % dtype)
+        shape, cells = self.land_mask.shape, self.land_mask.size
+        keys = [s[0] for _, sources in groups for s in sources]
+        if len(set(keys)) != len(keys):
+            raise ValueError("a name is given twice: %s" % keys)
+        if not 1 <= len(keys) <= self._PACK_MAX:
+            raise ValueError("1 to %d maps per call (got %d)" % (self._PACK_MAX, len(keys)))
+        plan, total = [], 0
+        for table, sources in groups:
+            calls = []
+            for key, src, rows, stride, divisor, stack in sources:
+                dt = np.dtype(np.int32) if src.dtype == np.int32 else dtype
+                calls.append(types.SimpleNamespace(key=key, src=src, rows=rows, stride=stride, divisor=divisor, stack=stack,
+                                                   dtype=dt, at=total, nbytes=rows * cells * dt.itemsize))
+                total += -(-calls[-1].nbytes // 256) * 256                     # (every map starts on a 256-byte boundary)
+            if calls:
+                plan.append((self._raster_table(table), calls))
+        b = self._report_count % 2
+        self._report_count += 1
+        # the set is used again: whoever holds its buffers is stale from here on, and its last copy has landed before the
+        # buffers are written (or replaced)
+        check(L.lf_download_wait(dev, b))
+        self._report_serial[b] = self._report_count
+        stage, pin = self._report_buffers(b, max(total, 256))
+        views = {}
+        side = self._side_begin(side)
+        try:
+            if not side:
+                check(L.lf_side_stream_join(dev))
+            if produce is not None:
+                produce()
+            check(L.lf_report_acquire(dev, b))
+            for table, calls in plan:
+                n = len(calls)
+                check(L.lf_pack_rasters_device(
+                    dev, n, (C.c_void_p * n)(*[c.src.ptr.value for c in calls]),
+                    (C.c_void_p * n)(*[stage.ptr.value + c.at for c in calls]), (C.c_int32 * n)(*[c.rows for c in calls]),
+                    (C.c_int64 * n)(*[c.stride for c in calls]), (C.c_int32 * n)(*[self._PACK_KIND[c.src.dtype] for c in calls]),
+                    (C.c_int32 * n)(*[self._PACK_KIND[c.dtype] for c in calls]), (C.c_double * n)(*[c.divisor for c in calls]),
+                    table.ptr, cells, float(fill)))
+                for c in calls:
+                    views[c.key] = pin.a[c.at:c.at + c.nbytes].view(c.dtype).reshape(((c.rows,) if c.stack else ()) + shape)
+            check(L.lf_download_begin(dev, b))
+            try:
+                check(L.lf_download_copy(dev, pin.ptr, stage.ptr, total))
+            finally:
+                check(L.lf_download_end(dev, b))
+        finally:
+            self._side_end(side)
+        return PendingRasters(self, b, self._report_count, views)
+
+    def _report_free(self):
+        for b in (0, 1):
+            check(lib().lf_download_wait(self.device, b))
+            if self._report_sets[b] is not None:
+                self._report_sets[b][0].free(); self._report_sets[b][1].free()
+        for d in self._report_tables.values():
+            d.free()
+        self._report_tables, self._report_sets, self._report_serial = {}, [None, None], [-1, -1]
+
     def _free_shared(self, arrays):
         """`arrays`: the device arrays of the class, which may include the routing module's (each is freed once); then the
         four routers, and -- once no upload can still be reading them -- the page-locked buffers"""
+        self._report_free()
         arrays = {id(a): a for a in arrays}
         if self.rmod is not None:
             arrays.update({id(a): a for a in list(self.rmod._st["dev"].values()) + list(self.rmod._dev.values())})
@@ -575,6 +698,27 @@ class HotPathDevice(_HotPath):
             return out
         return a
 
+    _CHANNEL_ROWS = set(RT._STATIC + RT._STATE + RT._OUT + ["SideflowChanM3"])        # what download() scatters through gpix
+
+    def rasters(self, names, dtype=np.float32, fill=output.FILL):
+        """Report maps of the step just enqueued as [H, W] rasters -- output.decompress(download(name)).astype(dtype) with
+        `fill` outside the land mask, bit for bit -- without waiting for them: up to 16 names, each a channel vector,
+        "ChanQAvg" (the bits of chan_q_avg()) or an [N] fp64 vector of the land part (not the forcing).  A kernel packs the
+        rows as the device holds them into rasters (lf_pack_rasters_device), an asynchronous copy on a stream of its own
+        brings them to page-locked memory; the next step() may be issued at once and runs beside the copy.
+        -> PendingRasters, whose wait() gives name -> array; the arrays live in one of two buffer sets that alternate call by
+        call."""
+        groups = {"channel": [], "land": []}
+        for name in names:
+            if name == "ChanQAvg":                     # Lisflood_dynamic.py:209, as chan_q_avg() divides
+                d, divisor, channel = self.d["sumDisDay"], float(self.sc["NoRoutSteps"]), True
+            else:
+                d, divisor, channel = self.d.get(name), 1.0, name in self._CHANNEL_ROWS
+                if d is None or name in FORCING or d.dtype != np.float64 or not (channel or d.shape == (self.N,)):
+                    raise ValueError("%s is neither a channel vector, ChanQAvg nor an [N] fp64 vector of the land part" % name)
+            groups["channel" if channel else "land"].append((name, d, 1, 0, divisor, False))
+        return self._report_rasters(list(groups.items()), dtype, fill, side=not groups["land"])
+
     # ---- warm start (_HotPath.STATE) -----------------------------------------------------------------------------
     def state_names(self):
         return [k for k in self.STATE if k in self.d]
@@ -802,6 +946,10 @@ class HotPathEnsemble(_HotPath):
     maximum over the members, the members above up to four threshold maps and order statistics (lf_members_summary_device,
     lf_members_order_statistics_device: one pass over the member rows as they lie, only the product maps cross PCIe) -- and
     sample(name, pixels), every member at a few gauges (lf_gather_rows_device), whose rows output.TssWriter.append takes.
+    Maps that are written every step do not wait for the device at all: summary_rasters() and rasters() enqueue the pack
+    kernel (lf_pack_rasters_device: [H, W] rasters of the writer's type, the fill outside the mask) and an asynchronous
+    copy into page-locked memory on a download stream of its own, and return a PendingRasters to wait() on after the next
+    step() has been issued.
     Not in this class (HotPathDevice has them): step_profile, state_maps / load_state_maps and mass_balance."""
 
     def __init__(self, values, scalars, land_mask, ldd_to_chan, ldd_kinematic, members, split=True, device=0, structures=None,
@@ -885,6 +1033,8 @@ class HotPathEnsemble(_HotPath):
         # summary() / sample(): engine position -> land pixel on the device (made on first use), the product maps, and the
         # threshold rows and gauge tables by the array object they were made from
         self._gpix_dev, self._row_of_pixel, self._products, self._thresholds, self._gauges = None, {}, {}, {}, {}
+        # summary_rasters(): product map -> what its pixels outside the channel domain hold (_summary_outside)
+        self._outside_held = {}
 
     def _lai_vectors(self):
         return self.land.dev
@@ -1096,6 +1246,7 @@ class HotPathEnsemble(_HotPath):
             if d is not None:
                 d.free()
             d = self._products[key] = DeviceArray(shape, dtype, self.device)
+            self._outside_held.pop(key, None)
         return d
 
     def _cached(self, cache, obj, channel, make):
@@ -1135,7 +1286,19 @@ class HotPathEnsemble(_HotPath):
         name: a channel row (RT._STATE + RT._OUT), "ChanQAvg" (sumDisDay / NoRoutSteps, the bits of chan_q_avg()) or an [N]
         member row of the land part.  Pixels outside the channel domain are what download() gives there, 0.0 in every member.
         Runs behind the channel loop of the last step (joins the side stream)."""
-        L, dev, M, N = lib(), self.device, self.members, self.N
+        q = self._summary_request(name, mean, minimum, maximum, thresholds, ranks)
+        check(lib().lf_side_stream_join(self.device))
+        maps = self._summary_maps(q)
+        self._summary_kernels(q, maps)
+        out = {k: d.download() for k, d in maps.items()}
+        if q.channel and self._outside.size:         # the kernels wrote the channel domain's pixels only
+            for k, a in out.items():
+                a[..., self._outside] = q.fill if k == "exceed" else 0.0
+        return out
+
+    def _summary_request(self, name, mean, minimum, maximum, thresholds, ranks):
+        """the arguments of summary() checked, the thresholds on the device: what _summary_maps and _summary_kernels take"""
+        M = self.members
         src, n, stride, divisor, channel = self._product_rows(name)
         want = [k for k, on in (("mean", mean), ("min", minimum), ("max", maximum)) if on]
         if ranks is not None:
@@ -1148,24 +1311,73 @@ class HotPathEnsemble(_HotPath):
             raise ValueError("summary(): nothing requested")
         thr, T, fill = self._cached(self._thresholds, thresholds, channel, self._upload_thresholds) if thresholds is not None \
             else (None, 0, None)
-        index = self._row_index(channel)
-        check(L.lf_side_stream_join(dev))
-        maps = {k: self._product(k, N) for k in want}
-        if T:
-            maps["exceed"] = self._product("exceed", (T, N), np.int32)
-        if maps:
+        return types.SimpleNamespace(src=src, n=n, stride=stride, divisor=divisor, channel=channel, want=want, ranks=ranks,
+                                     thr=thr, T=T, fill=fill, index=self._row_index(channel))
+
+    def _summary_maps(self, q):
+        """the device product maps of a request, [N] / [T, N] / [R, N] in pixel order"""
+        maps = {k: self._product(k, self.N) for k in q.want}
+        if q.T:
+            maps["exceed"] = self._product("exceed", (q.T, self.N), np.int32)
+        if q.ranks is not None:
+            maps["order"] = self._product("order", (q.ranks.size, self.N))
+        if not q.channel:                            # land rows fill every pixel: whatever _summary_outside wrote is gone
+            for k in maps:
+                self._outside_held.pop(k, None)
+        return maps
+
+    def _summary_kernels(self, q, maps):
+        L, dev, M, N = lib(), self.device, self.members, self.N
+        if q.want or q.T:
             ptr_of = lambda k: maps[k].ptr if k in maps else None
-            check(L.lf_members_summary_device(dev, src.ptr, M, stride, n, divisor, index.ptr, N, ptr_of("mean"), ptr_of("min"),
-                                              ptr_of("max"), T, thr.ptr if T else None, n, ptr_of("exceed")))
-        if ranks is not None:
-            maps["order"] = self._product("order", (ranks.size, N))
-            check(L.lf_members_order_statistics_device(dev, src.ptr, M, stride, n, divisor, index.ptr, N, ranks.size,
-                                                       ranks.ctypes.data_as(C.c_void_p), maps["order"].ptr))
-        out = {k: d.download() for k, d in maps.items()}
-        if channel and self._outside.size:           # the kernels wrote the channel domain's pixels only
-            for k, a in out.items():
-                a[..., self._outside] = fill if k == "exceed" else 0.0
-        return out
+            check(L.lf_members_summary_device(dev, q.src.ptr, M, q.stride, q.n, q.divisor, q.index.ptr, N, ptr_of("mean"),
+                                              ptr_of("min"), ptr_of("max"), q.T, q.thr.ptr if q.T else None, q.n, ptr_of("exceed")))
+        if q.ranks is not None:
+            check(L.lf_members_order_statistics_device(dev, q.src.ptr, M, q.stride, q.n, q.divisor, q.index.ptr, N, q.ranks.size,
+                                                       q.ranks.ctypes.data_as(C.c_void_p), maps["order"].ptr))
+
+    def _summary_outside(self, q, maps):
+        """The pixels outside the channel domain of the DEVICE product maps as summary() patches them on the host: 0.0, and
+        for `exceed` members * (0.0 > threshold).  The kernels of a channel row never write them, so each map gets them once
+        -- again only after a land row has filled the map, after the map has been made anew, or for another threshold set."""
+        if not (q.channel and self._outside.size):
+            return
+        for k, d in maps.items():
+            if k == "exceed":
+                if self._outside_held.get(k) is not q.fill:
+                    host = np.zeros((q.T, self.N), np.int32)
+                    host[:, self._outside] = q.fill
+                    d.upload(host)
+                    self._outside_held[k] = q.fill          # (the array itself: the cache entry of the threshold set owns it)
+            elif self._outside_held.get(k) is not True:
+                d.zero()
+                self._outside_held[k] = True
+
+    def summary_rasters(self, name, mean=True, minimum=True, maximum=True, thresholds=None, ranks=None, dtype=np.float32,
+                        fill=output.FILL):
+        """summary() as rasters, without waiting: the same kernels into the same device product maps, then the pack kernel
+        (lf_pack_rasters_device) and an asynchronous copy into page-locked memory on a stream of its own; the next step() may
+        be issued at once and runs beside the copy.  -> PendingRasters; wait() gives "mean" / "min" / "max" [H, W] as `dtype`
+        (float32 or float64), "exceed" [T, H, W] int32, "order" [R, H, W] -- output.decompress(summary()[k]).astype(dtype)
+        with `fill` outside the land mask ((int32)fill for "exceed"), bit for bit.  The arrays live in one of two buffer
+        sets that alternate call by call (shared with rasters()): valid until the request after the next."""
+        q = self._summary_request(name, mean, minimum, maximum, thresholds, ranks)
+        maps = self._summary_maps(q)
+        self._summary_outside(q, maps)
+        rows = lambda d: d.shape[0] if len(d.shape) == 2 else 1
+        sources = [(k, d, rows(d), self.N, 1.0, len(d.shape) == 2) for k, d in maps.items()]
+        return self._report_rasters([("pixel", sources)], dtype, fill, side=q.channel,
+                                    produce=lambda: self._summary_kernels(q, maps))
+
+    def rasters(self, names, dtype=np.float32, fill=output.FILL):
+        """HotPathDevice.rasters for every member: up to 16 of the vectors summary() takes -- channel rows, "ChanQAvg" (the
+        bits of chan_q_avg()), [N] member rows of the land part -- as [members, H, W] rasters each, straight from the rows as
+        the device holds them.  -> PendingRasters"""
+        groups = {"channel": [], "land": []}
+        for name in names:
+            src, _, stride, divisor, channel = self._product_rows(name)
+            groups["channel" if channel else "land"].append((name, src, self.members, stride, divisor, True))
+        return self._report_rasters(list(groups.items()), dtype, fill, side=not groups["land"])
 
     def _gauge_table(self, pixels, channel):
         """compressed land indices -> (device index in row positions, device [members, gauges] rows, gauges inside the
@@ -1296,6 +1508,6 @@ class HotPathEnsemble(_HotPath):
         self.land.free()
         products = [d for cache in (self._thresholds, self._gauges) for hit in cache.values() for d in hit
                     if isinstance(d, DeviceArray)] + list(self._products.values()) + [self._gpix_dev]
-        self._thresholds, self._gauges, self._products, self._gpix_dev = {}, {}, {}, None
+        self._thresholds, self._gauges, self._products, self._gpix_dev, self._outside_held = {}, {}, {}, None, {}
         self._free_shared([self._gidx, self._side, self._pidx] + list(self._qin.values()) +
                           list(self.force[1 - self._cur].values()) + [d for d in products if d is not None])

@@ -122,6 +122,26 @@ def decompress(vector, land_mask, fill=FILL):
     return out
 
 
+def raster_index(land_mask, row_of_pixel=None):
+    """The table the device's pack kernel reads (lf_pack_rasters_device): int32 [H * W], per raster cell -1 off the land
+    mask, and for land pixel p (pixel order) row_of_pixel[p], where p's value sits in a row as the device holds it -- or
+    -2 where row_of_pixel[p] < 0: a land pixel the row's domain leaves out.  row_of_pixel None: p itself (rows in pixel
+    order).  decompress() is np.where(table >= 0, row[table], fill) with this table."""
+    land_mask = np.asarray(land_mask, bool)
+    n = int(land_mask.sum())
+    if row_of_pixel is None:
+        rows = np.arange(n, dtype=np.int64)
+    else:
+        rows = np.asarray(row_of_pixel, np.int64).reshape(-1)
+        if rows.size != n:
+            raise ValueError("row_of_pixel must have one entry per land pixel (%d), got %d" % (n, rows.size))
+        if rows.size and rows.max() > np.iinfo(np.int32).max:
+            raise ValueError("row_of_pixel does not fit int32")
+    out = np.full(land_mask.size, -1, np.int32)
+    out[land_mask.reshape(-1)] = np.where(rows < 0, -2, rows)
+    return out
+
+
 def write_netcdf_classic(path, var_name, maps, x, y, time_values=None, time_units="days since 1990-01-01 00:00:00.0",
                          calendar="proleptic_gregorian", dtype="f8", standard_name="", long_name="", units="",
                          dims=("y", "x"), settings_path=""):
