@@ -347,6 +347,29 @@ void launch_sweep_cones(int cw, bool fused, bool ordered, dim3 grid, hipStream_t
     });
 }
 
+// Do rs[0 .. count) sweep the level blocks of rs[0]'s route plan together?  Only on one graph object with one plan; else
+// the segment schedule, which routers swept together share (swept_together)
+bool same_plan(int count, lf_router *const *rs)
+{
+    const lf_router *r = rs[0];
+    bool same = !r->rplan.empty();
+    for (int i = 1; i < count; ++i)
+        same = same && rs[i]->graph_serial == r->graph_serial && r->graph_serial != 0 && rs[i]->rplan.lmax == r->rplan.lmax &&
+               rs[i]->rplan.cw == r->rplan.cw;
+    return same;
+}
+
+// the launch counts of a call that swept rs[0 .. count) (lf_router_last_launches)
+void set_last_stats(int count, lf_router *const *rs, const launch_counts &c)
+{
+    for (int i = 0; i < count; ++i) {
+        rs[i]->last_stats[0] = c.launches;
+        rs[i]->last_stats[1] = c.wide;
+        rs[i]->last_stats[2] = c.narrow;
+        rs[i]->last_stats[3] = rs[i]->NL;
+    }
+}
+
 // `count` (1 to 4) routers built on the same graph (same level schedule) swept together: one launch per level block, wide
 // level or run of narrow levels for all of them.  One router: k_level / k_levels_narrow / k_sweep_cones<.., 1, ..>;
 // several: k_level_multi / k_levels_narrow_multi (blockIdx.y / blockIdx.x picks the router) and, on one graph object with
@@ -371,10 +394,7 @@ int enqueue_route(int count, lf_router **rs, double **q_dev, const double **lat_
             LF_TRY(r->prof_end());
             ++c.launches;
         }
-    bool blocks = !r->rplan.empty();
-    for (int i = 1; i < count; ++i)
-        blocks = blocks && rs[i]->graph_serial == r->graph_serial && r->graph_serial != 0 &&
-                 rs[i]->rplan.lmax == r->rplan.lmax && rs[i]->rplan.cw == r->rplan.cw;
+    const bool blocks = same_plan(count, rs);
     LF_TRY(pick_count(count, [&](auto nr) {
         constexpr int NR = nr;
         auto cones = [&](dim3 grid, const cone_plan_args &C, int64_t cells) {
@@ -406,12 +426,7 @@ int enqueue_route(int count, lf_router **rs, double **q_dev, const double **lat_
         };
         return route_schedule(*r, 0, r->rplan.nblocks(), r->schedule, blocks, c, cones, level, narrow);
     }));
-    for (int i = 0; i < count; ++i) {
-        rs[i]->last_stats[0] = c.launches;
-        rs[i]->last_stats[1] = c.wide;
-        rs[i]->last_stats[2] = c.narrow;
-        rs[i]->last_stats[3] = rs[i]->NL;
-    }
+    set_last_stats(count, rs, c);
     return LF_OK;
 }
 
@@ -425,6 +440,20 @@ int check_plain_call(const lf_router *r, int section)
     return LF_OK;
 }
 
+// May routers[0 .. count) be swept together, one launch for all of them?  Several routers without structure links, on one
+// device and stream, with the same cells, solver and level schedule, none of them profiling.
+bool swept_together(int count, lf_router *const *routers)
+{
+    const lf_router *r0 = routers[0];
+    bool together = count > 1;
+    for (int i = 0; i < count && together; ++i) {
+        const lf_router *r = routers[i];
+        together = !r->linked.p && r->device == r0->device && r->ctx == r0->ctx && r->N == r0->N && r->fused == r0->fused &&
+                   r->h_level_start == r0->h_level_start && !r->profile;
+    }
+    return together;
+}
+
 int route_device(lf_router *r, double *q_dev, const double *lat_dev, int section, bool ordered = false)
 {
     LF_TRY(check_plain_call(r, section));
@@ -435,7 +464,7 @@ int route_device(lf_router *r, double *q_dev, const double *lat_dev, int section
     return LF_OK;
 }
 
-// ---- an ensemble on one router (lf_sweep.h: member_rows) ----------------------------------------------------------------
+// ---- an ensemble on one or several routers of one graph (lf_sweep.h: member_rows) ---------------------------------------
 // Members per lane of k_level_members, chosen by measurement on the shallow 10 000^2 graph: 4
 // members per lane sweep 4 and 8 members in 0.77 of the time of as many single calls, 2 per lane in 0.86, 1 per lane in
 // 0.98; two members are one short group either way (0.87).  LF_MEMBERS_MB = 1, 2 or 4, read at every call, is the A/B
@@ -449,81 +478,99 @@ int members_per_lane()
     }
     return kMembersPerLane;
 }
-constexpr int kMaxGridY = 65535; // blockIdx.y picks the member (cones) or the member group (wide levels)
+constexpr int kMaxGridY = 65535; // blockIdx.y picks the unit (cones) or the member group (wide levels)
 
-template <bool FUSED, int STATICS>
-void launch_level_members(int mb, unsigned blocks, int members, hipStream_t s, int first, int cells, const sweep_args &A,
-                          const member_rows &R)
+template <bool FUSED, int STATICS, bool MULTI>
+void launch_level_members(int mb, unsigned blocks, int count, int members, hipStream_t s, int first, int cells,
+                          const member_block<MULTI> &B, const member_rows &R)
 {
-    const dim3 grid(blocks, (unsigned)((members + mb - 1) / mb)), block(kLevelBlock);
+    const dim3 grid(blocks, (unsigned)(count * ((members + mb - 1) / mb))), block(kLevelBlock);
     if (mb == 1)
-        hipLaunchKernelGGL((k_level_members<FUSED, true, STATICS, 1>), grid, block, 0, s, first, cells, A, R);
+        hipLaunchKernelGGL((k_level_members<FUSED, true, STATICS, 1, MULTI>), grid, block, 0, s, first, cells, B, R);
     else if (mb == 2)
-        hipLaunchKernelGGL((k_level_members<FUSED, true, STATICS, 2>), grid, block, 0, s, first, cells, A, R);
+        hipLaunchKernelGGL((k_level_members<FUSED, true, STATICS, 2, MULTI>), grid, block, 0, s, first, cells, B, R);
     else
-        hipLaunchKernelGGL((k_level_members<FUSED, true, STATICS, 4>), grid, block, 0, s, first, cells, A, R);
+        hipLaunchKernelGGL((k_level_members<FUSED, true, STATICS, 4, MULTI>), grid, block, 0, s, first, cells, B, R);
 }
 
-// `members` rows of q_dev / lat_dev (sweep order, `stride` elements apart) swept on r's schedule: the plan, the
-// LF_ROUTE_CONES switch and the profile hooks of enqueue_route, every launch once for all members (more than kMaxGridY
-// of them: in slices).  The chain / supply cone kernel stays a single router's: here the members fill the machine.
-int enqueue_route_members(lf_router *r, double *q_dev, const double *lat_dev, int members, int64_t stride, int section)
+// `count` routers, one or several that may be swept together (swept_together: the caller's check), each with its `members`
+// rows of q_dev[i] / lat_dev[i] (sweep order, `stride` elements apart), swept on rs[0]'s schedule: the plan, the
+// LF_ROUTE_CONES switch and the profile hooks of enqueue_route (routers swept together do not profile), every launch once
+// for all count * members units (more than kMaxGridY of them: in slices of members).  The chain / supply cone kernel stays
+// a single call's: here the members fill the machine.
+int enqueue_route_members(int count, lf_router **rs, double *const *q_dev, const double *const *lat_dev, int members,
+                          int64_t stride, int section)
 {
+    lf_router *r = rs[0];
     hipStream_t s = r->ctx->stream;
     const int n = (int)r->N;
-    if (!r->fused && r->constant.n < (size_t)members * (size_t)n) {
-        LF_HIP(hipStreamSynchronize(s)); // (earlier calls read the buffer that goes)
-        LF_TRY(r->constant.grow((size_t)members * (size_t)n)); // (refused: r keeps the buffer it had, for fewer members)
+    if (!r->fused) {
+        bool grow = false;
+        for (int i = 0; i < count; ++i) grow = grow || rs[i]->constant.n < (size_t)members * (size_t)n;
+        if (grow) LF_HIP(hipStreamSynchronize(s)); // (earlier calls read the buffers that go)
+        for (int i = 0; i < count; ++i) // (refused: a router keeps the buffer it had, for fewer members)
+            if (rs[i]->constant.n < (size_t)members * (size_t)n) LF_TRY(rs[i]->constant.grow((size_t)members * (size_t)n));
     }
-    const int mb = members_per_lane();
+    const bool blocks = same_plan(count, rs);
+    const int mb = members_per_lane(), slice = kMaxGridY / count;
     launch_counts c;
-    for (int m0 = 0; m0 < members; m0 += kMaxGridY) {
-        const int mm = std::min(members - m0, kMaxGridY);
-        sweep_args A = sweep_args_of(*r, section, q_dev + (int64_t)m0 * stride, nullptr, lat_dev + (int64_t)m0 * stride);
-        if (!r->fused) A.constant = r->constant.p + (int64_t)m0 * n;
-        const member_rows R{(long long)stride, (long long)n, mm};
-        if (!r->fused) {
-            LF_TRY(r->prof_begin(0, (int64_t)n * mm));
-            hipLaunchKernelGGL(k_prep_members, dim3(blocks_for(n), mm), dim3(kBlock), 0, s, n, A, R, (double *)A.constant);
-            LF_TRY(r->prof_end());
-            ++c.launches;
+    LF_TRY(pick_flags(r->fused, count > 1, [&](auto fused, auto multi) {
+        constexpr bool FUSED = fused, MULTI = multi;
+        // what a kernel is handed of the routers' blocks: all of them, or the one router's
+        auto block_of = [](const sweep_args_multi &M) -> const member_block<MULTI> & {
+            if constexpr (MULTI)
+                return M;
+            else
+                return M.r[0];
+        };
+        for (int m0 = 0; m0 < members; m0 += slice) {
+            const int mm = std::min(members - m0, slice), units = count * mm;
+            sweep_args_multi M;
+            for (int i = 0; i < kMaxMulti; ++i) {
+                const int j = i < count ? i : 0;
+                M.r[i] = sweep_args_of(*rs[j], section, q_dev[j] + (int64_t)m0 * stride, nullptr, lat_dev[j] + (int64_t)m0 * stride);
+                if (!FUSED) M.r[i].constant = rs[j]->constant.p + (int64_t)m0 * n;
+            }
+            const member_rows R{(long long)stride, (long long)n, mm};
+            if (!FUSED) {
+                LF_TRY(r->prof_begin(0, (int64_t)n * mm));
+                hipLaunchKernelGGL(k_prep_members<MULTI>, dim3(blocks_for(n), units), dim3(kBlock), 0, s, n, block_of(M), R);
+                LF_TRY(r->prof_end());
+                ++c.launches;
+            }
+            auto cones = [&](dim3 grid, const cone_plan_args &C, int64_t cells) {
+                LF_TRY(r->prof_begin(2, cells * mm));
+                grid.y = (unsigned)units;
+                if (r->rplan.cw == 64)
+                    hipLaunchKernelGGL((k_sweep_cones_members<FUSED, true, 64, MULTI>), grid, dim3(64), 0, s, C, block_of(M), R);
+                else
+                    hipLaunchKernelGGL((k_sweep_cones_members<FUSED, true, kBlock, MULTI>), grid, dim3(kBlock), 0, s, C, block_of(M), R);
+                return r->prof_end();
+            };
+            auto level = [&](int first, int cells) {
+                LF_TRY(r->prof_begin(1, (int64_t)cells * mm));
+                const unsigned nb = (unsigned)level_blocks_for(cells);
+                sweep_args_multi B = M;
+                bool records = FUSED; // the (a, dx) records: for every router or for none
+                for (int i = 0; i < count && records; ++i) records = (B.r[i].adx = level_statics(rs[i], M.r[i])) != nullptr;
+                for (int i = count; i < kMaxMulti; ++i) B.r[i].adx = B.r[0].adx;
+                if (records)
+                    launch_level_members<true, 1, MULTI>(mb, nb, count, mm, s, first, cells, block_of(B), R);
+                else
+                    launch_level_members<FUSED, 0, MULTI>(mb, nb, count, mm, s, first, cells, block_of(B), R);
+                return r->prof_end();
+            };
+            auto narrow = [&](int k0, int k1) {
+                LF_TRY(r->prof_begin(2, (r->h_level_start[k1] - r->h_level_start[k0]) * mm));
+                hipLaunchKernelGGL((k_levels_narrow_members<FUSED, true, MULTI>), dim3(units), dim3(kNarrowBlock), 0, s, k0, k1,
+                                   r->level_start.p, block_of(M), R);
+                return r->prof_end();
+            };
+            LF_TRY(route_schedule(*r, 0, r->rplan.nblocks(), r->schedule, blocks, c, cones, level, narrow));
         }
-        auto cones = [&](dim3 grid, const cone_plan_args &C, int64_t cells) {
-            LF_TRY(r->prof_begin(2, cells * mm));
-            grid.y = (unsigned)mm;
-            pick_flags(r->fused, r->rplan.cw == 64, [&](auto f, auto one_wavefront) {
-                constexpr int CW = one_wavefront ? 64 : kBlock;
-                hipLaunchKernelGGL((k_sweep_cones_members<f, true, CW>), grid, dim3(CW), 0, s, C, A, R);
-            });
-            return r->prof_end();
-        };
-        auto level = [&](int first, int cells) {
-            LF_TRY(r->prof_begin(1, (int64_t)cells * mm));
-            const unsigned blocks = (unsigned)level_blocks_for(cells);
-            sweep_args B = A;
-            if (r->fused) B.adx = level_statics(r, A);
-            if (B.adx)
-                launch_level_members<true, 1>(mb, blocks, mm, s, first, cells, B, R);
-            else if (r->fused)
-                launch_level_members<true, 0>(mb, blocks, mm, s, first, cells, B, R);
-            else
-                launch_level_members<false, 0>(mb, blocks, mm, s, first, cells, B, R);
-            return r->prof_end();
-        };
-        auto narrow = [&](int k0, int k1) {
-            LF_TRY(r->prof_begin(2, (r->h_level_start[k1] - r->h_level_start[k0]) * mm));
-            if (r->fused)
-                hipLaunchKernelGGL((k_levels_narrow_members<true, true>), dim3(mm), dim3(kNarrowBlock), 0, s, k0, k1, r->level_start.p, A, R);
-            else
-                hipLaunchKernelGGL((k_levels_narrow_members<false, true>), dim3(mm), dim3(kNarrowBlock), 0, s, k0, k1, r->level_start.p, A, R);
-            return r->prof_end();
-        };
-        LF_TRY(route_schedule(*r, 0, r->rplan.nblocks(), r->schedule, !r->rplan.empty(), c, cones, level, narrow));
-    }
-    r->last_stats[0] = c.launches;
-    r->last_stats[1] = c.wide;
-    r->last_stats[2] = c.narrow;
-    r->last_stats[3] = r->NL;
+        return (int)LF_OK;
+    }));
+    set_last_stats(count, rs, c);
     return LF_OK;
 }
 
@@ -534,98 +581,9 @@ int route_members(lf_router *r, double *q_dev, const double *lat_dev, int member
     LF_TRY(check_plain_call(r, section));
     if (r->N == 0) return LF_OK;
     LF_HIP(hipSetDevice(r->device));
-    LF_TRY(enqueue_route_members(r, q_dev, lat_dev, members, stride, section));
+    LF_TRY(enqueue_route_members(1, &r, &q_dev, &lat_dev, members, stride, section));
     LF_HIP(hipGetLastError());
     if (r->profile) LF_TRY(r->prof_collect());
-    return LF_OK;
-}
-
-// ---- an ensemble on several routers of one graph (lf_sweep.h: k_*_members_multi) -------------------------------------------
-template <bool FUSED, int STATICS>
-void launch_level_members_multi(int mb, unsigned blocks, int count, int members, hipStream_t s, int first, int cells,
-                                const sweep_args_multi &M, const member_rows &R)
-{
-    const dim3 grid(blocks, (unsigned)(count * ((members + mb - 1) / mb))), block(kLevelBlock);
-    if (mb == 1)
-        hipLaunchKernelGGL((k_level_members_multi<FUSED, true, STATICS, 1>), grid, block, 0, s, first, cells, M, R);
-    else if (mb == 2)
-        hipLaunchKernelGGL((k_level_members_multi<FUSED, true, STATICS, 2>), grid, block, 0, s, first, cells, M, R);
-    else
-        hipLaunchKernelGGL((k_level_members_multi<FUSED, true, STATICS, 4>), grid, block, 0, s, first, cells, M, R);
-}
-
-// `count` routers that may be swept together (the caller's check: the rule of lf_router_route_device_multi), each with its
-// `members` rows of q_dev[i] / lat_dev[i]: enqueue_route_members' schedule on rs[0], every launch once for all
-// count * members units (more than kMaxGridY of them: in slices of members).  Not profiling.
-int enqueue_route_members_multi(int count, lf_router **rs, double *const *q_dev, const double *const *lat_dev, int members,
-                                int64_t stride, int section)
-{
-    lf_router *r = rs[0];
-    hipStream_t s = r->ctx->stream;
-    const int n = (int)r->N;
-    if (!r->fused) {
-        bool grow = false;
-        for (int i = 0; i < count; ++i) grow = grow || rs[i]->constant.n < (size_t)members * (size_t)n;
-        if (grow) LF_HIP(hipStreamSynchronize(s)); // (earlier calls read the buffers that go)
-        for (int i = 0; i < count; ++i)
-            if (rs[i]->constant.n < (size_t)members * (size_t)n) LF_TRY(rs[i]->constant.grow((size_t)members * (size_t)n));
-    }
-    bool blocks = !r->rplan.empty(); // (enqueue_route's condition: one graph object, one plan)
-    for (int i = 1; i < count; ++i)
-        blocks = blocks && rs[i]->graph_serial == r->graph_serial && r->graph_serial != 0 &&
-                 rs[i]->rplan.lmax == r->rplan.lmax && rs[i]->rplan.cw == r->rplan.cw;
-    const int mb = members_per_lane(), slice = kMaxGridY / count;
-    launch_counts c;
-    for (int m0 = 0; m0 < members; m0 += slice) {
-        const int mm = std::min(members - m0, slice), units = count * mm;
-        sweep_args_multi M;
-        for (int i = 0; i < kMaxMulti; ++i) {
-            const int j = i < count ? i : 0;
-            M.r[i] = sweep_args_of(*rs[j], section, q_dev[j] + (int64_t)m0 * stride, nullptr, lat_dev[j] + (int64_t)m0 * stride);
-            if (!r->fused) M.r[i].constant = rs[j]->constant.p + (int64_t)m0 * n;
-        }
-        const member_rows R{(long long)stride, (long long)n, mm};
-        if (!r->fused) {
-            hipLaunchKernelGGL(k_prep_members_multi, dim3(blocks_for(n), units), dim3(kBlock), 0, s, n, M, R);
-            ++c.launches;
-        }
-        auto cones = [&](dim3 grid, const cone_plan_args &C, int64_t) {
-            grid.y = (unsigned)units;
-            pick_flags(r->fused, r->rplan.cw == 64, [&](auto f, auto one_wavefront) {
-                constexpr int CW = one_wavefront ? 64 : kBlock;
-                hipLaunchKernelGGL((k_sweep_cones_members_multi<f, true, CW>), grid, dim3(CW), 0, s, C, M, R);
-            });
-            return (int)LF_OK;
-        };
-        auto level = [&](int first, int cells) {
-            const unsigned nb = (unsigned)level_blocks_for(cells);
-            sweep_args_multi B = M;
-            bool records = r->fused; // the (a, dx) records: for every router or for none
-            for (int i = 0; i < count && records; ++i) records = (B.r[i].adx = level_statics(rs[i], M.r[i])) != nullptr;
-            for (int i = count; i < kMaxMulti; ++i) B.r[i].adx = B.r[0].adx;
-            if (records)
-                launch_level_members_multi<true, 1>(mb, nb, count, mm, s, first, cells, B, R);
-            else if (r->fused)
-                launch_level_members_multi<true, 0>(mb, nb, count, mm, s, first, cells, B, R);
-            else
-                launch_level_members_multi<false, 0>(mb, nb, count, mm, s, first, cells, B, R);
-            return (int)LF_OK;
-        };
-        auto narrow = [&](int k0, int k1) {
-            if (r->fused)
-                hipLaunchKernelGGL((k_levels_narrow_members_multi<true, true>), dim3(units), dim3(kNarrowBlock), 0, s, k0, k1, r->level_start.p, M, R);
-            else
-                hipLaunchKernelGGL((k_levels_narrow_members_multi<false, true>), dim3(units), dim3(kNarrowBlock), 0, s, k0, k1, r->level_start.p, M, R);
-            return (int)LF_OK;
-        };
-        LF_TRY(route_schedule(*r, 0, r->rplan.nblocks(), r->schedule, blocks, c, cones, level, narrow));
-    }
-    for (int i = 0; i < count; ++i) {
-        rs[i]->last_stats[0] = c.launches;
-        rs[i]->last_stats[1] = c.wide;
-        rs[i]->last_stats[2] = c.narrow;
-        rs[i]->last_stats[3] = rs[i]->NL;
-    }
     return LF_OK;
 }
 
@@ -823,13 +781,8 @@ int lf_router_route_device_multi(int count, lf_router **routers, double **discha
     for (int i = 0; i < count; ++i)
         if (!routers[i] || !discharge_dev[i] || !lateral_dev[i]) return lf_set_error(LF_E_INVALID, "null argument");
     LF_TRY(check_section(*routers[0], section)); // (the other routers are checked where they are not swept together)
-    bool together = count > 1 && count <= kMaxMulti;
-    for (int i = 0; i < count && together; ++i) {
-        const lf_router *r = routers[i], *r0 = routers[0];
-        together = !r->linked.p && r->device == r0->device && r->ctx == r0->ctx && r->N == r0->N &&
-                   r->fused == r0->fused && r->h_level_start == r0->h_level_start && !r->profile &&
-                   (section == LF_SECTION_MAIN || r->has_floodplains);
-    }
+    bool together = count <= kMaxMulti && swept_together(count, routers);
+    for (int i = 0; i < count && together; ++i) together = section == LF_SECTION_MAIN || routers[i]->has_floodplains;
     if (!together) {
         for (int i = 0; i < count; ++i)
             LF_TRY(route_device(routers[i], discharge_dev[i], lateral_dev[i], section, engine_order != 0));
@@ -863,8 +816,8 @@ int lf_router_route_ordered_members(lf_router *r, double *discharge_ord_dev, con
 }
 
 // An ensemble on `count` routers: router i sweeps its own `members` rows of discharge_ord_dev[i] / lateral_ord_dev[i].
-// Routers that lf_router_route_device_multi would sweep together get one launch per wide level, narrow run or level block
-// for all count * members units (enqueue_route_members_multi); others one member call each.  The arguments are checked
+// Routers that may be swept together (swept_together) get one launch per wide level, narrow run or level block
+// for all count * members units (enqueue_route_members); others one member call each.  The arguments are checked
 // before a router or a device is touched.
 int lf_router_route_ordered_members_multi(int count, lf_router **routers, double **discharge_ord_dev,
                                           const double **lateral_ord_dev, int members, int64_t stride, int section)
@@ -881,13 +834,7 @@ int lf_router_route_ordered_members_multi(int count, lf_router **routers, double
                                 (long long)routers[i]->N);
     }
     for (int i = 0; i < count; ++i) LF_TRY(check_plain_call(routers[i], section));
-    bool together = count > 1;
-    for (int i = 0; i < count && together; ++i) {
-        const lf_router *r = routers[i], *r0 = routers[0];
-        together = !r->linked.p && r->device == r0->device && r->ctx == r0->ctx && r->N == r0->N && r->fused == r0->fused &&
-                   r->h_level_start == r0->h_level_start && !r->profile;
-    }
-    if (!together) {
+    if (!swept_together(count, routers)) {
         for (int i = 0; i < count; ++i)
             LF_TRY(route_members(routers[i], discharge_ord_dev[i], lateral_ord_dev[i], members, stride, section));
         return LF_OK;
@@ -895,7 +842,7 @@ int lf_router_route_ordered_members_multi(int count, lf_router **routers, double
     if (members == 1) return lf_router_route_device_multi(count, routers, discharge_ord_dev, lateral_ord_dev, section, 1);
     if (routers[0]->N == 0) return LF_OK;
     LF_HIP(hipSetDevice(routers[0]->device));
-    LF_TRY(enqueue_route_members_multi(count, routers, discharge_ord_dev, lateral_ord_dev, members, stride, section));
+    LF_TRY(enqueue_route_members(count, routers, discharge_ord_dev, lateral_ord_dev, members, stride, section));
     LF_HIP(hipGetLastError());
     return LF_OK;
 }

@@ -1042,11 +1042,14 @@ __global__ void __launch_bounds__(kNarrowBlock) k_levels_narrow(int k0, int k1, 
     }
 }
 
-// ---- an ensemble on ONE router (lf_router_route_ordered_members) ---------------------------------------------------------
-// `members` state vectors that share the router's static vectors and so its whole launch schedule: member m's discharge
+// ---- an ensemble on one or several routers (lf_router_route_ordered_members, .._members_multi) ---------------------------
+// `members` state vectors that share a router's static vectors and so its whole launch schedule: member m's discharge
 // and lateral inflow are rows m of two [members][stride] arrays in sweep order.  Every launch of the schedule covers all
-// members; the argument block is one sweep_args (row 0) and this, whatever the count.  Per cell and member the code is
-// sweep_cell_state / sweep_cone on the member's rows: bit-identical to the member swept alone.
+// members; the argument block is one sweep_args (row 0) and member_rows, whatever the count.  Several routers of one graph
+// (the overland routers of an ensemble; MULTI) hand over one such block each, M.r[i], with the same rows R.  The unit of
+// work is (router, member), router-major: a unit picks its router's block (unit_block; one router: the block, the unit is
+// the member) and then runs sweep_cell_state / sweep_cone on the member's view of it -- per cell and member bit-identical to
+// the member swept alone.
 struct member_rows {
     long long stride;  // elements between the rows of the state vectors (>= N)
     long long cstride; // ... and of `constant` (general exponent: N)
@@ -1059,92 +1062,49 @@ __device__ __forceinline__ sweep_args member_view(sweep_args A, const member_row
     if (A.constant) A.constant += (long long)m * R.cstride;
     return A;
 }
+template <bool MULTI>
+using member_block = std::conditional_t<MULTI, sweep_args_multi, sweep_args>;
+// the argument block of `unit`, of per_router units to a router, and the unit's number within its router
+__device__ __forceinline__ const sweep_args &unit_block(const sweep_args &A, int &, int) { return A; }
+__device__ __forceinline__ const sweep_args &unit_block(const sweep_args_multi &M, int &unit, int per_router)
+{
+    const int router = unit / per_router;
+    unit -= router * per_router;
+    return M.r[router];
+}
 
-// k_prep for all members: blockIdx.y = member, vectors in sweep order
-__global__ void __launch_bounds__(kBlock) k_prep_members(int n, sweep_args A, member_rows R, double *__restrict__ constant)
+// k_prep for all units: blockIdx.y = unit, vectors in sweep order
+template <bool MULTI>
+__global__ void __launch_bounds__(kBlock) k_prep_members(int n, member_block<MULTI> B, member_rows R)
 {
     const int p = blockIdx.x * kBlock + threadIdx.x;
     if (p >= n) return;
-    const long long row = (long long)blockIdx.y * R.stride;
-    const double lateral = A.lat[row + p] * (A.dx ? A.dx[p] : A.dx_scalar); // (k_prep's expression, sweep order)
-    constant[(long long)blockIdx.y * R.cstride + p] = A.a[p] * pow(A.qord[row + p], A.beta) + lateral;
-}
-
-// One wide level for all members: a lane owns one cell for a group of MB members (blockIdx.y = group; the last one may be
-// short).  The cell's static operands -- the (a, dx) record or a and dx, and the ups_ptr pair -- are loaded once and stay
-// in registers; per member the requests then go out in sweep_cell_state's order.  (Sharing them through L2 instead would
-// depend on which XCD a workgroup lands on.)  The members one after the other, each behind its own uniform branch (in a
-// loop the compiler hoists the solve's constants out of it and runs out of registers).
-// One member per lane is k_level's code at k_level's 8 wavefronts per SIMD; with the statics held across two or four
-// members the kernel needs 77 VGPRs, and forced into 64 it spills: 6 wavefronts per SIMD (80 VGPRs), no scratch.
-#define LF_MEMBERS_ATTR(MB) __attribute__((amdgpu_waves_per_eu((MB) == 1 ? 8 : 6)))
-template <bool FUSED, bool ORDERED, int STATICS, int MB>
-__global__ void __launch_bounds__(kLevelBlock) LF_MEMBERS_ATTR(MB) k_level_members(int first, int count, sweep_args A, member_rows R)
-{
-    static_assert(ORDERED && (STATICS == 0 || (STATICS == 1 && FUSED)), "members lie in sweep order; records: (a, dx)");
-    const int i = blockIdx.x * kLevelBlock + threadIdx.x;
-    if (i >= count) return;
-    const int p = first + i;
-    const int u0 = A.ups_ptr[p], u1 = A.ups_ptr[p + 1];
-    double ap, dxp;
-    sweep_cell_statics<FUSED, STATICS>(p, A, ap, dxp);
-    const int m0 = (int)blockIdx.y * MB;
-#pragma unroll
-    for (int j = 0; j < MB; ++j)
-        if (m0 + j < R.members) sweep_cell_state<FUSED, ORDERED, false, STATICS>(p, p, ap, dxp, u0, u1, 0, member_view(A, R, m0 + j));
-}
-
-// A run of narrow levels: k_levels_narrow's walk, one workgroup per member (blockIdx.x)
-template <bool FUSED, bool ORDERED>
-__global__ void __launch_bounds__(kNarrowBlock) k_levels_narrow_members(int k0, int k1, const long long *__restrict__ level_start,
-                                                                        sweep_args A, member_rows R)
-{
-    const sweep_args B = member_view(A, R, (int)blockIdx.x);
-    for (int k = k0; k < k1; ++k) {
-        const int first = (int)level_start[k], last = (int)level_start[k + 1];
-        for (int p = first + (int)threadIdx.x; p < last; p += kNarrowBlock) sweep_cell<FUSED, ORDERED, false>(p, B);
-        __threadfence_block();
-        __syncthreads();
-    }
-}
-
-// A level block: k_sweep_cones' cone (one router), blockIdx.y = member
-template <bool FUSED, bool ORDERED, int CW>
-__global__ void __launch_bounds__(CW) k_sweep_cones_members(cone_plan_args C, sweep_args A, member_rows R)
-{
-    sweep_args_multi M;
-    M.r[0] = member_view(A, R, (int)blockIdx.y);
-    sweep_cone<FUSED, ORDERED, 1, CW>(blockIdx.x, C, M);
-}
-
-// ---- an ensemble on SEVERAL routers of one graph (lf_router_route_ordered_members_multi) ---------------------------------
-// The overland routers of an ensemble: M.r[i] is router i's argument block with member 0's rows, R the rows of every router
-// (same stride, same count).  The unit of work is (router, member), router-major; a unit picks its router's block and then
-// runs the member kernels' code on the member's view of it: sweep_cell_state / sweep_cone<.., 1, ..> on member_view.
-// k_prep for all units: blockIdx.y = router * members + member
-__global__ void __launch_bounds__(kBlock) k_prep_members_multi(int n, sweep_args_multi M, member_rows R)
-{
-    const int p = blockIdx.x * kBlock + threadIdx.x;
-    if (p >= n) return;
-    const int router = (int)blockIdx.y / R.members, m = (int)blockIdx.y - router * R.members;
-    const sweep_args &A = M.r[router];
+    int m = (int)blockIdx.y;
+    const sweep_args &A = unit_block(B, m, R.members);
     double *__restrict__ constant = const_cast<double *>(A.constant);
     const long long row = (long long)m * R.stride;
     const double lateral = A.lat[row + p] * (A.dx ? A.dx[p] : A.dx_scalar); // (k_prep's expression, sweep order)
     constant[(long long)m * R.cstride + p] = A.a[p] * pow(A.qord[row + p], A.beta) + lateral;
 }
 
-// One wide level: blockIdx.y = router * groups + group of MB members -- a group stays within one router, whose (a, dx) the
-// lane holds across it
-template <bool FUSED, bool ORDERED, int STATICS, int MB>
-__global__ void __launch_bounds__(kLevelBlock) LF_MEMBERS_ATTR(MB) k_level_members_multi(int first, int count, sweep_args_multi M, member_rows R)
+// One wide level for all units: a lane owns one cell for a group of MB members (blockIdx.y = router * groups + group; a
+// router's last group may be short, so a group stays within one router, whose (a, dx) the lane holds across it).  The
+// cell's static operands -- the (a, dx) record or a and dx, and the ups_ptr pair -- are loaded once and stay in registers;
+// per member the requests then go out in sweep_cell_state's order.  (Sharing them through L2 instead would depend on which
+// XCD a workgroup lands on.)  The members one after the other, each behind its own uniform branch (in a loop the compiler
+// hoists the solve's constants out of it and runs out of registers).
+// One member per lane is k_level's code at k_level's 8 wavefronts per SIMD; with the statics held across two or four
+// members the kernel needs 77 VGPRs (75 for several routers), and forced into 64 it spills: 6 wavefronts per SIMD (80 VGPRs), no scratch.
+#define LF_MEMBERS_ATTR(MB) __attribute__((amdgpu_waves_per_eu((MB) == 1 ? 8 : 6)))
+template <bool FUSED, bool ORDERED, int STATICS, int MB, bool MULTI>
+__global__ void __launch_bounds__(kLevelBlock) LF_MEMBERS_ATTR(MB) k_level_members(int first, int count, member_block<MULTI> B, member_rows R)
 {
     static_assert(ORDERED && (STATICS == 0 || (STATICS == 1 && FUSED)), "members lie in sweep order; records: (a, dx)");
     const int i = blockIdx.x * kLevelBlock + threadIdx.x;
     if (i >= count) return;
-    const int groups = (R.members + MB - 1) / MB;
-    const int router = (int)blockIdx.y / groups, m0 = ((int)blockIdx.y - router * groups) * MB;
-    const sweep_args &A = M.r[router];
+    int group = (int)blockIdx.y;
+    const sweep_args &A = unit_block(B, group, (R.members + MB - 1) / MB);
+    const int m0 = group * MB;
     const int p = first + i;
     const int u0 = A.ups_ptr[p], u1 = A.ups_ptr[p + 1];
     double ap, dxp;
@@ -1154,28 +1114,30 @@ __global__ void __launch_bounds__(kLevelBlock) LF_MEMBERS_ATTR(MB) k_level_membe
         if (m0 + j < R.members) sweep_cell_state<FUSED, ORDERED, false, STATICS>(p, p, ap, dxp, u0, u1, 0, member_view(A, R, m0 + j));
 }
 
-// A run of narrow levels: one workgroup per unit (blockIdx.x = router * members + member)
-template <bool FUSED, bool ORDERED>
-__global__ void __launch_bounds__(kNarrowBlock) k_levels_narrow_members_multi(int k0, int k1, const long long *__restrict__ level_start,
-                                                                              sweep_args_multi M, member_rows R)
+// A run of narrow levels: k_levels_narrow's walk, one workgroup per unit (blockIdx.x)
+template <bool FUSED, bool ORDERED, bool MULTI>
+__global__ void __launch_bounds__(kNarrowBlock) k_levels_narrow_members(int k0, int k1, const long long *__restrict__ level_start,
+                                                                        member_block<MULTI> B, member_rows R)
 {
-    const int router = (int)blockIdx.x / R.members;
-    const sweep_args B = member_view(M.r[router], R, (int)blockIdx.x - router * R.members);
+    int m = (int)blockIdx.x;
+    const sweep_args &A = unit_block(B, m, R.members);
+    const sweep_args V = member_view(A, R, m);
     for (int k = k0; k < k1; ++k) {
         const int first = (int)level_start[k], last = (int)level_start[k + 1];
-        for (int p = first + (int)threadIdx.x; p < last; p += kNarrowBlock) sweep_cell<FUSED, ORDERED, false>(p, B);
+        for (int p = first + (int)threadIdx.x; p < last; p += kNarrowBlock) sweep_cell<FUSED, ORDERED, false>(p, V);
         __threadfence_block();
         __syncthreads();
     }
 }
 
-// A level block: blockIdx.y = router * members + member
-template <bool FUSED, bool ORDERED, int CW>
-__global__ void __launch_bounds__(CW) k_sweep_cones_members_multi(cone_plan_args C, sweep_args_multi M, member_rows R)
+// A level block: k_sweep_cones' cone (one router), blockIdx.y = unit
+template <bool FUSED, bool ORDERED, int CW, bool MULTI>
+__global__ void __launch_bounds__(CW) k_sweep_cones_members(cone_plan_args C, member_block<MULTI> B, member_rows R)
 {
-    const int router = (int)blockIdx.y / R.members;
+    int m = (int)blockIdx.y;
+    const sweep_args &A = unit_block(B, m, R.members);
     sweep_args_multi U;
-    U.r[0] = member_view(M.r[router], R, (int)blockIdx.y - router * R.members);
+    U.r[0] = member_view(A, R, m);
     sweep_cone<FUSED, ORDERED, 1, CW>(blockIdx.x, C, U);
 }
 
@@ -1260,18 +1222,14 @@ inline int core_from_engine_order(lf_router_core &r, const double *src_ord_dev, 
     return LF_OK;
 }
 
-// The instantiation of a kernel for two run-time flags: fn(std::bool_constant<a>, std::bool_constant<b>)
+// The instantiation of a kernel for two run-time flags: fn(std::bool_constant<a>, std::bool_constant<b>), its result
 template <class Fn>
-void pick_flags(bool a, bool b, Fn &&fn)
+decltype(auto) pick_flags(bool a, bool b, Fn &&fn)
 {
-    if (a && b)
-        fn(std::true_type(), std::true_type());
-    else if (a)
-        fn(std::true_type(), std::false_type());
-    else if (b)
-        fn(std::false_type(), std::true_type());
-    else
-        fn(std::false_type(), std::false_type());
+    if (a && b) return fn(std::true_type(), std::true_type());
+    if (a) return fn(std::true_type(), std::false_type());
+    if (b) return fn(std::false_type(), std::true_type());
+    return fn(std::false_type(), std::false_type());
 }
 
 // ... for a count of 1 to 4 (routers swept together, accuflux vectors): fn(std::integral_constant<int, n>), its result

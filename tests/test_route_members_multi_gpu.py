@@ -81,7 +81,7 @@ def test_units_through_every_launch_kind(amd, case, solver, monkeypatch, family,
 @pytest.mark.parametrize("mb", ["1", "2", "4"])
 @pytest.mark.parametrize("config", ["segments", "blocks_wide"])
 def test_wide_levels_with_1_2_4_members_per_lane(amd, case, solver, monkeypatch, config, mb):
-    """every instantiation of k_level_members_multi: the groups of 5 members stay within one router"""
+    """every instantiation of k_level_members<.., MULTI = true>: the groups of 5 members stay within one router"""
     monkeypatch.setenv("LF_MEMBERS_MB", mb)
     every_unit_as_alone(amd, case, monkeypatch, "shallow", config)
 
