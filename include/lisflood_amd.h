@@ -289,6 +289,35 @@ int lf_members_summary_device(int device, const double *rows_dev, int members, i
 int lf_members_order_statistics_device(int device, const double *rows_dev, int members, int64_t stride, int64_t n,
                                        double divisor, const int32_t *dst_index_dev, int64_t dst_n, int n_ranks,
                                        const int32_t *ranks_host, double *out_dev);
+/* Products over the steps of a run, per member and element: one call folds the step's member rows (the same rows, stride,
+ * divisor and value v = rows_dev[m * stride + i] / divisor as above) into accumulators that stay on the device.  Accumulator
+ * rows are track_stride elements apart, in the order of the source rows: peak_dev[m * track_stride + i], and the thresholded
+ * ones [n_thresholds][members] rows, first_above_dev[(t * members + m) * track_stride + i]; the thresholds are shared by the
+ * members, thresholds_dev[t * threshold_stride + i].  Elements between n and a stride are neither read nor written, in the
+ * sources and the accumulators alike.  Every output pointer may be NULL and is then skipped (peak_step_dev needs peak_dev).
+ * first != 0 reads no accumulator:
+ *   peak = v, peak_step = step, sum = v, first_above[t] = v > thr[t] ? step : -1, steps_above[t] = v > thr[t] ? 1 : 0.
+ * first == 0:
+ *   take = v > peak || (v != v && peak == peak);  peak = take ? v : peak;  peak_step = take ? step : peak_step
+ *          (np.maximum with the accumulator first: a NaN sticks from the step it arrives, on a tie -- -0.0 against +0.0
+ *          too -- the earlier step stays);
+ *   sum = sum + v: one addition per call, the sum is in call order;
+ *   with a = v > thr[t] (false with a NaN on either side):
+ *          first_above[t] = (a && steps_above[t] == 0) ? step : first_above[t];  steps_above[t] += a
+ *          (without steps_above_dev the test is first_above[t] < 0).
+ * step is the caller's number of this update, >= 0 (-1 marks "never"); the library keeps no counter.  Asynchronous on the
+ * stream the library calls currently go to.  One lane per element, every (member, element) has one owner; a value that does
+ * not change is not stored, peak_step and (with steps_above_dev) first_above are never loaded: 32 + 8 n_thresholds bytes per
+ * (member, element) at most with every output.
+ * LF_E_INVALID, with the argument named, before a device is touched: members < 1, n < 0 or beyond the 32-bit range of a
+ * launch, stride < n, rows_dev NULL with n > 0, track_stride < n, step < 0, n_thresholds outside 0..4, thresholds without
+ * thresholds_dev, with threshold_stride < n or with both first_above_dev and steps_above_dev NULL, peak_step_dev without
+ * peak_dev, no output at all.  n == 0: LF_OK, nothing is launched. */
+int lf_members_track_device(int device, const double *rows_dev, int members, int64_t stride, int64_t n, double divisor,
+                            int step, int first, int64_t track_stride,
+                            double *peak_dev, int32_t *peak_step_dev, double *sum_dev,
+                            int n_thresholds, const double *thresholds_dev, int64_t threshold_stride,
+                            int32_t *first_above_dev, int32_t *steps_above_dev);
 /* Report maps in the form a map writer takes (lf_report.hip): for up to 16 sources in ONE launch, source k < nmaps,
  * row r < rows_host[k] and cell < cells = H * W,  dst_dev[k][r * cells + cell] =
  *     idx_dev[cell] >= 0 : convert(src_dev[k][r * stride_host[k] + idx_dev[cell]] / divisor_host[k])

@@ -4,6 +4,8 @@
 //
 //   k_members_summary : mean, minimum, maximum and the number of members above up to four threshold maps, one pass
 //   k_members_order   : order statistics (the value with exactly r values before it in the stable order), column in LDS
+//   k_members_track   : one step folded into run-long accumulators per member -- peak and its step, sum, first step above
+//                       and steps above up to four threshold maps -- rows laid out like their source
 //
 // The value of (m, i) is rows[m * stride + i] / divisor, an IEEE division (divisor 1: the element itself), the result of
 // element i goes to dst_index ? dst_index[i] : i.  Everything is in member order: the sum is ((x0 + x1) + x2) + ..., the
@@ -33,6 +35,17 @@ struct summary_out {
     const double *thresholds;
     long long threshold_stride;
     int *exceed;
+};
+
+struct track_out {
+    double *peak;
+    int *peak_step;
+    double *sum;
+    const double *thresholds;
+    long long threshold_stride;
+    int *first_above, *steps_above;
+    long long track_stride;
+    int step;
 };
 
 struct order_out {
@@ -88,6 +101,79 @@ __global__ void __launch_bounds__(kSummaryLanes) k_members_summary(members_rows 
     if (O.max) O.max[dst] = hi;
 #pragma unroll
     for (int t = 0; t < NT; ++t) O.exceed[(long long)t * R.dst_n + dst] = above[t];
+}
+
+// What one (member, element) holds of its accumulators while a group of source rows is in flight: the peak, the sum and, per
+// threshold, steps_above -- or first_above where there is no steps_above (its sign then says whether the value was above before).
+template <int NT>
+struct track_held {
+    double peak, sum;
+    int had[NT > 0 ? NT : 1];
+};
+
+// The streaming update of the run-long accumulators (lf_members_track_device): the summary kernel's shape -- one lane per
+// element, its NT thresholds in registers, kUnroll source rows in flight -- with the member's accumulators loaded beside its
+// source row.  Every (member, element) has one owner; peak, peak_step and first_above are stored only where they change,
+// steps_above only where it counts, peak_step and (with steps_above) first_above are never loaded.  FIRST: nothing is loaded.
+template <int NT, bool DIV, bool FIRST>
+__global__ void __launch_bounds__(kSummaryLanes) k_members_track(members_rows R, track_out O)
+{
+    const long long i = (long long)blockIdx.x * kSummaryLanes + threadIdx.x;
+    if (i >= R.n) return;
+    double thr[NT > 0 ? NT : 1];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) thr[t] = O.thresholds[(long long)t * O.threshold_stride + i];
+    const double *p = R.rows + i;
+    auto row_of = [&](int t, int m) { return ((long long)t * R.members + m) * O.track_stride + i; };
+    auto load = [&](int m) {
+        track_held<NT> h = {};
+        if (!FIRST) {
+            if (O.peak) h.peak = O.peak[row_of(0, m)];
+            if (O.sum) h.sum = O.sum[row_of(0, m)];
+#pragma unroll
+            for (int t = 0; t < NT; ++t) h.had[t] = O.steps_above ? O.steps_above[row_of(t, m)] : O.first_above[row_of(t, m)];
+        }
+        return h;
+    };
+    auto take = [&](int m, double raw, const track_held<NT> &h) {
+        const double v = member_value<DIV>(raw, R.divisor);
+        const long long at = row_of(0, m);
+        if (FIRST) {
+            if (O.peak) O.peak[at] = v;
+            if (O.peak_step) O.peak_step[at] = O.step;
+            if (O.sum) O.sum[at] = v;
+        } else {
+            if (O.peak && ((v > h.peak) || (v != v && h.peak == h.peak))) {
+                O.peak[at] = v;
+                if (O.peak_step) O.peak_step[at] = O.step;
+            }
+            if (O.sum) O.sum[at] = h.sum + v;
+        }
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            const bool above = v > thr[t];
+            const long long att = row_of(t, m);
+            if (FIRST) {
+                if (O.first_above) O.first_above[att] = above ? O.step : -1;
+                if (O.steps_above) O.steps_above[att] = above ? 1 : 0;
+            } else if (above) {
+                if (O.first_above && (O.steps_above ? h.had[t] == 0 : h.had[t] < 0)) O.first_above[att] = O.step;
+                if (O.steps_above) O.steps_above[att] = h.had[t] + 1;
+            }
+        }
+    };
+    int m = 0;
+    for (; m + kUnroll <= R.members; m += kUnroll) {
+        double raw[kUnroll];
+        track_held<NT> held[kUnroll];
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u) raw[u] = row_load(p + (long long)(m + u) * R.stride);
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u) held[u] = load(m + u);
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u) take(m + u, raw[u], held[u]);
+    }
+    for (; m < R.members; ++m) take(m, row_load(p + (long long)m * R.stride), load(m));
 }
 
 // a goes before b whatever their members: a < b, or b is a NaN and a is none (np.sort puts the NaNs last)
@@ -148,6 +234,23 @@ void launch_summary(hipStream_t s, const members_rows &R, const summary_out &O)
         hipLaunchKernelGGL((k_members_summary<NT, true>), grid, block, 0, s, R, O);
 }
 
+template <int NT>
+void launch_track(hipStream_t s, const members_rows &R, const track_out &O, bool first)
+{
+    const dim3 grid((unsigned)((R.n + kSummaryLanes - 1) / kSummaryLanes)), block(kSummaryLanes);
+    if (R.divisor == 1.0) {
+        if (first)
+            hipLaunchKernelGGL((k_members_track<NT, false, true>), grid, block, 0, s, R, O);
+        else
+            hipLaunchKernelGGL((k_members_track<NT, false, false>), grid, block, 0, s, R, O);
+    } else {
+        if (first)
+            hipLaunchKernelGGL((k_members_track<NT, true, true>), grid, block, 0, s, R, O);
+        else
+            hipLaunchKernelGGL((k_members_track<NT, true, false>), grid, block, 0, s, R, O);
+    }
+}
+
 template <int W>
 void launch_order(hipStream_t s, const members_rows &R, const order_out &O)
 {
@@ -185,6 +288,42 @@ int lf_members_summary_device(int device, const double *rows_dev, int members, i
     case 2: launch_summary<2>(c->stream, R, O); break;
     case 3: launch_summary<3>(c->stream, R, O); break;
     default: launch_summary<4>(c->stream, R, O); break;
+    }
+    LF_HIP(hipGetLastError());
+    return LF_OK;
+}
+
+int lf_members_track_device(int device, const double *rows_dev, int members, int64_t stride, int64_t n, double divisor, int step,
+                            int first, int64_t track_stride, double *peak_dev, int32_t *peak_step_dev, double *sum_dev,
+                            int n_thresholds, const double *thresholds_dev, int64_t threshold_stride, int32_t *first_above_dev,
+                            int32_t *steps_above_dev)
+{
+    LF_TRY(check_rows(rows_dev, members, stride, n, nullptr, n));
+    if (track_stride < n)
+        return lf_set_error(LF_E_INVALID, "track_stride %lld is less than n = %lld", (long long)track_stride, (long long)n);
+    if (step < 0) return lf_set_error(LF_E_INVALID, "step must be at least 0 (got %d): -1 is the mark of never", step);
+    if (n_thresholds < 0 || n_thresholds > kMaxThresholds)
+        return lf_set_error(LF_E_INVALID, "n_thresholds must be 0 to %d (got %d)", kMaxThresholds, n_thresholds);
+    if (n_thresholds > 0 && !thresholds_dev) return lf_set_error(LF_E_INVALID, "thresholds_dev is NULL with n_thresholds = %d", n_thresholds);
+    if (n_thresholds > 0 && threshold_stride < n)
+        return lf_set_error(LF_E_INVALID, "threshold_stride %lld is less than n = %lld", (long long)threshold_stride, (long long)n);
+    if (n_thresholds > 0 && !first_above_dev && !steps_above_dev)
+        return lf_set_error(LF_E_INVALID, "first_above_dev and steps_above_dev are both NULL with n_thresholds = %d", n_thresholds);
+    if (peak_step_dev && !peak_dev) return lf_set_error(LF_E_INVALID, "peak_step_dev without peak_dev: the peak decides when it changes");
+    if (!peak_dev && !sum_dev && n_thresholds == 0)
+        return lf_set_error(LF_E_INVALID, "no output requested: peak_dev and sum_dev are NULL and n_thresholds is 0");
+    if (n == 0) return LF_OK;
+    lf_device_ctx *c;
+    LF_TRY(lf_ctx(device, &c));
+    const members_rows R = {rows_dev, (long long)stride, (long long)n, (long long)n, members, divisor, nullptr};
+    const track_out O = {peak_dev, (int *)peak_step_dev, sum_dev, thresholds_dev, (long long)threshold_stride,
+                         (int *)first_above_dev, (int *)steps_above_dev, (long long)track_stride, step};
+    switch (n_thresholds) {
+    case 0: launch_track<0>(c->stream, R, O, first != 0); break;
+    case 1: launch_track<1>(c->stream, R, O, first != 0); break;
+    case 2: launch_track<2>(c->stream, R, O, first != 0); break;
+    case 3: launch_track<3>(c->stream, R, O, first != 0); break;
+    default: launch_track<4>(c->stream, R, O, first != 0); break;
     }
     LF_HIP(hipGetLastError());
     return LF_OK;

@@ -35,6 +35,7 @@ _SIGNATURES = {
     "ipi": "soil_substep_histogram",
     "ipiiqq": "soil_columns_members_device",
     "ipiqqdpqipp": "members_order_statistics_device",
+    "ipiqqdiiqpppipqpp": "members_track_device",
     "ipiqqdpqpppipqp": "members_summary_device",
     "ipiqqq": "pixel_aggregates_members_device",
     "ipiz": "memset",

@@ -28,6 +28,9 @@ from .kinematic_wave_parallel import Graph, kinematicWave
 
 FORCING = ("Rain", "SnowMelt", "EWRef", "ETRef", "ESRef")
 _CHANNEL_NAMES = set(RT._STATIC + RT._STATE + RT._OUT)
+# HotPathEnsemble.track_begin: the derived names of a tracked name's accumulators, and what lies between the int32 rows
+_TRACK_F64, _TRACK_I32 = ("peak", "sum", "period_mean"), ("peak_step", "first_above", "steps_above")
+TRACK_GAP_I32 = -7
 
 
 # Maps of the land-surface stages that nothing else on the hot path reads (HotPathDevice(report=...)): the soil kernel's
@@ -297,8 +300,8 @@ class _HotPath:
     def _report_rasters(self, groups, dtype, fill, side, produce=None):
         """groups: [(table name, [(key, device vector, rows, stride, divisor, stack)])] -- every source of a group is packed
         in one launch through the group's table, fp64 sources as `dtype`, int32 sources as int32; a key comes out as [H, W],
-        or as [rows, H, W] if `stack` (rows is 1 without it).  side: the work may go to the channel loop's stream (nothing but
-        that stream writes the sources).  produce(): enqueues what makes the sources, on the stream the pack follows.  -> PendingRasters"""
+        or as [rows, H, W] if `stack` (rows is 1 without it; a tuple: the leading shape the rows are split into).  side: the
+        work may go to the channel loop's stream (nothing but that stream writes the sources).  produce(): enqueues what makes the sources, on the stream the pack follows.  -> PendingRasters"""
         L, dev = lib(), self.device
         dtype = np.dtype(dtype)
         if dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
@@ -343,7 +346,8 @@ class _HotPath:
                     (C.c_int32 * n)(*[self._PACK_KIND[c.dtype] for c in calls]), (C.c_double * n)(*[c.divisor for c in calls]),
                     table.ptr, cells, float(fill)))
                 for c in calls:
-                    views[c.key] = pin.a[c.at:c.at + c.nbytes].view(c.dtype).reshape(((c.rows,) if c.stack else ()) + shape)
+                    lead = c.stack if isinstance(c.stack, tuple) else ((c.rows,) if c.stack else ())
+                    views[c.key] = pin.a[c.at:c.at + c.nbytes].view(c.dtype).reshape(lead + shape)
             check(L.lf_download_begin(dev, b))
             try:
                 check(L.lf_download_copy(dev, pin.ptr, stage.ptr, total))
@@ -950,6 +954,10 @@ class HotPathEnsemble(_HotPath):
     kernel (lf_pack_rasters_device: [H, W] rasters of the writer's type, the fill outside the mask) and an asynchronous
     copy into page-locked memory on a download stream of its own, and return a PendingRasters to wait() on after the next
     step() has been issued.
+    Products over the steps of a run -- every member's peak and when it came, whether, when and for how long it was above
+    threshold maps, the period mean -- are folded on the device step by step: track_begin(name, thresholds) and from then
+    on one lf_members_track_device per step(); the accumulators lie like their source and go through summary() / rasters() /
+    sample() / download() as "<name>.peak" and so on.  They are not part of save_state() / load_state().
     Not in this class (HotPathDevice has them): step_profile, state_maps / load_state_maps and mass_balance."""
 
     def __init__(self, values, scalars, land_mask, ldd_to_chan, ldd_kinematic, members, split=True, device=0, structures=None,
@@ -1035,6 +1043,8 @@ class HotPathEnsemble(_HotPath):
         self._gpix_dev, self._row_of_pixel, self._products, self._thresholds, self._gauges = None, {}, {}, {}, {}
         # summary_rasters(): product map -> what its pixels outside the channel domain hold (_summary_outside)
         self._outside_held = {}
+        # track_begin(): tracked name -> its accumulators on the device and the number of updates so far
+        self._trackers = {}
 
     def _lai_vectors(self):
         return self.land.dev
@@ -1130,6 +1140,7 @@ class HotPathEnsemble(_HotPath):
                                             self.stride, self.pstride))                                     # dyn.py:165
         finally:                                  # (nothing behind this point reads forcing: set b may be uploaded again)
             check(L.lf_compute_release(dev, b))
+        self._track_update(False)                 # trackers of land rows: on the main stream, behind the overland step
         check(L.lf_side_stream_join(dev))         # (before the gather overwrites the sideflow of the loop of the step before)
         check(L.lf_gather_rows_device(dev, self.Nk, self._gidx.ptr, E.dev["ToChanM3RunoffDt"].ptr, self.pstride,
                                       self._side.ptr, self.kstride, M))
@@ -1144,6 +1155,7 @@ class HotPathEnsemble(_HotPath):
             else:
                 args = self.chan.vectors.with_overrides(SideflowChanM3=self._side.ptr.value)
                 self.river.routing_substeps_members(args, nsteps, M, self.kstride, 0, self.kstride)          # dyn.py:179-180
+            self._track_update(True)              # trackers of channel rows: behind the channel loop, on its stream
         finally:
             self._side_end(side)
 
@@ -1190,8 +1202,17 @@ class HotPathEnsemble(_HotPath):
 
     def download(self, name):
         """[members, N] / [members, 3, N] in pixel order of a member vector, the array itself of a shared one; channel
-        vectors scattered to the land domain as HotPathDevice.download does"""
+        vectors scattered to the land domain as HotPathDevice.download does.  The accumulators of a tracker (track_begin):
+        "<name>.peak" / ".sum" / ".period_mean" [members, N], "<name>.peak_step" int32 [members, N], "<name>.first_above" /
+        ".steps_above" int32 [T, members, N]; outside the channel domain a channel row's are 0.0 and, the integer rows, 0
+        (they are not tracked there)"""
         E = self.land
+        t, key = self._tracked(name)
+        if t is not None:
+            rows = self._track_rows(t, key)[0]
+            rows = self._to_land(rows.reshape(-1, t.n), True).reshape(rows.shape[:-1] + (self.N,)) if t.channel \
+                else self._pixel_order(rows)
+            return rows / np.float64(t.steps) if key == "period_mean" else rows
         if name in E.dev and name != "scratch":
             return self._pixel_order(E.get(name))
         if name in self.chan._groups and self.chan._groups[name][2] or name in RT._STATE + RT._OUT + ["SideflowChanM3"]:
@@ -1222,7 +1243,19 @@ class HotPathEnsemble(_HotPath):
     _CACHED = 8            # threshold sets / gauge tables kept per object (the oldest goes first)
 
     def _product_rows(self, name):
-        """(device vector, entries of a row, stride, divisor, channel row?) of a vector summary() and sample() take"""
+        """(device vector, entries of a row, stride, divisor, channel row?) of a vector summary() and sample() take: a member
+        vector of a stage (_source_rows) or an fp64 accumulator of a tracker (track_begin)"""
+        t, key = self._tracked(name)
+        if t is None:
+            return self._source_rows(name)
+        if key in _TRACK_I32:
+            raise ValueError("%s holds integer rows: download() and rasters() take it, products over the members do not" % name)
+        if key == "period_mean":                   # the sum row with the number of updates as its divisor
+            return t.dev["sum"], t.n, t.stride, float(t.steps), t.channel
+        return t.dev[key], t.n, t.stride, 1.0, t.channel
+
+    def _source_rows(self, name):
+        """_product_rows of a member vector of the channel or the land part"""
         if name == "ChanQAvg":                     # Lisflood_dynamic.py:209, as chan_q_avg() divides
             return self.chan.vectors.dev["sumDisDay"], self.Nk, self.kstride, float(self.sc["NoRoutSteps"]), True
         if name in RT._STATE + RT._OUT:
@@ -1372,9 +1405,17 @@ class HotPathEnsemble(_HotPath):
     def rasters(self, names, dtype=np.float32, fill=output.FILL):
         """HotPathDevice.rasters for every member: up to 16 of the vectors summary() takes -- channel rows, "ChanQAvg" (the
         bits of chan_q_avg()), [N] member rows of the land part -- as [members, H, W] rasters each, straight from the rows as
-        the device holds them.  -> PendingRasters"""
+        the device holds them.  The accumulators of a tracker (track_begin) too: "<name>.peak" / ".sum" / ".period_mean" like
+        any fp64 row, "<name>.peak_step" as int32 [members, H, W], "<name>.first_above" / ".steps_above" as int32
+        [T, members, H, W] (the int32 fill outside the mask, 0 on land pixels outside the channel domain: the integer rows
+        are not tracked there).  -> PendingRasters"""
         groups = {"channel": [], "land": []}
         for name in names:
+            t, key = self._tracked(name)
+            if key in _TRACK_I32:
+                lead = (self.members,) if key == "peak_step" else (t.T, self.members)
+                groups["channel" if t.channel else "land"].append((name, t.dev[key], int(np.prod(lead)), t.stride, 1.0, lead))
+                continue
             src, _, stride, divisor, channel = self._product_rows(name)
             groups["channel" if channel else "land"].append((name, src, self.members, stride, divisor, True))
         return self._report_rasters(list(groups.items()), dtype, fill, side=not groups["land"])
@@ -1411,7 +1452,107 @@ class HotPathEnsemble(_HotPath):
         check(L.lf_gather_rows_device(dev, G, idx.ptr, src.ptr, stride, dst.ptr, G, M))
         rows = dst.download().reshape(M, G)
         rows[:, ~inside] = 0.0
-        return rows / self.sc["NoRoutSteps"] if name == "ChanQAvg" else rows
+        return rows / divisor if divisor != 1.0 else rows
+
+    # ---- products over the steps of a run: accumulators per member, updated on the device by every step -------------------
+    _TRACK_MAX = 4         # names tracked at once
+
+    def track_begin(self, name, thresholds=None):
+        """From now on every step() folds the member rows of `name` -- anything summary() takes: a channel row, "ChanQAvg",
+        an [N] member row of the land part -- into accumulators that stay on the device (lf_members_track_device, one call
+        per tracked name and step, no host synchronisation; a channel row behind the channel loop on its stream, a land row
+        on the main stream behind the overland step):
+            "<name>.peak"         the largest value of every member so far (np.maximum in step order: a NaN sticks, the
+                                  earlier step wins a tie), "<name>.peak_step" int32: the update it came with (0-based);
+            "<name>.sum"          the sum in step order, "<name>.period_mean": the sum / track_steps(name);
+            "<name>.first_above"  int32 [T, members, .]: the first update with value > threshold map t (-1: none yet),
+            "<name>.steps_above"  int32 [T, members, .]: how many updates had it above -- with thresholds= ([T, N] or [N] in
+                                  pixel order, T <= 4, uploaded here once).
+        The accumulators lie as their source does, same stride: the three fp64 names go wherever the source's name goes
+        (summary, summary_rasters, rasters, sample, download), so summary("ChanQAvg.peak", thresholds=...)["exceed"] is the
+        members that exceeded a map at any time of the horizon.  The int32 names go to download() and rasters().  On land
+        pixels outside the channel domain a channel row's fp64 accumulators read 0.0 like every channel row; the int32 ones
+        read 0: they are not tracked there.  Until the first update every derived name raises RuntimeError.  At most 4
+        names at once.  Trackers are not part of save_state() / load_state()."""
+        if name in self._trackers:
+            raise ValueError("%s is tracked already" % name)
+        if len(self._trackers) >= self._TRACK_MAX:
+            raise ValueError("at most %d names are tracked at once (%s)" % (self._TRACK_MAX, ", ".join(self._trackers)))
+        _, n, stride, _, channel = self._source_rows(name)
+        thr, T = None, 0
+        if thresholds is not None:
+            thr, T, _ = self._upload_thresholds(thresholds, channel)
+        M, dev = self.members, {}
+        for key, rows, dtype, gap in (("peak", M, np.float64, self._gap), ("sum", M, np.float64, self._gap),
+                                      ("peak_step", M, np.int32, TRACK_GAP_I32), ("first_above", T * M, np.int32, TRACK_GAP_I32),
+                                      ("steps_above", T * M, np.int32, TRACK_GAP_I32)):
+            if rows:                      # (what lies between the rows is set here and never touched again)
+                dev[key] = DeviceArray.from_host(np.full(rows * stride, gap, dtype), self.device)
+        self._trackers[name] = types.SimpleNamespace(name=name, n=n, stride=stride, channel=channel, thr=thr, T=T, dev=dev, steps=0)
+
+    def _tracker(self, name):
+        if name not in self._trackers:
+            raise ValueError("%s is not tracked (track_begin)" % name)
+        return self._trackers[name]
+
+    def _tracked(self, name):
+        """(tracker, key) of a derived name "<tracked name>.<key>", (None, None) of any other name"""
+        base, _, key = str(name).rpartition(".")
+        t = self._trackers.get(base)
+        if t is None or key not in _TRACK_F64 + _TRACK_I32:
+            return None, None
+        if key in ("first_above", "steps_above") and not t.T:
+            raise ValueError("%s is tracked without thresholds" % base)
+        if t.steps == 0:
+            raise RuntimeError("%s: no step() since track_begin / track_reset, the accumulators hold nothing yet" % name)
+        return t, key
+
+    def _track_update(self, channel):
+        """one lf_members_track_device per tracked channel row (or land row) on the stream the calls go to now"""
+        L, M = lib(), self.members
+        for t in self._trackers.values():
+            if t.channel is not channel:
+                continue
+            src, n, stride, divisor, _ = self._source_rows(t.name)
+            p = lambda k: t.dev[k].ptr if k in t.dev else None
+            check(L.lf_members_track_device(self.device, src.ptr, M, stride, n, divisor, t.steps, int(t.steps == 0), t.stride,
+                                            p("peak"), p("peak_step"), p("sum"), t.T, t.thr.ptr if t.T else None, n,
+                                            p("first_above"), p("steps_above")))
+            t.steps += 1
+
+    def track_steps(self, name):
+        """the updates of a tracker since track_begin() / track_reset(): the next one's step index"""
+        return self._tracker(name).steps
+
+    def track_reset(self, name):
+        """a new horizon: the next step() starts the accumulators over (it reads none of them) with step index 0.  Nothing
+        is enqueued; until that step the derived names raise RuntimeError."""
+        self._tracker(name).steps = 0
+
+    def track_end(self, name):
+        """stop tracking `name` and free its accumulators (waits for the step in flight)"""
+        t = self._tracker(name)
+        check(lib().lf_device_synchronize(self.device))
+        for d in list(t.dev.values()) + [t.thr]:
+            if d is not None:
+                d.free()
+        del self._trackers[name]
+
+    def _track_rows(self, t, key):
+        """(rows, what lies between them) of an accumulator as the device holds it: [members, .] or [T, members, .]"""
+        d = t.dev["sum" if key == "period_mean" else key]
+        lead = (t.T, self.members) if key in ("first_above", "steps_above") else (self.members,)
+        rows = d.download().reshape(lead + (t.stride,))
+        return rows[..., :t.n], rows[..., t.n:]
+
+    def track_gaps(self, name, key):
+        """gaps() of an accumulator (key: "peak", "sum", "peak_step", "first_above", "steps_above"): the elements between
+        its rows, which no call reads or writes -- in the fp64 rows the gap value at the time of track_begin() (set_gaps()
+        does not reach the trackers), TRACK_GAP_I32 in the int32 rows"""
+        t = self._tracker(name)
+        if key not in t.dev:
+            raise ValueError("%s has no accumulator %s" % (name, key))
+        return self._track_rows(t, key)[1]
 
     def state_names(self):
         return [k for k in self.STATE if k in self.land.dev or k in RT._STATE]
@@ -1508,6 +1649,8 @@ class HotPathEnsemble(_HotPath):
         self.land.free()
         products = [d for cache in (self._thresholds, self._gauges) for hit in cache.values() for d in hit
                     if isinstance(d, DeviceArray)] + list(self._products.values()) + [self._gpix_dev]
+        products += [d for t in self._trackers.values() for d in list(t.dev.values()) + [t.thr]]
         self._thresholds, self._gauges, self._products, self._gpix_dev, self._outside_held = {}, {}, {}, None, {}
+        self._trackers = {}
         self._free_shared([self._gidx, self._side, self._pidx] + list(self._qin.values()) +
                           list(self.force[1 - self._cur].values()) + [d for d in products if d is not None])
