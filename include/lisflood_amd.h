@@ -318,6 +318,34 @@ int lf_members_track_device(int device, const double *rows_dev, int members, int
                             double *peak_dev, int32_t *peak_step_dev, double *sum_dev,
                             int n_thresholds, const double *thresholds_dev, int64_t threshold_stride,
                             int32_t *first_above_dev, int32_t *steps_above_dev);
+/* The analysis step of an ensemble (EnKF / ETKF / smoother update, particle resampling), element by element and IN PLACE on
+ * `members` rows of n doubles, `stride` elements apart; elements between n and stride are neither read nor written.
+ * Asynchronous on the stream the library calls currently go to; no allocation, no synchronisation, no atomics, no scratch.
+ * lf_members_transform_device: with x[k] = rows_dev[k * stride + i] as it was BEFORE the call, for every output member m
+ *   t = x[0] * W[0][m];  for k = 1 .. members - 1:  t = t + x[k] * W[k][m]     (one multiply, one add, ascending k; never fused)
+ *   v = taper_dev ? x[m] + taper_dev[i] * (t - x[m]) : t
+ *   lo = lower_dev ? lower_dev[i] : lower;   v = (lo > v || (lo != lo && v == v)) ? lo : v
+ *   hi = upper_dev ? upper_dev[i] : upper;   v = (hi < v || (hi != hi && v == v)) ? hi : v
+ *   rows_dev[m * stride + i] = v
+ * W[k][m] = weights_dev[k * members + m], one [members][members] table in device memory for the whole domain; taper_dev,
+ * lower_dev and upper_dev are [n] rows shared by the members, or NULL (no taper; the scalar bound).  A scalar bound of
+ * -inf / +inf leaves every bit of v (-0.0 and NaN included); a NaN bound makes every non-NaN v a NaN.  The identity matrix
+ * is NOT a bit-exact no-op: a -0.0 comes back as +0.0 unless every other member of its column has its sign bit set (the
+ * other members' products are zeros of their own sign), and a column with an inf or a NaN becomes NaN in every other member
+ * (0 * inf) -- with one member nothing is added and every bit stays.  A selection matrix is therefore no substitute for
+ * lf_members_resample_device.  Up to 64 members (the table is 32 KiB, read through the scalar cache).  A lane owns its
+ * element's whole column, which sits in LDS before the first store; 256 lanes per workgroup up to 32 members, 128 up to 64.
+ * lf_members_resample_device: rows_dev[m * stride + i] = x[parents_host[m]], a copy of the bits.  parents_host: int32
+ * [members] on the host, read before the call returns.  A row with parents_host[m] == m is not written, and read only where
+ * another row draws from it; with the identity nothing is launched.  Up to 128 members.
+ * LF_E_INVALID, with the argument named, before a device is touched: rows_dev, weights_dev or parents_host NULL,
+ * members < 1 or above the call's limit, n < 0 or beyond the 32-bit range of a launch, stride < n with members > 1, a parent
+ * outside 0 .. members - 1, lower > upper where both are scalars.  n == 0: LF_OK, nothing is launched. */
+int lf_members_transform_device(int device, double *rows_dev, int members, int64_t stride, int64_t n,
+                                const double *weights_dev, const double *taper_dev,
+                                const double *lower_dev, double lower, const double *upper_dev, double upper);
+int lf_members_resample_device(int device, double *rows_dev, int members, int64_t stride, int64_t n,
+                               const int32_t *parents_host);
 /* Report maps in the form a map writer takes (lf_report.hip): for up to 16 sources in ONE launch, source k < nmaps,
  * row r < rows_host[k] and cell < cells = H * W,  dst_dev[k][r * cells + cell] =
  *     idx_dev[cell] >= 0 : convert(src_dev[k][r * stride_host[k] + idx_dev[cell]] / divisor_host[k])

@@ -6,6 +6,9 @@
 //   k_members_order   : order statistics (the value with exactly r values before it in the stable order), column in LDS
 //   k_members_track   : one step folded into run-long accumulators per member -- peak and its step, sum, first step above
 //                       and steps above up to four threshold maps -- rows laid out like their source
+//   k_members_transform / k_members_resample : the analysis step of an assimilation cycle, the only kernels here that WRITE
+//                       the member rows -- x_new[m] = sum_k x[k] W[k][m] with taper and bounds, x_new[m] = x[parents[m]];
+//                       in place, the element's column in LDS before the first store (their own section below)
 //
 // The value of (m, i) is rows[m * stride + i] / divisor, an IEEE division (divisor 1: the element itself), the result of
 // element i goes to dst_index ? dst_index[i] : i.  Everything is in member order: the sum is ((x0 + x1) + x2) + ..., the
@@ -211,6 +214,142 @@ __global__ void __launch_bounds__(W) k_members_order(members_rows R, order_out O
     }
 }
 
+// ---- the analysis step of an ensemble: the members' rows rewritten in place, element by element --------------------------------
+constexpr int kMaxTransformMembers = 64;  // the weight table: 64 x 64 doubles = 32 KiB, read through the scalar cache
+constexpr int kMaxResampleMembers = 128;
+constexpr int kBlock = 8;                 // output members per register block: 8 accumulators with compile-time indices
+constexpr int kStage = 16;                // rows in flight per lane while the column goes to LDS
+
+struct transform_args {
+    long long stride, n;
+    int members;
+    double lower, upper;
+};
+
+struct resample_plan {
+    int n_src, n_dst;
+    unsigned char src[kMaxResampleMembers];  // the rows some OTHER row draws from, each once: slot s of the tile holds row src[s]
+    unsigned char dst[kMaxResampleMembers];  // the rows with parents[m] != m ...
+    unsigned char slot[kMaxResampleMembers]; // ... and the slot their parent sits in
+};
+
+// One register block of the transform: output members m0 .. m0 + kBlock - 1 of the lane's column (in LDS, complete) -- the
+// sum in ascending k with one multiply and one add each, then taper and bounds, then the store.  The weight addresses are
+// uniform across the lanes (k, m0 and M come from kernel arguments): scalar loads.  FULL: the block lies inside the table;
+// otherwise the columns past M - 1 read column M - 1 again and store nothing.
+template <int W, bool FULL>
+__device__ __forceinline__ void transform_block(const double *tile, int lane, double *__restrict__ out, const double *__restrict__ w,
+                                                int M, int m0, long long stride, bool tapered, double tp, double lo, double hi)
+{
+    int col[kBlock];
+#pragma unroll
+    for (int j = 0; j < kBlock; ++j) col[j] = FULL ? m0 + j : (m0 + j < M ? m0 + j : M - 1);
+    double acc[kBlock];
+    const double x0 = tile[lane];
+#pragma unroll
+    for (int j = 0; j < kBlock; ++j) acc[j] = x0 * w[col[j]];
+#pragma unroll 4                        // (the weights and column values of four k in flight ahead of their 64 operations)
+    for (int k = 1; k < M; ++k) {
+        const double xk = tile[k * W + lane];
+        const double *wk = w + k * M;
+#pragma unroll
+        for (int j = 0; j < kBlock; ++j) acc[j] = acc[j] + xk * wk[col[j]];
+    }
+#pragma unroll
+    for (int j = 0; j < kBlock; ++j) {
+        if (!FULL && m0 + j >= M) break;
+        double v = acc[j];
+        if (tapered) {
+            const double xm = tile[(m0 + j) * W + lane];
+            v = xm + tp * (v - xm);
+        }
+        v = (lo > v || (lo != lo && v == v)) ? lo : v;
+        v = (hi < v || (hi != hi && v == v)) ? hi : v;
+        out[(long long)(m0 + j) * stride] = v;
+    }
+}
+
+// x_new[m] = sum_k x[k] W[k][m] in place (lf_members_transform_device).  A lane owns element i of every member: the column
+// goes to LDS as tile[k * W + lane] (k_members_order's layout: no barrier, consecutive lanes on consecutive banks) before
+// the first store, and no row is read from global again.  The element's taper and bound values are read once.
+template <int W>
+__global__ void __launch_bounds__(W)
+k_members_transform(double *__restrict__ rows, const double *__restrict__ weights, const double *__restrict__ taper,
+                    const double *__restrict__ lower_dev, const double *__restrict__ upper_dev, transform_args A)
+{
+    extern __shared__ double tile[];
+    const int lane = threadIdx.x;
+    const long long i = (long long)blockIdx.x * W + lane;
+    if (i >= A.n) return;
+    double *p = rows + i;
+    const int M = A.members;
+    int k = 0;
+    for (; k + kStage <= M; k += kStage) {
+        double raw[kStage];
+#pragma unroll
+        for (int u = 0; u < kStage; ++u) raw[u] = row_load(p + (long long)(k + u) * A.stride);
+#pragma unroll
+        for (int u = 0; u < kStage; ++u) tile[(k + u) * W + lane] = raw[u];
+    }
+    for (; k < M; ++k) tile[k * W + lane] = row_load(p + (long long)k * A.stride);
+    const bool tapered = taper != nullptr;
+    const double tp = tapered ? taper[i] : 1.0;
+    const double lo = lower_dev ? lower_dev[i] : A.lower;
+    const double hi = upper_dev ? upper_dev[i] : A.upper;
+    int m0 = 0;
+    for (; m0 + kBlock <= M; m0 += kBlock) transform_block<W, true>(tile, lane, p, weights, M, m0, A.stride, tapered, tp, lo, hi);
+    if (m0 < M) transform_block<W, false>(tile, lane, p, weights, M, m0, A.stride, tapered, tp, lo, hi);
+}
+
+// x_new[m] = x[parents[m]] in place (lf_members_resample_device): the rows another row draws from go to LDS, each once, then
+// the rows that change are stored.  A row that keeps itself is not stored, and loaded only where another row draws from it.
+template <int W>
+__global__ void __launch_bounds__(W) k_members_resample(double *__restrict__ rows, long long stride, long long n, resample_plan P)
+{
+    extern __shared__ double tile[];
+    const int lane = threadIdx.x;
+    const long long i = (long long)blockIdx.x * W + lane;
+    if (i >= n) return;
+    double *p = rows + i;
+    int s = 0;
+    for (; s + kUnroll <= P.n_src; s += kUnroll) {
+        double raw[kUnroll];
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u) raw[u] = row_load(p + (long long)P.src[s + u] * stride);
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u) tile[(s + u) * W + lane] = raw[u];
+    }
+    for (; s < P.n_src; ++s) tile[s * W + lane] = row_load(p + (long long)P.src[s] * stride);
+    for (int d = 0; d < P.n_dst; ++d) p[(long long)P.dst[d] * stride] = tile[P.slot[d] * W + lane];
+}
+
+// what the two in-place calls refuse in common
+int check_inplace_rows(const double *rows_dev, int members, int cap, const char *what, int64_t stride, int64_t n)
+{
+    if (!rows_dev) return lf_set_error(LF_E_INVALID, "rows_dev is NULL");
+    if (members < 1) return lf_set_error(LF_E_INVALID, "members must be at least 1 (got %d)", members);
+    if (members > cap) return lf_set_error(LF_E_INVALID, "members = %d: %s takes at most %d members", members, what, cap);
+    if (n < 0 || n > 0x7fffffffll) return lf_set_error(LF_E_INVALID, "n = %lld outside the 32-bit range of a launch", (long long)n);
+    if (members > 1 && stride < n) return lf_set_error(LF_E_INVALID, "stride %lld is less than n = %lld", (long long)stride, (long long)n);
+    return LF_OK;
+}
+
+template <int W>
+void launch_transform(hipStream_t s, double *rows, const double *weights, const double *taper, const double *lower_dev,
+                      const double *upper_dev, const transform_args &A)
+{
+    const dim3 grid((unsigned)((A.n + W - 1) / W)), block(W);
+    hipLaunchKernelGGL((k_members_transform<W>), grid, block, (size_t)A.members * W * sizeof(double), s, rows, weights, taper,
+                       lower_dev, upper_dev, A);
+}
+
+template <int W>
+void launch_resample(hipStream_t s, double *rows, long long stride, long long n, const resample_plan &P)
+{
+    const dim3 grid((unsigned)((n + W - 1) / W)), block(W);
+    hipLaunchKernelGGL((k_members_resample<W>), grid, block, (size_t)P.n_src * W * sizeof(double), s, rows, stride, n, P);
+}
+
 // what both entry points refuse, in the order the header lists it (no device is touched)
 int check_rows(const double *rows_dev, int members, int64_t stride, int64_t n, const int32_t *dst_index_dev, int64_t dst_n)
 {
@@ -358,6 +497,58 @@ int lf_members_order_statistics_device(int device, const double *rows_dev, int m
         launch_order<128>(c->stream, R, O);
     else
         launch_order<64>(c->stream, R, O);
+    LF_HIP(hipGetLastError());
+    return LF_OK;
+}
+
+int lf_members_transform_device(int device, double *rows_dev, int members, int64_t stride, int64_t n, const double *weights_dev,
+                                const double *taper_dev, const double *lower_dev, double lower, const double *upper_dev, double upper)
+{
+    LF_TRY(check_inplace_rows(rows_dev, members, kMaxTransformMembers, "the transform (a 32 KiB weight table)", stride, n));
+    if (!weights_dev) return lf_set_error(LF_E_INVALID, "weights_dev is NULL");
+    if (!lower_dev && !upper_dev && lower > upper)
+        return lf_set_error(LF_E_INVALID, "lower = %g is greater than upper = %g", lower, upper);
+    if (n == 0) return LF_OK;
+    lf_device_ctx *c;
+    LF_TRY(lf_ctx(device, &c));
+    const transform_args A = {(long long)stride, (long long)n, members, lower, upper};
+    // the widest workgroup whose [members][W] tile fits: 256 lanes up to 32 members, 128 up to 64
+    if ((size_t)members * 256 * sizeof(double) <= kOrderTileBytes)
+        launch_transform<256>(c->stream, rows_dev, weights_dev, taper_dev, lower_dev, upper_dev, A);
+    else
+        launch_transform<128>(c->stream, rows_dev, weights_dev, taper_dev, lower_dev, upper_dev, A);
+    LF_HIP(hipGetLastError());
+    return LF_OK;
+}
+
+int lf_members_resample_device(int device, double *rows_dev, int members, int64_t stride, int64_t n, const int32_t *parents_host)
+{
+    LF_TRY(check_inplace_rows(rows_dev, members, kMaxResampleMembers, "resampling", stride, n));
+    if (!parents_host) return lf_set_error(LF_E_INVALID, "parents_host is NULL");
+    resample_plan P = {};
+    int slot_of[kMaxResampleMembers];
+    for (int m = 0; m < members; ++m) slot_of[m] = -1;
+    for (int m = 0; m < members; ++m) {
+        const int parent = parents_host[m];
+        if (parent < 0 || parent >= members)
+            return lf_set_error(LF_E_INVALID, "parent %d (parents_host[%d]) outside 0 .. members - 1 = %d", parent, m, members - 1);
+        if (parent == m) continue;
+        if (slot_of[parent] < 0) {
+            slot_of[parent] = P.n_src;
+            P.src[P.n_src++] = (unsigned char)parent;
+        }
+        P.dst[P.n_dst] = (unsigned char)m;
+        P.slot[P.n_dst++] = (unsigned char)slot_of[parent];
+    }
+    if (n == 0 || P.n_dst == 0) return LF_OK;      // (the identity: nothing is launched)
+    lf_device_ctx *c;
+    LF_TRY(lf_ctx(device, &c));
+    if ((size_t)P.n_src * 256 * sizeof(double) <= kOrderTileBytes)
+        launch_resample<256>(c->stream, rows_dev, (long long)stride, (long long)n, P);
+    else if ((size_t)P.n_src * 128 * sizeof(double) <= kOrderTileBytes)
+        launch_resample<128>(c->stream, rows_dev, (long long)stride, (long long)n, P);
+    else
+        launch_resample<64>(c->stream, rows_dev, (long long)stride, (long long)n, P);
     LF_HIP(hipGetLastError());
     return LF_OK;
 }

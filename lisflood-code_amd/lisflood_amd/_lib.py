@@ -37,6 +37,8 @@ _SIGNATURES = {
     "ipiqqdpqipp": "members_order_statistics_device",
     "ipiqqdiiqpppipqpp": "members_track_device",
     "ipiqqdpqpppipqp": "members_summary_device",
+    "ipiqqp": "members_resample_device",
+    "ipiqqpppdpd": "members_transform_device",
     "ipiqqq": "pixel_aggregates_members_device",
     "ipiz": "memset",
     "ippii": "lddrepair_raster_device",

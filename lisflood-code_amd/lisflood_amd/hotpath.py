@@ -958,6 +958,13 @@ class HotPathEnsemble(_HotPath):
     threshold maps, the period mean -- are folded on the device step by step: track_begin(name, thresholds) and from then
     on one lf_members_track_device per step(); the accumulators lie like their source and go through summary() / rasters() /
     sample() / download() as "<name>.peak" and so on.  They are not part of save_state() / load_state().
+    The analysis step of an assimilation cycle -- step, sample() the gauges, update every member's state, step -- rewrites
+    the state where it lies: transform(weights, taper=, bounds=) applies one [members, members] matrix to every state vector
+    element by element (the update of every ensemble Kalman variant; lf_members_transform_device), resample(parents) makes
+    member m a copy of member parents[m] (a particle filter's resampling; lf_members_resample_device).  Only the matrix or
+    the parents cross PCIe (assimilation.enkf_weights / systematic_parents make them from sample()).  Both rewrite the
+    particle -- state_names() and, with structures=, the site state and TransCum -- and leave what belongs to the member's
+    slot: forcing sets, inflow-hydrograph rows, trackers, optional diagnostic maps.
     Not in this class (HotPathDevice has them): step_profile, state_maps / load_state_maps and mass_balance."""
 
     def __init__(self, values, scalars, land_mask, ldd_to_chan, ldd_kinematic, members, split=True, device=0, structures=None,
@@ -1045,6 +1052,9 @@ class HotPathEnsemble(_HotPath):
         self._outside_held = {}
         # track_begin(): tracked name -> its accumulators on the device and the number of updates so far
         self._trackers = {}
+        # transform(): the weight table on the device ([array object it holds, device table], made on first use), the taper /
+        # bound rows on the device by the array object they were made from, and the keys the call in hand uses
+        self._weights, self._analysis_cache, self._analysis_pinned = None, {}, set()
 
     def _lai_vectors(self):
         return self.land.dev
@@ -1580,6 +1590,163 @@ class HotPathEnsemble(_HotPath):
         host[:, :width] = rows
         d.upload(np.ascontiguousarray(host.reshape(-1)[:d.nbytes // 8]), prefix=False)
 
+    # ---- the analysis step: every member's state rewritten on the device from the members' rows as they lie --------------------
+    _ROWS_CACHED = 64      # taper / bound rows kept on the device (per array object and row order; the oldest goes first)
+
+    def analysis_names(self):
+        """what transform() and resample() rewrite by default: every vector of state_names() and, with structures=, the lake
+        and reservoir state rows and TransCum that save_state() writes"""
+        names = self.state_names()
+        if self.rmod is not None:
+            names += [k for k in RT._LAKE_STATE + RT._RES_STATE + ["TransCum"] if k in self.chan._groups]
+        return names
+
+    def _analysis_names(self, names):
+        known = self.analysis_names()
+        if names is None:
+            return known
+        names = [names] if isinstance(names, str) else list(names)
+        for k in names:
+            if k not in known:
+                raise ValueError("%s is no state vector of this object (analysis_names(): %s)" % (k, ", ".join(known)))
+        if len(set(names)) != len(names):
+            raise ValueError("names holds a vector twice: it would be rewritten twice")
+        return names
+
+    def _analysis_rows(self, name):
+        """the row sets of a state vector -> [(address of member 0's row, entries, stride, row order, row of a [3, N] vector)]:
+        a [3, N] member vector is three sets on the offsets v N, a site vector's rows lie back to back"""
+        E = self.land
+        if name in E.dev and name not in RT._STATE:
+            base = E.dev[name].ptr.value
+            if name in E._member:
+                return [(base + 8 * v * self.N, self.N, self.stride, "land", v) for v in range(E.V)]
+            return [(base, self.N, self.pstride, "land", None)]
+        d, width, stride = self._channel_rows(name)
+        order = "lake" if name in RT._LAKE_STATE else "res" if name in RT._RES_STATE else "channel"
+        return [(d.ptr.value, width, stride, order, None)]
+
+    def _pixel_rows(self, a, order, v=None):
+        """The device row of a per-pixel host array ([N] in pixel order, or row v of a [3, N] one) in the order of a row set:
+        "land" sweep order, "channel" engine order, "lake" / "res" the site's pixel.  Gathered and uploaded once per array
+        object and order: pass the SAME array every cycle (a changed copy of it is a new array).  The rows a transform() call
+        has resolved are pinned (_analysis_pinned) until its kernels are enqueued: what makes room for a new row is the row
+        used longest ago that the call in hand does NOT use, and where it uses them all the cache grows instead."""
+        key = (id(a), order, v)
+        self._analysis_pinned.add(key)
+        hit = self._analysis_cache.pop(key, None)                   # (the entry holds its array, so the id is the array's own)
+        if hit is not None:
+            self._analysis_cache[key] = hit                         # (used last: to the back of the queue)
+        else:
+            if order in ("lake", "res"):
+                var = self.rmod.var
+                index = self.ids[np.asarray(var.LakeIndex if order == "lake" else var.ReservoirIndex, np.int64)]
+            else:
+                index = self.pixel_of_position if order == "land" else self.gpix
+            host = np.asarray(a, np.float64)
+            host = host if host.ndim == 1 else host[v]
+            while len(self._analysis_cache) >= self._ROWS_CACHED:
+                old = next((k for k in self._analysis_cache if k not in self._analysis_pinned), None)
+                if old is None:
+                    break
+                check(lib().lf_device_synchronize(self.device))     # (a kernel of an earlier call may still read it)
+                self._analysis_cache.pop(old)[1].free()
+            hit = self._analysis_cache[key] = (a, DeviceArray.from_host(np.ascontiguousarray(host[index]), self.device))
+        return hit[1]
+
+    def _analysis_bounds(self, names, bounds):
+        """bounds of transform() checked -> name -> (lower, upper), each None, a float or an array"""
+        out = {}
+        for name, pair in (bounds or {}).items():
+            if name not in names:
+                raise ValueError("bounds for %s, which is not among the names of this call" % name)
+            if not isinstance(pair, (tuple, list)) or len(pair) != 2:
+                raise ValueError("bounds[%s] must be (lower, upper)" % name)
+            shapes = [(self.N,)] + ([(self.land.V, self.N)] if name in self.land._member else [])
+            checked = []
+            for b in pair:
+                if b is not None and np.ndim(b) == 0:
+                    b = float(b)
+                elif b is not None and np.shape(b) not in shapes:
+                    raise ValueError("a bound of %s must be None, a scalar or an array of shape %s"
+                                     % (name, " or ".join(str(list(s)) for s in shapes)))
+                checked.append(b)
+            if isinstance(checked[0], float) and isinstance(checked[1], float) and checked[0] > checked[1]:
+                raise ValueError("bounds[%s]: lower %g is greater than upper %g" % ((name,) + tuple(checked)))
+            out[name] = tuple(checked)
+        return out
+
+    def transform(self, weights, names=None, taper=None, bounds=None):
+        """The update of an ensemble Kalman analysis (stochastic EnKF, ETKF, an ensemble smoother) on the device: for every
+        element i of every state vector, x_new[m, i] = sum_k x[k, i] weights[k][m], summed in ascending k with one multiply
+        and one add each, in place on the member rows as they lie (lf_members_transform_device: one call per row set, a
+        [3, N] vector three).  Only `weights` -- [members, members] float64, e.g. assimilation.enkf_weights() of sample() at
+        the gauges -- crosses PCIe: into one resident table, asynchronously, whenever the array object is not the one of the
+        call before (a changed copy of it is a new array); at most 64 members.
+        names: the vectors to rewrite, by default analysis_names().  NOT touched, whatever the names: the forcing sets, the
+        inflow-hydrograph rows (QInM3Old, QDelta and the host's copy of the last inflow), the trackers' accumulators, the
+        optional diagnostic maps and every output of a step -- each belongs to the member's slot, not to the particle.
+        taper: None or [N] in pixel order, the localisation: x_new = x + taper * (x_new - x) element by element (a site
+        row takes the taper at the site's pixel).
+        bounds: name -> (lower, upper), applied after the taper; each None, a scalar or an array in pixel order -- [N], or
+        [3, N] for a [3, N] vector -- and v = lower where lower > v or lower is a NaN, then the same with upper from above.
+        Arrays go to the device once per object, like thresholds.  Names without an entry are unbounded.
+        Joins the side stream (runs behind the channel loop of the last step) and enqueues: no host synchronisation, the
+        next step() sees the new state; steps_done stays."""
+        M, N = self.members, self.N
+        if M > 64:
+            raise ValueError("transform() takes at most 64 members (%d)" % M)
+        if not (isinstance(weights, np.ndarray) and weights.dtype == np.float64 and weights.shape == (M, M)):
+            raise ValueError("weights must be a float64 array of shape [%d, %d]" % (M, M))
+        if taper is not None and np.shape(taper) != (N,):
+            raise ValueError("taper must be [%d] in pixel order" % N)
+        names = self._analysis_names(names)
+        bounds = self._analysis_bounds(names, bounds)
+        calls = []
+        self._analysis_pinned = set()             # the rows this call uses stay until its kernels are enqueued (_pixel_rows)
+        try:
+            for name in names:
+                lower, upper = bounds.get(name, (None, None))
+                for base, n, stride, order, v in self._analysis_rows(name):
+                    arg = lambda b, inf: (None, inf) if b is None else (None, b) if isinstance(b, float) \
+                        else (self._pixel_rows(b, order, v).ptr, 0.0)
+                    if n:
+                        calls.append((base, stride, n, None if taper is None else self._pixel_rows(taper, order).ptr)
+                                     + arg(lower, -np.inf) + arg(upper, np.inf))
+            L, dev = lib(), self.device
+            check(L.lf_side_stream_join(dev))
+            # ONE weight table on the device.  A new array object (enkf_weights() returns one every cycle) goes into it through
+            # a page-locked staging slot, in order on the main stream behind the kernels of the call before: nothing is
+            # allocated or freed from cycle to cycle, so nothing synchronises.  The same object again: no upload.
+            if self._weights is None:
+                self._weights = [None, DeviceArray(M * M, np.float64, dev)]
+            if self._weights[0] is not weights:
+                self._weights[1].upload(np.ascontiguousarray(weights).reshape(-1), staged=True)
+                self._weights[0] = weights
+            w = self._weights[1]
+            for base, stride, n, tp, lo_dev, lo, hi_dev, hi in calls:
+                check(L.lf_members_transform_device(dev, base, M, stride, n, w.ptr, tp, lo_dev, lo, hi_dev, hi))
+        finally:
+            self._analysis_pinned = set()
+
+    def resample(self, parents, names=None):
+        """The resampling step of a particle filter on the device: member m becomes a copy, bit for bit, of member
+        parents[m] in every state vector (lf_members_resample_device; names and what stays untouched: as transform()).
+        parents: [members] integers 0 .. members - 1, e.g. assimilation.systematic_parents(); a member that keeps itself is
+        not written, with the identity nothing is launched.  At most 128 members.  Ordered like transform()."""
+        M = self.members
+        p = np.asarray(parents)
+        if p.shape != (M,) or p.dtype.kind not in "iu" or p.min() < 0 or p.max() >= M:
+            raise ValueError("parents must be [%d] integers from 0 to members - 1 = %d" % (M, M - 1))
+        if M > 128:
+            raise ValueError("resample() takes at most 128 members (%d)" % M)
+        p = np.ascontiguousarray(p, np.int32)
+        calls = [row for name in self._analysis_names(names) for row in self._analysis_rows(name) if row[1]]
+        L, dev = lib(), self.device
+        check(L.lf_side_stream_join(dev))
+        for base, n, stride, _, _ in calls:
+            check(L.lf_members_resample_device(dev, base, M, stride, n, p.ctypes.data_as(C.c_void_p)))
+
     def gaps(self, name, buffer_set=None):
         """[members, pad]: the elements between the members' rows of a member vector, which no call reads or writes (the
         last member's gap of a channel vector may lie beyond the vector: NaN here).  A forcing vector: of the set in use,
@@ -1647,10 +1814,11 @@ class HotPathEnsemble(_HotPath):
         check(lib().lf_device_synchronize(self.device))
         self.chan.free()
         self.land.free()
-        products = [d for cache in (self._thresholds, self._gauges) for hit in cache.values() for d in hit
-                    if isinstance(d, DeviceArray)] + list(self._products.values()) + [self._gpix_dev]
+        products = [d for cache in (self._thresholds, self._gauges, self._analysis_cache) for hit in cache.values()
+                    for d in hit if isinstance(d, DeviceArray)] + list(self._products.values()) + [self._gpix_dev]
+        products += [self._weights[1]] if self._weights else []
         products += [d for t in self._trackers.values() for d in list(t.dev.values()) + [t.thr]]
         self._thresholds, self._gauges, self._products, self._gpix_dev, self._outside_held = {}, {}, {}, None, {}
-        self._trackers = {}
+        self._trackers, self._weights, self._analysis_cache = {}, None, {}
         self._free_shared([self._gidx, self._side, self._pidx] + list(self._qin.values()) +
                           list(self.force[1 - self._cur].values()) + [d for d in products if d is not None])
