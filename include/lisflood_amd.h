@@ -346,6 +346,48 @@ int lf_members_transform_device(int device, double *rows_dev, int members, int64
                                 const double *lower_dev, double lower, const double *upper_dev, double upper);
 int lf_members_resample_device(int device, double *rows_dev, int members, int64_t stride, int64_t n,
                                const int32_t *parents_host);
+/* The forecast half of the cycle: what makes the members differ.  Member rows (forcing, or state as model error / jitter)
+ * perturbed from `rank` static spatial patterns on the device and a [members][rank] table of coefficients from the host --
+ * only the table crosses PCIe.  For every element i < n and member m < members
+ *   s = c[m][0] * P[0][i];   for r = 1 .. rank-1:  s = s + c[m][r] * P[r][i]      (one multiply, one add, ascending r; never fused)
+ *   b = base_dev ? base_dev[i] : rows_dev[m*stride + i]                          (as it was BEFORE the call)
+ *   v = multiplicative ? b * (1.0 + s) : b + s
+ *   lo = lower_dev ? lower_dev[i] : lower;   v = (lo > v || (lo != lo && v == v)) ? lo : v
+ *   hi = upper_dev ? upper_dev[i] : upper;   v = (hi < v || (hi != hi && v == v)) ? hi : v
+ *   rows_dev[m*stride + i] = v
+ * P[r][i] = patterns_dev[r*pattern_stride + i] (device); c[m][r] = coeff_host[m*rank + r], HOST memory, read before the call
+ * returns (the source is free again on return, like parents_host): the table goes up through a page-locked slot of the
+ * library (as lf_memcpy_h2d_staged does) into one of four tables kept on the device, on the call's own stream.  lower_dev /
+ * upper_dev: [n] rows shared by the members, or NULL (the scalar bound); the bound lines are lf_members_transform_device's.
+ * Elements n .. stride-1 of a row are neither read nor written.  base_dev: one [n] row for every member, or NULL (every
+ * member's own row, in place).  base_dev may be rows_dev itself -- member 0's row, which is how a forcing vector that went up
+ * as one row is spread over the members: a lane owns element i of every member and has read b before its first store, so
+ * the in-place form is safe.  Consequences: all-zero coefficients under `multiplicative` leave every non-NaN bit of b, -0.0
+ * included (s = +0.0, 1.0 + s = 1.0, b * 1.0 = b), before the bounds; in additive mode -0.0 + (+0.0) is +0.0, so zero
+ * coefficients are no bit-exact no-op there; 0 * inf in a pattern gives NaN (a zero coefficient does not switch an infinite
+ * pattern value off).  Up to 128 members, rank up to 16 (the table: 16 KiB, read through the scalar cache).
+ * lf_members_perturb_device is asynchronous on the stream the library calls currently go to (main, side or lane).
+ * lf_upload_perturb_rows runs on the copy stream and is legal only between lf_upload_begin(set) and lf_upload_end(set), where
+ * it runs behind the lf_upload_rows of the same destination.  Neither allocates per call (the four tables are made on first
+ * use), neither synchronises the host; no atomics, no LDS, no scratch.  Traffic per element: 8 (rank + 1 + members) bytes with
+ * a base row, 8 (rank + 2 members) in place, plus 8 per bound row; 2 rank + 2 unfused fp64 operations per store.  Measured
+ * (MI355X, 4e6 elements, rank 8, 4 / 16 / 51 members; profiles/members_perturb.json): 0.077 / 0.159 /
+ * 0.323 ms from one base row and 0.097 / 0.249 / 0.600 ms in place, 0.80 - 0.94 of the 6.29 TB/s copy ceiling; a prefetched
+ * ensemble step with two forcing vectors spread this way takes what it takes on [n] forcing alone, within its spread.
+ * LF_E_INVALID, with the argument named, before a device is touched: rows_dev, patterns_dev or coeff_host NULL, members < 1
+ * or > 128, rank < 1 or > 16, n < 0 or beyond the 32-bit range of a launch, stride < n with members > 1, pattern_stride < n with
+ * rank > 1, multiplicative not 0 or 1, lower > upper where both are scalars.  lf_upload_perturb_rows outside an open upload
+ * section: LF_E_INVALID.  n == 0: LF_OK, nothing is launched. */
+int lf_members_perturb_device(int device, double *rows_dev, int members, int64_t stride, int64_t n,
+                              const double *base_dev,
+                              int rank, const double *patterns_dev, int64_t pattern_stride,
+                              const double *coeff_host, int multiplicative,
+                              const double *lower_dev, double lower, const double *upper_dev, double upper);
+int lf_upload_perturb_rows(int device, double *rows_dev, int members, int64_t stride, int64_t n,
+                           const double *base_dev,
+                           int rank, const double *patterns_dev, int64_t pattern_stride,
+                           const double *coeff_host, int multiplicative,
+                           const double *lower_dev, double lower, const double *upper_dev, double upper);
 /* Report maps in the form a map writer takes (lf_report.hip): for up to 16 sources in ONE launch, source k < nmaps,
  * row r < rows_host[k] and cell < cells = H * W,  dst_dev[k][r * cells + cell] =
  *     idx_dev[cell] >= 0 : convert(src_dev[k][r * stride_host[k] + idx_dev[cell]] / divisor_host[k])

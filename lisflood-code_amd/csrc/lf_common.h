@@ -71,6 +71,17 @@ struct lf_device_ctx {
     };
     staged_slot staged[8];
     int staged_next = 0;
+    int upload_open = -1; // the set between lf_upload_begin and lf_upload_end, -1: none (lf_upload_perturb_rows asks)
+    // coefficient tables of lf_members_perturb_device / lf_upload_perturb_rows on the device: a ring of kPerturbSlots
+    // tables of 128 x 16 doubles in one allocation made on first use (lf_device_trim frees it).  A table is filled through
+    // the page-locked ring above on the call's stream; the event behind the call's kernel lets the next user of the
+    // slot -- possibly on another stream -- wait for it on the device, never on the host
+    static constexpr int kPerturbSlots = 4;
+    static constexpr size_t kPerturbTableBytes = 128 * 16 * sizeof(double);
+    void *perturb_tables = nullptr;
+    hipEvent_t perturb_read[kPerturbSlots] = {nullptr, nullptr, nullptr, nullptr};
+    bool perturb_read_valid[kPerturbSlots] = {false, false, false, false};
+    int perturb_next = 0;
     // side stream (lf_side_stream_*): a part of a step that the NEXT step's first kernels do not depend on -- the channel
     // wavefront of a model step beside the canopy / soil / overland kernels of the step after it (hotpath.py)
     hipStream_t side_stream = nullptr, main_stream = nullptr;
@@ -86,6 +97,9 @@ struct lf_device_ctx {
     bool lane_forked = false;
 };
 int lf_ctx(int device, lf_device_ctx **out); // makes `device` current, creates the context on first use
+// lf_memcpy_h2d_staged on a stream of the caller's choice: `bytes` of host memory through a page-locked slot of the context's
+// ring (the source is free again on return) to dst_dev by DMA on `s`; the slot's event is recorded on `s`
+int lf_staged_h2d(lf_device_ctx *c, hipStream_t s, void *dst_dev, const void *src_host, size_t bytes);
 
 // Host-side graph.  Positions ("sweep order") are the engine's internal cell numbering: levels
 // ascending (level = max distance to outlet - distance, as kinematic_wave_parallel.py:148-149),

@@ -50,6 +50,30 @@ int lf_ctx(int device, lf_device_ctx **out)
     return LF_OK;
 }
 
+// A small upload that does not stall the host: the bytes go to a page-locked slot of a ring owned by the context (host
+// memcpy, the source is free again on return) and from there by DMA on `s`, in order with the kernels around it.  A slot is
+// reused only after its copy has finished (event per slot, recorded on the stream the copy went to).
+int lf_staged_h2d(lf_device_ctx *c, hipStream_t s, void *dst_dev, const void *src_host, size_t bytes)
+{
+    lf_device_ctx::staged_slot &sl = c->staged[c->staged_next];
+    c->staged_next = (c->staged_next + 1) % 8;
+    if (sl.in_flight) LF_HIP(hipEventSynchronize(sl.done));
+    sl.in_flight = false;
+    if (sl.cap < bytes) {
+        if (sl.host) (void)hipHostFree(sl.host);
+        sl.host = nullptr;
+        sl.cap = 0;
+        LF_HIP(hipHostMalloc(&sl.host, bytes, hipHostMallocDefault));
+        sl.cap = bytes;
+    }
+    if (!sl.done) LF_HIP(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
+    std::memcpy(sl.host, src_host, bytes);
+    LF_HIP(hipMemcpyAsync(dst_dev, sl.host, bytes, hipMemcpyHostToDevice, s));
+    LF_HIP(hipEventRecord(sl.done, s));
+    sl.in_flight = true;
+    return LF_OK;
+}
+
 extern "C" {
 
 const char *lf_last_error(void) { return g_err; }
@@ -164,34 +188,16 @@ int lf_memcpy_h2d(int device, void *dst_dev, const void *src_host, size_t bytes)
     return LF_OK;
 }
 
-// A small upload that does not stall the host: the bytes go to a page-locked slot of a ring owned by the context (host
-// memcpy, the source is free again on return) and from there by DMA on the stream the library calls currently go to -- main,
-// side or lane -- in order with the kernels around it.  lf_memcpy_h2d waits for the stream (its source may be pageable and
-// the caller may reuse it at once): for the per-step vectors of a small domain that wait IS the step (LF_ETRS89: two 23 kB
-// inflow vectors cost 0.7 of 1.85 ms).  A slot is reused only after its copy has finished (event per slot).
+// The staged upload (lf_staged_h2d above) on the stream the library calls currently go to -- main, side or lane.
+// lf_memcpy_h2d waits for the stream (its source may be pageable and the caller may reuse it at once): for the per-step
+// vectors of a small domain that wait IS the step (LF_ETRS89: two 23 kB inflow vectors cost 0.7 of 1.85 ms).
 int lf_memcpy_h2d_staged(int device, void *dst_dev, const void *src_host, size_t bytes)
 {
     if (!dst_dev || (!src_host && bytes)) return lf_set_error(LF_E_INVALID, "null argument");
     lf_device_ctx *c;
     LF_TRY(lf_ctx(device, &c));
     if (!bytes) return LF_OK;
-    lf_device_ctx::staged_slot &sl = c->staged[c->staged_next];
-    c->staged_next = (c->staged_next + 1) % 8;
-    if (sl.in_flight) LF_HIP(hipEventSynchronize(sl.done));
-    sl.in_flight = false;
-    if (sl.cap < bytes) {
-        if (sl.host) (void)hipHostFree(sl.host);
-        sl.host = nullptr;
-        sl.cap = 0;
-        LF_HIP(hipHostMalloc(&sl.host, bytes, hipHostMallocDefault));
-        sl.cap = bytes;
-    }
-    if (!sl.done) LF_HIP(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
-    std::memcpy(sl.host, src_host, bytes);
-    LF_HIP(hipMemcpyAsync(dst_dev, sl.host, bytes, hipMemcpyHostToDevice, c->stream));
-    LF_HIP(hipEventRecord(sl.done, c->stream));
-    sl.in_flight = true;
-    return LF_OK;
+    return lf_staged_h2d(c, c->stream, dst_dev, src_host, bytes);
 }
 
 // ---- double-buffered uploads on a second stream ------------------------------------------------------------------
@@ -219,6 +225,7 @@ int lf_upload_begin(int device, int set)
     lf_device_ctx *c;
     LF_TRY(upload_ctx(device, set, &c));
     if (c->consumed_valid[set]) LF_HIP(hipStreamWaitEvent(c->copy_stream, c->consumed[set], 0));
+    c->upload_open = set; // (only lf_upload_perturb_rows asks: the other upload calls take any time, as before)
     return LF_OK;
 }
 
@@ -379,6 +386,7 @@ int lf_upload_end(int device, int set)
     LF_TRY(upload_ctx(device, set, &c));
     LF_HIP(hipEventRecord(c->copied[set], c->copy_stream));
     c->copied_valid[set] = true;
+    c->upload_open = -1;
     return LF_OK;
 }
 
@@ -633,7 +641,7 @@ int lf_side_stream_join(int device)
 }
 
 // Releases what the context created on demand and keeps for reuse: the lane streams and their events, the staging
-// buffers of lf_upload_copy_f32 / lf_upload_rows, the download stream with its events, the staging arena of the *_host entry points.  Waits for the device first; refuses inside
+// buffers of lf_upload_copy_f32 / lf_upload_rows, the download stream with its events, the staging arena of the *_host entry points, the coefficient tables of the perturb calls.  Waits for the device first; refuses inside
 // a lane or side section.  Everything is created again on next use.
 int lf_device_trim(int device)
 {
@@ -660,6 +668,9 @@ int lf_device_trim(int device)
     c->soil_ws = nullptr;
     c->soil_ws_bytes = 0;
     c->soil_ntiles = 0;
+    if (c->perturb_tables) (void)hipFree(c->perturb_tables); // coefficient tables of the perturb calls: made again on next use
+    c->perturb_tables = nullptr;
+    for (int k = 0; k < lf_device_ctx::kPerturbSlots; ++k) c->perturb_read_valid[k] = false;
     return LF_OK;
 }
 

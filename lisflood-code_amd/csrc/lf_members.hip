@@ -9,6 +9,8 @@
 //   k_members_transform / k_members_resample : the analysis step of an assimilation cycle, the only kernels here that WRITE
 //                       the member rows -- x_new[m] = sum_k x[k] W[k][m] with taper and bounds, x_new[m] = x[parents[m]];
 //                       in place, the element's column in LDS before the first store (their own section below)
+//   k_members_perturb : the forecast step's counterpart -- the member rows written or rewritten from one base row or their
+//                       own values plus / times a sum of `rank` static patterns weighted by a [members][rank] table
 //
 // The value of (m, i) is rows[m * stride + i] / divisor, an IEEE division (divisor 1: the element itself), the result of
 // element i goes to dst_index ? dst_index[i] : i.  Everything is in member order: the sum is ((x0 + x1) + x2) + ..., the
@@ -323,6 +325,137 @@ __global__ void __launch_bounds__(W) k_members_resample(double *__restrict__ row
     for (int d = 0; d < P.n_dst; ++d) p[(long long)P.dst[d] * stride] = tile[P.slot[d] * W + lane];
 }
 
+// ---- the forecast step's counterpart: member rows perturbed from a few static patterns and a [members][rank] table ----------
+constexpr int kMaxPerturbMembers = 128;
+constexpr int kMaxPerturbRank = 16;   // 128 x 16 coefficients = 16 KiB: lf_device_ctx::kPerturbTableBytes
+constexpr int kPerturbLanes = 256;
+
+struct perturb_args {
+    long long stride, n, pattern_stride;
+    int members, multiplicative;
+    double lower, upper;
+};
+
+// s = sum_r c[r] P[r] in ascending r with one multiply and one add each, then the base, the mode and the bounds.  c is uniform
+// across the lanes (the member comes from a loop counter, the table from a kernel argument): RANK scalar loads.
+template <int RANK>
+__device__ __forceinline__ double perturb_value(const double (&P)[RANK], const double *__restrict__ c, double b, bool mul, double lo,
+                                                double hi)
+{
+    double s = c[0] * P[0];
+#pragma unroll
+    for (int r = 1; r < RANK; ++r) s = s + c[r] * P[r];
+    double v = mul ? b * (1.0 + s) : b + s;
+    v = (lo > v || (lo != lo && v == v)) ? lo : v;
+    v = (hi < v || (hi != hi && v == v)) ? hi : v;
+    return v;
+}
+
+// rows[m][i] = bound(base (+ or * (1 +)) sum_r coeff[m][r] patterns[r][i]) (lf_members_perturb_device).  A lane owns element
+// i of every member: its RANK pattern values, its bound values and (OWN = false) the one base value are loaded together and
+// stay in registers while it walks the members, every store a full line of consecutive positions.  OWN: every member's row is
+// its own base; the rows are loaded kStage at a time ahead of their arithmetic, each element read once and stored once.
+// base may be rows (member 0's row): the lane has read base[i] before it stores rows[0 * stride + i] and no other lane
+// touches element i, so neither pointer is __restrict__.  No LDS.
+template <int RANK, bool OWN>
+__global__ void __launch_bounds__(kPerturbLanes)
+k_members_perturb(double *rows, const double *base, const double *__restrict__ patterns, const double *__restrict__ coeff,
+                  const double *__restrict__ lower_dev, const double *__restrict__ upper_dev, perturb_args A)
+{
+    const long long i = (long long)blockIdx.x * kPerturbLanes + threadIdx.x;
+    if (i >= A.n) return;
+    double P[RANK];
+#pragma unroll
+    for (int r = 0; r < RANK; ++r) P[r] = patterns[(long long)r * A.pattern_stride + i];
+    const double lo = lower_dev ? lower_dev[i] : A.lower;
+    const double hi = upper_dev ? upper_dev[i] : A.upper;
+    const bool mul = A.multiplicative != 0;
+    const int M = A.members;
+    double *p = rows + i;
+    if (!OWN) {
+        const double b = base[i];
+#pragma unroll 4                        // (the coefficients of four members in flight ahead of their arithmetic)
+        for (int m = 0; m < M; ++m) p[(long long)m * A.stride] = perturb_value<RANK>(P, coeff + m * RANK, b, mul, lo, hi);
+        return;
+    }
+    int m = 0;
+    for (; m + kStage <= M; m += kStage) {
+        double raw[kStage];
+#pragma unroll
+        for (int u = 0; u < kStage; ++u) raw[u] = row_load(p + (long long)(m + u) * A.stride);
+#pragma unroll
+        for (int u = 0; u < kStage; ++u)
+            p[(long long)(m + u) * A.stride] = perturb_value<RANK>(P, coeff + (m + u) * RANK, raw[u], mul, lo, hi);
+    }
+    for (; m < M; ++m) {
+        double *q = p + (long long)m * A.stride;
+        *q = perturb_value<RANK>(P, coeff + m * RANK, row_load(q), mul, lo, hi);
+    }
+}
+
+template <int RANK>
+void launch_perturb(hipStream_t s, double *rows, const double *base, const double *patterns, const double *coeff,
+                    const double *lower_dev, const double *upper_dev, const perturb_args &A)
+{
+    const dim3 grid((unsigned)((A.n + kPerturbLanes - 1) / kPerturbLanes)), block(kPerturbLanes);
+    if (base)
+        hipLaunchKernelGGL((k_members_perturb<RANK, false>), grid, block, 0, s, rows, base, patterns, coeff, lower_dev, upper_dev, A);
+    else
+        hipLaunchKernelGGL((k_members_perturb<RANK, true>), grid, block, 0, s, rows, base, patterns, coeff, lower_dev, upper_dev, A);
+}
+
+// what the two perturb entry points refuse, in the order the header lists it (no device is touched)
+int check_perturb(const double *rows_dev, int members, int64_t stride, int64_t n, int rank, const double *patterns_dev,
+                  int64_t pattern_stride, const double *coeff_host, int multiplicative, const double *lower_dev, double lower,
+                  const double *upper_dev, double upper)
+{
+    if (!rows_dev) return lf_set_error(LF_E_INVALID, "rows_dev is NULL");
+    if (!patterns_dev) return lf_set_error(LF_E_INVALID, "patterns_dev is NULL");
+    if (!coeff_host) return lf_set_error(LF_E_INVALID, "coeff_host is NULL");
+    if (members < 1) return lf_set_error(LF_E_INVALID, "members must be at least 1 (got %d)", members);
+    if (members > kMaxPerturbMembers)
+        return lf_set_error(LF_E_INVALID, "members = %d: a perturbation takes at most %d members", members, kMaxPerturbMembers);
+    if (rank < 1 || rank > kMaxPerturbRank) return lf_set_error(LF_E_INVALID, "rank must be 1 to %d (got %d)", kMaxPerturbRank, rank);
+    if (n < 0 || n > 0x7fffffffll) return lf_set_error(LF_E_INVALID, "n = %lld outside the 32-bit range of a launch", (long long)n);
+    if (members > 1 && stride < n) return lf_set_error(LF_E_INVALID, "stride %lld is less than n = %lld", (long long)stride, (long long)n);
+    if (rank > 1 && pattern_stride < n)
+        return lf_set_error(LF_E_INVALID, "pattern_stride %lld is less than n = %lld", (long long)pattern_stride, (long long)n);
+    if (multiplicative != 0 && multiplicative != 1)
+        return lf_set_error(LF_E_INVALID, "multiplicative must be 0 or 1 (got %d)", multiplicative);
+    if (!lower_dev && !upper_dev && lower > upper)
+        return lf_set_error(LF_E_INVALID, "lower = %g is greater than upper = %g", lower, upper);
+    return LF_OK;
+}
+
+// The coefficient table goes up through a page-locked slot into the next table of the context's ring, on `s`; the kernel
+// behind it on `s`; the event behind the kernel is what the slot's next user makes ITS stream wait for.  The host never waits.
+int enqueue_perturb(lf_device_ctx *c, hipStream_t s, double *rows_dev, int members, int64_t stride, int64_t n, const double *base_dev,
+                    int rank, const double *patterns_dev, int64_t pattern_stride, const double *coeff_host, int multiplicative,
+                    const double *lower_dev, double lower, const double *upper_dev, double upper)
+{
+    if (!c->perturb_tables) LF_HIP(hipMalloc(&c->perturb_tables, lf_device_ctx::kPerturbSlots * lf_device_ctx::kPerturbTableBytes));
+    const int k = c->perturb_next;
+    c->perturb_next = (k + 1) % lf_device_ctx::kPerturbSlots;
+    if (!c->perturb_read[k]) LF_HIP(hipEventCreateWithFlags(&c->perturb_read[k], hipEventDisableTiming));
+    if (c->perturb_read_valid[k]) LF_HIP(hipStreamWaitEvent(s, c->perturb_read[k], 0));
+    double *coeff = (double *)((char *)c->perturb_tables + (size_t)k * lf_device_ctx::kPerturbTableBytes);
+    LF_TRY(lf_staged_h2d(c, s, coeff, coeff_host, (size_t)members * (size_t)rank * sizeof(double)));
+    const perturb_args A = {(long long)stride, (long long)n, (long long)pattern_stride, members, multiplicative, lower, upper};
+#define LF_PERTURB_RANK(R) \
+    case R: launch_perturb<R>(s, rows_dev, base_dev, patterns_dev, coeff, lower_dev, upper_dev, A); break;
+    switch (rank) {
+        LF_PERTURB_RANK(1) LF_PERTURB_RANK(2) LF_PERTURB_RANK(3) LF_PERTURB_RANK(4) LF_PERTURB_RANK(5) LF_PERTURB_RANK(6)
+        LF_PERTURB_RANK(7) LF_PERTURB_RANK(8) LF_PERTURB_RANK(9) LF_PERTURB_RANK(10) LF_PERTURB_RANK(11) LF_PERTURB_RANK(12)
+        LF_PERTURB_RANK(13) LF_PERTURB_RANK(14) LF_PERTURB_RANK(15)
+    default: launch_perturb<16>(s, rows_dev, base_dev, patterns_dev, coeff, lower_dev, upper_dev, A); break;
+    }
+#undef LF_PERTURB_RANK
+    LF_HIP(hipGetLastError());
+    LF_HIP(hipEventRecord(c->perturb_read[k], s));
+    c->perturb_read_valid[k] = true;
+    return LF_OK;
+}
+
 // what the two in-place calls refuse in common
 int check_inplace_rows(const double *rows_dev, int members, int cap, const char *what, int64_t stride, int64_t n)
 {
@@ -551,4 +684,32 @@ int lf_members_resample_device(int device, double *rows_dev, int members, int64_
         launch_resample<64>(c->stream, rows_dev, (long long)stride, (long long)n, P);
     LF_HIP(hipGetLastError());
     return LF_OK;
+}
+
+int lf_members_perturb_device(int device, double *rows_dev, int members, int64_t stride, int64_t n, const double *base_dev, int rank,
+                              const double *patterns_dev, int64_t pattern_stride, const double *coeff_host, int multiplicative,
+                              const double *lower_dev, double lower, const double *upper_dev, double upper)
+{
+    LF_TRY(check_perturb(rows_dev, members, stride, n, rank, patterns_dev, pattern_stride, coeff_host, multiplicative, lower_dev,
+                         lower, upper_dev, upper));
+    if (n == 0) return LF_OK;
+    lf_device_ctx *c;
+    LF_TRY(lf_ctx(device, &c));
+    return enqueue_perturb(c, c->stream, rows_dev, members, stride, n, base_dev, rank, patterns_dev, pattern_stride, coeff_host,
+                           multiplicative, lower_dev, lower, upper_dev, upper);
+}
+
+int lf_upload_perturb_rows(int device, double *rows_dev, int members, int64_t stride, int64_t n, const double *base_dev, int rank,
+                           const double *patterns_dev, int64_t pattern_stride, const double *coeff_host, int multiplicative,
+                           const double *lower_dev, double lower, const double *upper_dev, double upper)
+{
+    LF_TRY(check_perturb(rows_dev, members, stride, n, rank, patterns_dev, pattern_stride, coeff_host, multiplicative, lower_dev,
+                         lower, upper_dev, upper));
+    lf_device_ctx *c;
+    LF_TRY(lf_ctx(device, &c));
+    if (c->upload_open < 0 || !c->copy_stream)
+        return lf_set_error(LF_E_INVALID, "lf_upload_perturb_rows outside lf_upload_begin(set) .. lf_upload_end(set)");
+    if (n == 0) return LF_OK;
+    return enqueue_perturb(c, c->copy_stream, rows_dev, members, stride, n, base_dev, rank, patterns_dev, pattern_stride, coeff_host,
+                           multiplicative, lower_dev, lower, upper_dev, upper);
 }

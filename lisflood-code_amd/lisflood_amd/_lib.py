@@ -38,6 +38,7 @@ _SIGNATURES = {
     "ipiqqdiiqpppipqpp": "members_track_device",
     "ipiqqdpqpppipqp": "members_summary_device",
     "ipiqqp": "members_resample_device",
+    "ipiqqpipqpipdpd": "members_perturb_device upload_perturb_rows",
     "ipiqqpppdpd": "members_transform_device",
     "ipiqqq": "pixel_aggregates_members_device",
     "ipiz": "memset",

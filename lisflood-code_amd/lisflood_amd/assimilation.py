@@ -58,3 +58,64 @@ def systematic_parents(weights, u):
     spare = np.repeat(np.arange(M), np.maximum(counts - 1, 0))
     parents[free] = spare
     return parents
+
+
+def fourier_patterns(land_mask, rank, length_scale, rng):
+    """Static spatial patterns for HotPathEnsemble.forcing_perturbation() / perturb(): random Fourier features (Rahimi &
+    Recht 2007) of a Gaussian covariance with the given length scale, in pixels, on the land pixels of land_mask [H, W]:
+
+        P_r(x) = sqrt(2 / rank) cos(w_r . x + phi_r),   w_r ~ N(0, I / length_scale^2),   phi_r ~ U[0, 2 pi),   x = (row, column)
+
+    With iid N(0, 1) coefficients c [members, rank], c @ P is a smooth field of (approximately, for the rank is small) unit
+    variance and covariance exp(-|x - y|^2 / (2 length_scale^2)); |P| <= sqrt(2 / rank) everywhere.
+    -> float64 [rank, N] in pixel order (the land pixels in row-major order), rank 1 to 16.  rng: a numpy Generator, which
+    is drawn from in a fixed order (the rank frequencies, then the rank phases)."""
+    mask = np.asarray(land_mask)
+    if mask.ndim != 2 or mask.dtype != np.bool_:
+        raise ValueError("land_mask must be a boolean [H, W] array")
+    if not (isinstance(rank, (int, np.integer)) and 1 <= rank <= 16):
+        raise ValueError("rank must be an integer from 1 to 16")
+    if not (np.ndim(length_scale) == 0 and np.isfinite(length_scale) and length_scale > 0):
+        raise ValueError("length_scale must be a finite number of pixels above 0")
+    rows, cols = np.nonzero(mask)
+    w = rng.standard_normal((rank, 2)) / float(length_scale)
+    phi = rng.uniform(0.0, 2.0 * np.pi, rank)
+    x = np.stack([rows, cols]).astype(np.float64)                     # [2, N]
+    return np.sqrt(2.0 / rank) * np.cos(w @ x + phi[:, None])
+
+
+def ar1_coefficients(previous, rho, sigma, rng):
+    """One step of the AR(1) process that perturbed-forcing and model-error schemes run on their coefficients:
+
+        c = rho previous + sqrt(1 - rho^2) sigma N(0, 1)
+
+    whose stationary standard deviation is sigma.  previous: [members, rank] -- or None with rho = (members, rank): a first
+    draw, sigma N(0, 1).  rho in [-1, 1]; sigma >= 0, a scalar or anything that broadcasts to [members, rank] (a value
+    per pattern).  rho = 1 returns a copy of previous bit for bit (nothing is added, so a -0.0 keeps its sign); the rng is
+    drawn from all the same, so a run's random stream does not depend on rho.  -> float64 [members, rank]."""
+    sigma = np.asarray(sigma, np.float64)
+    if not (np.all(np.isfinite(sigma)) and np.all(sigma >= 0)):
+        raise ValueError("sigma must be finite and not negative")
+    if previous is None:
+        shape = tuple(rho) if np.ndim(rho) == 1 and len(rho) == 2 else None
+        if shape is None or not all(isinstance(k, (int, np.integer)) and k >= 1 for k in shape):
+            raise ValueError("a first draw (previous=None) takes rho = (members, rank)")
+        try:
+            np.broadcast_to(sigma, shape)
+        except ValueError:
+            raise ValueError("sigma does not broadcast to [%d, %d]" % shape) from None
+        return sigma * rng.standard_normal(shape)
+    previous = np.asarray(previous, np.float64)
+    if previous.ndim != 2:
+        raise ValueError("previous must be [members, rank]")
+    if not (np.ndim(rho) == 0 and -1.0 <= rho <= 1.0):
+        raise ValueError("rho must lie in [-1, 1]")
+    try:
+        np.broadcast_to(sigma, previous.shape)
+    except ValueError:
+        raise ValueError("sigma does not broadcast to [%d, %d]" % previous.shape) from None
+    noise = rng.standard_normal(previous.shape)
+    scale = np.sqrt(1.0 - float(rho) * float(rho))
+    if scale == 0.0:
+        return float(rho) * previous
+    return float(rho) * previous + (scale * sigma) * noise

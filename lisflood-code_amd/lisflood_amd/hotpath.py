@@ -965,6 +965,17 @@ class HotPathEnsemble(_HotPath):
     the parents cross PCIe (assimilation.enkf_weights / systematic_parents make them from sample()).  Both rewrite the
     particle -- state_names() and, with structures=, the site state and TransCum -- and leave what belongs to the member's
     slot: forcing sets, inflow-hydrograph rows, trackers, optional diagnostic maps.
+    The forecast half of that cycle -- what makes the members differ -- is made on the device as well, from a few static
+    spatial patterns and a [members, rank] table of coefficients per step (e.g. an AR(1) in time:
+    assimilation.fourier_patterns / ar1_coefficients); only the table crosses PCIe.  forcing_perturbation(name, patterns)
+    registers the patterns of a forcing vector, step(forcing, coefficients=) / prefetch(forcing, coefficients=) then write
+    every member's row as f * (1 + sum_r c[m, r] P[r]) or f + sum, bounded, on the copy stream behind the upload
+    (lf_upload_perturb_rows; an [N] vector goes up as ONE row); perturb(coefficients, patterns, names) does the same to state
+    vectors in place (lf_members_perturb_device), which keeps the copies resample() made from staying copies.  Measured at
+    2000^2, rank 8, Rain and ETRef perturbed, 4 / 16 / 51 members (tools/bench_members_perturb.py): the prefetched step on
+    [N] forcing 12.59 / 46.87 / 139.23 ms, with coefficients 12.72 / 46.66 / 139.66 ms (the two kernels take 0.15 / 0.32 /
+    0.65 ms, 0.80 - 0.94 of the copy ceiling at 8 (rank + 1 + members) bytes per element), from host-made [members, N]
+    rows 12.67 / 47.17 / 141.54 ms plus 222 / 854 / 2523 ms of numpy per step to make them.
     Not in this class (HotPathDevice has them): step_profile, state_maps / load_state_maps and mass_balance."""
 
     def __init__(self, values, scalars, land_mask, ldd_to_chan, ldd_kinematic, members, split=True, device=0, structures=None,
@@ -1041,7 +1052,9 @@ class HotPathEnsemble(_HotPath):
         self.force = [{k: E.dev[k] for k in FORCING},
                       {k: DeviceArray(M * self.pstride, np.float64, device).zero() for k in FORCING}]
         self._shared = [{k: E._shared_forcing[k] for k in FORCING}, {k: True for k in FORCING}]
-        self._cur, self._prefetched, self._keep = 0, None, [None, None]
+        self._cur, self._prefetched, self._prefetched_coefficients, self._keep = 0, None, None, [None, None]
+        # forcing_perturbation(): name -> (patterns on the device in sweep order, rank, multiplicative, lower, upper)
+        self._perturbations = {}
         # position -> pixel, for the upload (a blocking copy on the main stream: the memsets of set 1 have ended with it,
         # before the copy stream can write the set)
         self._pidx = DeviceArray.from_host(self.pixel_of_position.astype(np.int32), device)
@@ -1078,10 +1091,14 @@ class HotPathEnsemble(_HotPath):
         self._qin_old = q
 
     # ---- forcing: two sets of member rows, uploaded on the copy stream and ordered on the device ----------------------------
-    def _upload(self, b, forcing):
+    def _upload(self, b, forcing, coefficients=None):
         """the five vectors as the caller holds them into set b: one lf_upload_rows each (raw copy + gather / widen kernel on
-        the copy stream, behind the kernels that last read set b); the host arrays stay alive until the set is uploaded again"""
+        the copy stream, behind the kernels that last read set b); the host arrays stay alive until the set is uploaded again.
+        A vector with a forcing_perturbation() and coefficients: an [N] vector goes into member 0's row only and
+        lf_upload_perturb_rows, behind it on the copy stream, writes every member's row from that one; [members, N] rows go
+        up as always and are perturbed where they lie.  Either way the rows differ from then on (_shared)."""
         L, dev, M, N = lib(), self.device, self.members, self.N
+        coeff = self._forcing_coefficients(coefficients)
         host = []
         for k in FORCING:
             a = np.asarray(forcing[k])
@@ -1091,12 +1108,67 @@ class HotPathEnsemble(_HotPath):
         check(L.lf_upload_begin(dev, b))
         try:
             for k, a in zip(FORCING, host):
-                check(L.lf_upload_rows(dev, self.force[b][k].ptr, self.pstride, M, a.ctypes.data_as(C.c_void_p),
-                                       1 if a.ndim == 1 else M, 1 if a.dtype == np.float32 else 0, N, self._pidx.ptr))
-                self._shared[b][k] = a.ndim == 1
+                c, rows = coeff.get(k), self.force[b][k].ptr
+                check(L.lf_upload_rows(dev, rows, self.pstride, 1 if c is not None and a.ndim == 1 else M,
+                                       a.ctypes.data_as(C.c_void_p), 1 if a.ndim == 1 else M, 1 if a.dtype == np.float32 else 0,
+                                       N, self._pidx.ptr))
+                if c is not None:
+                    patterns, rank, multiplicative, lower, upper = self._perturbations[k]
+                    check(L.lf_upload_perturb_rows(dev, rows, M, self.pstride, N, rows if a.ndim == 1 else None, rank,
+                                                   patterns.ptr, N, c.ctypes.data_as(C.c_void_p), multiplicative, None, lower,
+                                                   None, upper))
+                self._shared[b][k] = a.ndim == 1 and c is None
         finally:
             check(L.lf_upload_end(dev, b))
         self._keep[b] = host
+
+    def forcing_perturbation(self, name, patterns, multiplicative=True, lower=0.0, upper=np.inf):
+        """Register the spatial patterns from which the member rows of forcing vector `name` are perturbed on the device:
+        with coefficients={name: c} in step() / prefetch(), c [members, rank] float64, member m's row becomes
+            bound(f * (1 + sum_r c[m, r] patterns[r]))   (multiplicative)      bound(f + sum_r c[m, r] patterns[r])   (additive)
+        element by element, the sum in ascending r with one multiply and one add each, f the vector as uploaded -- [N], one
+        row for every member, or [members, N] -- and bound(v) = lower where lower > v, then upper where upper < v (scalars;
+        the defaults keep a flux non-negative).  patterns: [rank, N] float64 in pixel order, rank 1 to 16, e.g.
+        assimilation.fourier_patterns(); gathered to sweep order and uploaded here, once, with a blocking copy (the copy
+        stream reads them, and nothing orders it behind the main stream but the host).  patterns=None removes the
+        registration.  Only the [members, rank] table crosses PCIe per step (lf_upload_perturb_rows)."""
+        if name not in FORCING:
+            raise ValueError("%s is no forcing vector (%s)" % (name, ", ".join(FORCING)))
+        if self.members > 128:
+            raise ValueError("a forcing perturbation takes at most 128 members (%d)" % self.members)
+        new = None
+        if patterns is not None:
+            host = np.asarray(patterns, np.float64)
+            if host.ndim != 2 or host.shape[1] != self.N or not 1 <= host.shape[0] <= 16:
+                raise ValueError("patterns must be [rank, %d] in pixel order with rank 1 to 16" % self.N)
+            if multiplicative not in (True, False, 0, 1):
+                raise ValueError("multiplicative must be True or False")
+            lower, upper = float(lower), float(upper)
+            if lower > upper:
+                raise ValueError("lower %g is greater than upper %g" % (lower, upper))
+            new = (np.ascontiguousarray(host[:, self.pixel_of_position]), host.shape[0], int(bool(multiplicative)), lower, upper)
+        old = self._perturbations.pop(name, None)
+        if old is not None:
+            check(lib().lf_device_synchronize(self.device))     # (a kernel on the copy stream may still read the patterns)
+            old[0].free()
+        if new is not None:
+            self._perturbations[name] = (DeviceArray.from_host(new[0].reshape(-1), self.device),) + new[1:]
+
+    def _forcing_coefficients(self, coefficients):
+        """coefficients of step() / prefetch() checked -> name -> contiguous float64 [members, rank]"""
+        out = {}
+        if coefficients is None:
+            return out
+        if not isinstance(coefficients, dict):
+            raise ValueError("coefficients must be a dict: forcing name -> [members, rank] float64")
+        for k, c in coefficients.items():
+            if k not in self._perturbations:
+                raise ValueError("coefficients for %s, which has no forcing_perturbation()" % k)
+            rank = self._perturbations[k][1]
+            if np.shape(c) != (self.members, rank):
+                raise ValueError("coefficients[%s] must be [%d, %d]" % (k, self.members, rank))
+            out[k] = f64(c)
+        return out
 
     def _use_set(self, b):
         """point the argument blocks of the stages that read forcing, and the land surface's own table, at set b"""
@@ -1119,24 +1191,36 @@ class HotPathEnsemble(_HotPath):
         the call has returned: upload_wait() before refilling a set that was handed over (or alternate between two sets)."""
         return self._pinned_set((self.members, self.N) if per_member else (self.N,), dtype)
 
-    def prefetch(self, forcing):
+    def prefetch(self, forcing, coefficients=None):
         """Start uploading the forcing of the NEXT step(forcing) call now, into the set that is not in use: the copy and the
         ordering kernel run on the copy stream while the kernels of the step just enqueued are still executing.  Pass the
-        same dict object to that step(); a step(None) in between stays on the set in use and leaves the prefetch pending."""
-        self._upload(1 - self._cur, forcing)
-        self._prefetched = forcing
+        same dict object to that step(); a step(None) in between stays on the set in use and leaves the prefetch pending.
+        coefficients: as step(); the prefetch carries them, the matching step() passes None or the same dict."""
+        if forcing is None and coefficients is not None:
+            raise ValueError("coefficients without forcing: the rows on the device are perturbed already")
+        self._upload(1 - self._cur, forcing, coefficients)
+        self._prefetched, self._prefetched_coefficients = forcing, coefficients
 
-    def step(self, forcing, time_since_start=None, QInM3=None):
+    def step(self, forcing, time_since_start=None, QInM3=None, coefficients=None):
         """forcing: dict of Rain, SnowMelt, EWRef, ETRef, ESRef, each [N] (every member) or [members, N], pixel order,
         float32 or float64 -- or None: the forcing rows of the step before (no PCIe traffic); QInM3 (structures= with inflow
-        hydrographs): [N] or [members, N]"""
+        hydrographs): [N] or [members, N]; coefficients: None or forcing name -> [members, rank] float64 for vectors with a
+        forcing_perturbation(), whose member rows are then perturbed on the device behind their upload"""
+        if forcing is None and coefficients is not None:
+            raise ValueError("coefficients without forcing: the rows on the device are perturbed already")
+        if forcing is not None and self._prefetched is forcing and coefficients is not None \
+                and coefficients is not self._prefetched_coefficients:
+            raise ValueError("this forcing was prefetched with other coefficients: the prefetch carries them, pass None or "
+                             "the same dict")
+        if forcing is not None and self._prefetched is not forcing:
+            self._forcing_coefficients(coefficients)    # (refused before anything of this step is enqueued)
         if QInM3 is not None:
             self.set_inflow(QInM3)
         L, dev, E, M = lib(), self.device, self.land, self.members
         if forcing is not None:
             if self._prefetched is not forcing:
-                self._upload(1 - self._cur, forcing)
-            self._prefetched = None
+                self._upload(1 - self._cur, forcing, coefficients)
+            self._prefetched = self._prefetched_coefficients = None
             self._use_set(1 - self._cur)
         b = self._cur
         check(L.lf_compute_acquire(dev, b))
@@ -1627,7 +1711,8 @@ class HotPathEnsemble(_HotPath):
         return [(d.ptr.value, width, stride, order, None)]
 
     def _pixel_rows(self, a, order, v=None):
-        """The device row of a per-pixel host array ([N] in pixel order, or row v of a [3, N] one) in the order of a row set:
+        """The device row of a per-pixel host array ([N] in pixel order, or row v of a [3, N] one; v = "all": every row of a
+        [rank, N] one, N' entries apart, the patterns of perturb()) in the order of a row set:
         "land" sweep order, "channel" engine order, "lake" / "res" the site's pixel.  Gathered and uploaded once per array
         object and order: pass the SAME array every cycle (a changed copy of it is a new array).  The rows a transform() call
         has resolved are pinned (_analysis_pinned) until its kernels are enqueued: what makes room for a new row is the row
@@ -1644,14 +1729,15 @@ class HotPathEnsemble(_HotPath):
             else:
                 index = self.pixel_of_position if order == "land" else self.gpix
             host = np.asarray(a, np.float64)
-            host = host if host.ndim == 1 else host[v]
+            host = host if host.ndim == 1 or v == "all" else host[v]
             while len(self._analysis_cache) >= self._ROWS_CACHED:
                 old = next((k for k in self._analysis_cache if k not in self._analysis_pinned), None)
                 if old is None:
                     break
                 check(lib().lf_device_synchronize(self.device))     # (a kernel of an earlier call may still read it)
                 self._analysis_cache.pop(old)[1].free()
-            hit = self._analysis_cache[key] = (a, DeviceArray.from_host(np.ascontiguousarray(host[index]), self.device))
+            rows = np.ascontiguousarray(host[..., index]).reshape(-1)
+            hit = self._analysis_cache[key] = (a, DeviceArray.from_host(rows, self.device))
         return hit[1]
 
     def _analysis_bounds(self, names, bounds):
@@ -1726,6 +1812,50 @@ class HotPathEnsemble(_HotPath):
             w = self._weights[1]
             for base, stride, n, tp, lo_dev, lo, hi_dev, hi in calls:
                 check(L.lf_members_transform_device(dev, base, M, stride, n, w.ptr, tp, lo_dev, lo, hi_dev, hi))
+        finally:
+            self._analysis_pinned = set()
+
+    def perturb(self, coefficients, patterns, names, multiplicative=False, bounds=None):
+        """Model error or jitter on the device: for every element i of the state vectors `names`, in place on the member
+        rows as they lie,  x[m, i] = x[m, i] + sum_r coefficients[m, r] patterns[r, i]  (multiplicative: x[m, i] * (1 + sum)),
+        summed in ascending r with one multiply and one add each (lf_members_perturb_device: one call per row set, a [3, N]
+        vector three, each with the same patterns).  It is what keeps the copies that resample() made from staying copies.
+        coefficients: [members, rank] float64, e.g. assimilation.ar1_coefficients(); only they cross PCIe, through a
+        page-locked slot.  patterns: [rank, N] float64 in pixel order, rank 1 to 16, e.g. assimilation.fourier_patterns();
+        laid out per row order and uploaded once per array object, like taper and bound rows (pass the SAME array every
+        cycle); a site row takes the pattern at the site's pixel.  names: required -- a vector of analysis_names() or a list
+        of them.  bounds: as transform().  At most 128 members.  Ordered like transform(): joins the side stream and
+        enqueues, no host synchronisation."""
+        M, N = self.members, self.N
+        if M > 128:
+            raise ValueError("perturb() takes at most 128 members (%d)" % M)
+        if not (isinstance(patterns, np.ndarray) and patterns.dtype == np.float64 and patterns.ndim == 2
+                and patterns.shape[1] == N and 1 <= patterns.shape[0] <= 16):
+            raise ValueError("patterns must be a float64 array of shape [rank, %d] in pixel order with rank 1 to 16" % N)
+        rank = patterns.shape[0]
+        if np.shape(coefficients) != (M, rank):
+            raise ValueError("coefficients must be [%d, %d]" % (M, rank))
+        if names is None:
+            raise ValueError("names is required: the state vectors to perturb")
+        c = f64(coefficients)
+        names = self._analysis_names(names)
+        bounds = self._analysis_bounds(names, bounds)
+        calls = []
+        self._analysis_pinned = set()
+        try:
+            for name in names:
+                lower, upper = bounds.get(name, (None, None))
+                for base, n, stride, order, v in self._analysis_rows(name):
+                    arg = lambda b, inf: (None, inf) if b is None else (None, b) if isinstance(b, float) \
+                        else (self._pixel_rows(b, order, v).ptr, 0.0)
+                    if n:
+                        calls.append((base, stride, n, self._pixel_rows(patterns, order, "all").ptr)
+                                     + arg(lower, -np.inf) + arg(upper, np.inf))
+            L, dev = lib(), self.device
+            check(L.lf_side_stream_join(dev))
+            for base, stride, n, pt, lo_dev, lo, hi_dev, hi in calls:
+                check(L.lf_members_perturb_device(dev, base, M, stride, n, None, rank, pt, n, c.ctypes.data_as(C.c_void_p),
+                                                  int(bool(multiplicative)), lo_dev, lo, hi_dev, hi))
         finally:
             self._analysis_pinned = set()
 
@@ -1818,6 +1948,8 @@ class HotPathEnsemble(_HotPath):
                     for d in hit if isinstance(d, DeviceArray)] + list(self._products.values()) + [self._gpix_dev]
         products += [self._weights[1]] if self._weights else []
         products += [d for t in self._trackers.values() for d in list(t.dev.values()) + [t.thr]]
+        products += [p[0] for p in self._perturbations.values()]
+        self._perturbations = {}
         self._thresholds, self._gauges, self._products, self._gpix_dev, self._outside_held = {}, {}, {}, None, {}
         self._trackers, self._weights, self._analysis_cache = {}, None, {}
         self._free_shared([self._gidx, self._side, self._pidx] + list(self._qin.values()) +
