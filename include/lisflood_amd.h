@@ -853,6 +853,51 @@ int lf_pixel_aggregates_device(int device, const lf_pixel_args *a);
 int lf_pixel_aggregates_members_device(int device, const lf_pixel_args *a, int members, int64_t member_stride,
                                        int64_t pixel_member_stride, int64_t forcing_member_stride);
 
+/* The front of the model step: snow.dynamic followed by frost.dynamic, three elevation zones (0: the highest).  From
+ * precipitation and average temperature it makes the Rain, SnowMelt and isFrozenSoil the land surface starts from, and it
+ * carries the snow pack of the zones (SnowCoverS) and the frost index from one step to the next.  All arithmetic is fp64,
+ * every + - * / one IEEE operation in the order written, max / min are numpy's maximum / minimum (a NaN operand gives
+ * NaN), comparisons are false on NaN; exp is OCML's (exactly 1 where its argument is a zero).  Per pixel p:
+ *   seas = SnowSeasonTerm + SnowMeltCoef[p];  Snow = Rain = SnowMelt = SnowCover = 0
+ *   for i in 0, 1, 2:
+ *     TavgS = Tavg + DeltaTSnow[p] * (i - 1)                       ((i - 1) as the doubles -1.0, 0.0, 1.0)
+ *     SnowS = TavgS <  TempSnow ? SnowFactor[p] * Precipitation : 0
+ *     RainS = TavgS >= TempSnow ? Precipitation : 0
+ *     MeltS = max((TavgS - TempMelt) * seas * (1 + 0.01 * RainS) * DtDay, 0)
+ *     IceS  = max((i < 2 ? Tavg : TavgS) * IceMeltCoef * DtDay * SummerSeason, 0)
+ *     MeltS = max(min(MeltS + IceS, SnowCoverS[i]), 0)
+ *     SnowCoverS[i] = SnowCoverS[i] + SnowS - MeltS
+ *     Snow += SnowS;  Rain += RainS;  SnowMelt += MeltS;  SnowCover += SnowCoverS[i]
+ *   Snow /= 3;  Rain /= 3;  SnowMelt /= 3;  SnowCover /= 3          (divisions)
+ *   Kfrost = Tavg < 0 ? 0.08 : 0.5
+ *   rate = -(1 - Afrost) * FrostIndex - Tavg * exp(-0.04 * Kfrost * SnowCover / SnowWaterEquivalent)
+ *   FrostIndex = max(FrostIndex + rate * DtDay, 0);  isFrozenSoil = FrostIndex > FrostIndexThreshold
+ * SnowSeasonTerm and SummerSeason are the step's season values, taken as given (lisflood_amd.snow_frost.season_terms). */
+typedef struct lf_snow_frost_args {
+    const double *Precipitation, *Tavg;                   /* rows, forcing layout */
+    double *SnowCoverS;                                   /* [3,N] rows, in / out */
+    double *FrostIndex;                                   /* [N] rows, in / out */
+    double *Rain, *SnowMelt, *Snow, *SnowCover;           /* [N] rows, out; Snow may be NULL */
+    uint8_t *isFrozenSoil;                                /* byte rows, out */
+    const double *DeltaTSnow, *SnowMeltCoef, *SnowFactor; /* [N], shared by all members */
+    double TempSnow, TempMelt, IceMeltCoef, DtDay, Afrost, SnowWaterEquivalent, FrostIndexThreshold, SnowSeasonTerm,
+        SummerSeason;
+    int64_t N;
+} lf_snow_frost_args;
+/* One kernel and one enqueue for a single run (members = 1) and an ensemble: `a` names member 0's rows, member m's lie
+ * m * zone_stride elements further on (SnowCoverS, zone i at i * N inside), m * row_stride elements further on (FrostIndex
+ * and the [N] outputs; isFrozenSoil: row_stride BYTES) and m * forcing_stride elements further on (Precipitation, Tavg;
+ * 0: one row for all).  Elements between a row's length and its stride are neither read nor written.  A lane owns a pixel
+ * and walks up to 8 members: the statics are read once per pixel and slice of 8 members.
+ * Halves: FrostIndex == NULL (and then isFrozenSoil == NULL): snow only.  SnowCoverS == NULL: frost only, SnowCover is
+ * then an INPUT and Precipitation, Rain, SnowMelt, Snow and the three statics are not used (the first four must be NULL).
+ * Refused with LF_E_INVALID before anything is enqueued: every other NULL combination, two vectors of which one is
+ * written sharing an element, N < 0, members < 1, zone_stride < 3 * N, row_stride < N, forcing_stride neither 0 nor at
+ * least N.  N == 0 succeeds and launches nothing.  Enqueued on the current stream (it follows lf_side_stream_begin); the
+ * call does not synchronise. */
+int lf_snow_frost_members_device(int device, const lf_snow_frost_args *a, int members, int64_t zone_stride, int64_t row_stride,
+                                 int64_t forcing_stride);
+
 /* host-buffer forms (drop-in for the numba kernels; PCIe-inclusive) */
 int lf_interception_host(int device, const lf_interception_args *a);
 int lf_soil_columns_host(int device, const lf_soil_args *a);

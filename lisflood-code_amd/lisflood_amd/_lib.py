@@ -40,7 +40,7 @@ _SIGNATURES = {
     "ipiqqp": "members_resample_device",
     "ipiqqpipqpipdpd": "members_perturb_device upload_perturb_rows",
     "ipiqqpppdpd": "members_transform_device",
-    "ipiqqq": "pixel_aggregates_members_device",
+    "ipiqqq": "pixel_aggregates_members_device snow_frost_members_device",
     "ipiz": "memset",
     "ippii": "lddrepair_raster_device",
     "ipppi": "land_columns_device",

@@ -6,6 +6,9 @@ covers), with every vector kept in HBM between steps:
     wavefront) -> ChanQAvg
 
 Per step only the meteorological forcing (Rain, SnowMelt, EWRef, ETRef, ESRef -- five [N] vectors) crosses PCIe.
+With meteo= the step begins one module earlier: snow.dynamic and frost.dynamic (snow_frost.py, lf_snow_frost_members_device)
+make Rain, SnowMelt and isFrozenSoil on the device from Precipitation and Tavg, which take the two vectors' place in the
+forcing, and the snow pack of three elevation zones and the frost index are state like the soil's.
 The stages are exactly the kernels the module classes (`soilloop`, `pixel_aggregates`, `surface_routing`,
 `routing`) call -- those stage their `var` arrays through the host on every call, this class wires the same
 device buffers from one stage to the next.  Channel vectors live in the channel router's engine order; the one
@@ -20,6 +23,7 @@ import numpy as np
 from . import output
 from . import pixel_aggregates as PA
 from . import routing as RT
+from . import snow_frost as SF
 from . import soilloop as SL
 from . import surface_routing as SR
 from ._lib import DeviceArray, PinnedArray, check, f64, lib, timer_start, timer_stop, u8
@@ -27,6 +31,8 @@ from .channel_domain import _structures_on_subdomain, channel_domain, inert_pixe
 from .kinematic_wave_parallel import Graph, kinematicWave
 
 FORCING = ("Rain", "SnowMelt", "EWRef", "ETRef", "ESRef")
+# with meteo=: the snow and frost kernel makes Rain, SnowMelt and isFrozenSoil on the device from these
+METEO_FORCING = SF.METEO + ("EWRef", "ETRef", "ESRef")
 _CHANNEL_NAMES = set(RT._STATIC + RT._STATE + RT._OUT)
 # HotPathEnsemble.track_begin: the derived names of a tracked name's accumulators, and what lies between the int32 rows
 _TRACK_F64, _TRACK_I32 = ("peak", "sum", "period_mean"), ("peak_step", "first_above", "steps_above")
@@ -78,9 +84,9 @@ class _HotPath:
     # default_options.py:131-160): the in/out vectors of the canopy and soil kernels, the accumulators of the per-pixel
     # aggregates, the overland and channel router states
     STATE = tuple(dict.fromkeys(SL._CANOPY_IO + list(SL._V_IO) + PA._STATE + SR._STATE +
-                                ["OFM3Direct", "OFM3Other", "OFM3Forest"] + RT._STATE))
+                                ["OFM3Direct", "OFM3Other", "OFM3Forest"] + RT._STATE + list(SF.STATE)))
 
-    def _begin(self, scalars, land_mask, split, device, overlap_channel, report):
+    def _begin(self, scalars, land_mask, split, device, overlap_channel, report, meteo=None, members=None):
         self.device, self.split = device, bool(split)
         # overlap_channel: the channel wavefront of a step on a second HIP stream, beside the canopy / soil / overland kernels
         # of the step after it (same kernels, same results; False: one stream, as rounds 1-3).  Read at every call.
@@ -101,7 +107,52 @@ class _HotPath:
         # first use), two buffer sets (device staging, page-locked host image) and which request holds each of them
         self.land_mask = land_mask
         self._report_tables, self._report_sets, self._report_serial, self._report_count = {}, [None, None], [0, 0], 0
+        # meteo: None -- the forcing is Rain, SnowMelt, EWRef, ETRef, ESRef and isFrozenSoil stays what `values` says -- or the
+        # dict snow_frost.check_meteo describes: the forcing is Precipitation, Tavg, EWRef, ETRef, ESRef, and the snow and
+        # frost kernel (lf_snow_frost_members_device) is the first launch of every step
+        self.meteo = None if meteo is None else SF.check_meteo(meteo, self.N, members)
+        self.forcing_names = FORCING if meteo is None else METEO_FORCING
         return land_mask
+
+    def _meteo_values(self):
+        """what `meteo` adds to the per-pixel arrays of the constructor (pixel order): the statics and the two states"""
+        return {k: self.meteo[k] for k in SF.STATICS + SF.STATE}
+
+    def _meteo_block(self, pointer_of):
+        """the argument block of the snow and frost kernel: pointer_of(name) -> address of (member 0's row of) a vector"""
+        a = SF.fill_scalars(SF._SnowFrostArgs(), self.meteo, self.N)
+        for k in SF._POINTERS:
+            if k != "Snow" or self.meteo["Snow"]:
+                setattr(a, k, pointer_of(k))
+        return a
+
+    def _season(self, season):
+        """season= of step() checked: required with meteo=, refused without; sets the two scalars of the block"""
+        if self.meteo is None:
+            if season is not None:
+                raise ValueError("season= without meteo=: this object takes Rain and SnowMelt as forcing")
+            return
+        if season is None or np.shape(season) != (2,):
+            raise ValueError("step(..., season=(SnowSeasonTerm, SummerSeason)) is required with meteo= "
+                             "(snow_frost.season_terms)")
+        self.snow_frost.SnowSeasonTerm, self.snow_frost.SummerSeason = float(season[0]), float(season[1])
+
+    def _check_forcing(self, forcing):
+        """the names of a forcing dict against what an object with meteo= takes"""
+        if self.meteo is None:
+            return
+        made = [k for k in ("Rain", "SnowMelt") if k in forcing]
+        if made:
+            raise ValueError("%s in the forcing of an object with meteo=: the snow and frost kernel makes them from "
+                             "Precipitation and Tavg" % " and ".join(made))
+        missing = [k for k in self.forcing_names if k not in forcing]
+        if missing:
+            raise ValueError("forcing lacks %s" % ", ".join(missing))
+
+    def _check_state_file(self, files):
+        missing = [k for k in SF.STATE if self.meteo is not None and k not in files]
+        if missing:
+            raise ValueError("state file without %s: it was written by an object without meteo=" % " and ".join(missing))
 
     def _kept(self):
         """the optional maps that exist in this object: the reported ones plus what they are made of (the per-pixel Theta
@@ -252,7 +303,7 @@ class _HotPath:
 
     def _pinned_set(self, shape, dtype):
         """a forcing dict of page-locked host arrays that belong to this object (freed by free())"""
-        bufs = {k: PinnedArray(shape, dtype, self.device) for k in FORCING}
+        bufs = {k: PinnedArray(shape, dtype, self.device) for k in self.forcing_names}
         self._pinned.append(bufs)
         return {k: b.a for k, b in bufs.items()}
 
@@ -386,7 +437,7 @@ class _HotPath:
 
 class HotPathDevice(_HotPath):
     def __init__(self, values, scalars, land_mask, ldd_to_chan, ldd_kinematic, split=True, device=0, structures=None,
-                 compact=True, overlap_channel=True, surface_order=True, land_fused=None, report=None):
+                 compact=True, overlap_channel=True, surface_order=True, land_fused=None, report=None, meteo=None):
         """values: name -> host array in pixel order ([N], [3,N]) for every vector of the stages (reference
         attribute names); scalars: Beta, DtSec, DtRouting, NoRoutSteps, DtDay, PixelLength, MMtoM3, M3toMM,
         LeafDrainageK, AvWaterThreshold, CourantCrit, DrainedFraction, InvDtDay.  ldd_to_chan / ldd_kinematic:
@@ -396,9 +447,12 @@ class HotPathDevice(_HotPath):
         (structures.py:44-61) and the sub-step loop runs with the structures inside the wavefront.
         compact: leave inert pixels out of the channel router's domain (see inert_pixels): on real domains most land
         pixels are not channel pixels, and the channel wavefront then touches only the ones that are."""
-        # overlap_channel, report: see _HotPath._begin
-        land_mask = self._begin(scalars, land_mask, split, device, overlap_channel, report)
+        # overlap_channel, report, meteo: see _HotPath._begin
+        land_mask = self._begin(scalars, land_mask, split, device, overlap_channel, report, meteo)
         N, sc = self.N, self.sc
+        if self.meteo is not None:
+            values = dict(values, **self._meteo_values())
+            values.setdefault("isFrozenSoil", np.zeros(N, bool))
         # surface_order: every per-pixel vector that is not a channel vector lives in the sweep order of the OVERLAND
         # routers' graph (the canopy / soil / aggregate kernels are element-wise and do not care; the three overland routers
         # then stream their vectors instead of going through the position -> pixel table: lf_surface_step_ordered).
@@ -448,9 +502,9 @@ class HotPathDevice(_HotPath):
             return self.d[name]
         # forcing: two buffer sets, so that the upload of the next step's vectors (second HIP stream) overlaps the
         # kernels of the current step -- see prefetch()
-        self.force = [{k: DeviceArray(N, np.float64, device).zero() for k in FORCING} for _ in range(2)]
+        self.force = [{k: DeviceArray(N, np.float64, device).zero() for k in self.forcing_names} for _ in range(2)]
         self._prefetched, self._keep = [None, None], [None, None]
-        for k in FORCING:
+        for k in self.forcing_names:
             self.d[k] = self.force[0][k]
         # ---- argument blocks (pointers into self.d) -----------------------------------------------------
         def fill(args, names, shape_of):
@@ -488,6 +542,10 @@ class HotPathDevice(_HotPath):
             vec.allocate(["SideflowChanM3"] + RT._OUT + ["scratch0", "scratch1"])
             self.d.update(vec.dev)
         self.rout = vec.args
+        if self.meteo is not None:  # Rain and SnowMelt exist once (made above, by the blocks that read them), written by the kernel
+            for k in ["SnowCover"] + (["Snow"] if self.meteo["Snow"] else []):
+                zeros(k, N)
+            self.snow_frost = self._meteo_block(lambda k: self.d[k].ptr.value)
 
     def _lai_vectors(self):
         return self.d
@@ -511,9 +569,10 @@ class HotPathDevice(_HotPath):
         what widening them on the host first would give, at half the PCIe traffic"""
         L, dev = lib(), self.device
         as_is = lambda a: np.ascontiguousarray(a) if np.asarray(a).dtype == np.float32 else f64(a)
-        host = [as_is(forcing[k]) if ordered else as_is(self._ordered(forcing[k])) for k in FORCING]
+        self._check_forcing(forcing)
+        host = [as_is(forcing[k]) if ordered else as_is(self._ordered(forcing[k])) for k in self.forcing_names]
         check(L.lf_upload_begin(dev, b))
-        for k, a in zip(FORCING, host):
+        for k, a in zip(self.forcing_names, host):
             if a.size != self.N:
                 raise ValueError("forcing vector %s must have %d entries" % (k, self.N))
             if a.dtype == np.float32:
@@ -541,9 +600,9 @@ class HotPathDevice(_HotPath):
         self._prefetched[b] = forcing
 
     def _use_set(self, b):
-        for k in FORCING:
+        for k in self.forcing_names:
             self.d[k] = self.force[b][k]
-            for st in (self.canopy, self.soil, self.pixel, self.surface):
+            for st in (self.canopy, self.soil, self.pixel, self.surface) + (() if self.meteo is None else (self.snow_frost,)):
                 if hasattr(type(st), k):
                     setattr(st, k, self.force[b][k].ptr.value)
 
@@ -564,7 +623,11 @@ class HotPathDevice(_HotPath):
             self._side_end(side)
         self._qin_old = q
 
-    def step(self, forcing, time_since_start=None, QInM3=None, ordered=False):
+    def step(self, forcing, time_since_start=None, QInM3=None, ordered=False, season=None):
+        """With meteo=: forcing holds Precipitation, Tavg, EWRef, ETRef, ESRef, and season=(SnowSeasonTerm, SummerSeason)
+        of the step is required (snow_frost.season_terms); step(None, season=...) takes the meteo its buffer set holds, as
+        without meteo=, and still advances the snow pack and the frost index."""
+        self._season(season)
         if QInM3 is not None:
             self.set_inflow(QInM3)
         self._step(forcing, time_since_start, ordered)
@@ -603,6 +666,9 @@ class HotPathDevice(_HotPath):
                 if stage_ms is not None and exc[0] is None:
                     stage_ms[self.name] = stage_ms.get(self.name, 0.0) + timer_stop(dev)
                 return False
+        if self.meteo is not None:         # snow.dynamic, frost.dynamic: Rain, SnowMelt, isFrozenSoil of this step
+            with stage("snow_frost"):
+                check(L.lf_snow_frost_members_device(dev, C.byref(self.snow_frost), 1, 3 * self.N, self.N, 0))
         if self.land_fused:
             # canopy, ESMax and the soil columns in ONE pass (k_soil_fused<.., CANOPY>): the lane that runs a column's canopy
             # carries LeafDrainage / Interception / W1a / W1b / W1 / ESMax into its soil water balance in registers
@@ -649,8 +715,9 @@ class HotPathDevice(_HotPath):
         finally:
             self._side_end(side)
 
-    def step_profile(self, forcing, time_since_start=None, ordered=False):
+    def step_profile(self, forcing, time_since_start=None, ordered=False, season=None):
         """step() with every stage timed on its own (synchronising; no overlap between the stages) -> {stage: ms}"""
+        self._season(season)
         ms = {}
         self._step(forcing, time_since_start, ordered, ms)
         return ms
@@ -683,6 +750,8 @@ class HotPathDevice(_HotPath):
             out.pop("canopy"); out.pop("soil_columns")
         else:
             out.pop("land_surface")
+        if self.meteo is not None:         # 48 B read and 57 B (65 with Snow) written per pixel, 24 B of statics
+            out["snow_frost"] = N * (48 + 24 + (65 if self.meteo["Snow"] else 57))
         return out
 
     def download(self, name):
@@ -718,7 +787,7 @@ class HotPathDevice(_HotPath):
                 d, divisor, channel = self.d["sumDisDay"], float(self.sc["NoRoutSteps"]), True
             else:
                 d, divisor, channel = self.d.get(name), 1.0, name in self._CHANNEL_ROWS
-                if d is None or name in FORCING or d.dtype != np.float64 or not (channel or d.shape == (self.N,)):
+                if d is None or name in self.forcing_names or d.dtype != np.float64 or not (channel or d.shape == (self.N,)):
                     raise ValueError("%s is neither a channel vector, ChanQAvg nor an [N] fp64 vector of the land part" % name)
             groups["channel" if channel else "land"].append((name, d, 1, 0, divisor, False))
         return self._report_rasters(list(groups.items()), dtype, fill, side=not groups["land"])
@@ -739,6 +808,7 @@ class HotPathDevice(_HotPath):
 
     def load_state(self, path):
         z = np.load(path)
+        self._check_state_file(z.files)
         for k in self.state_names():
             if k not in z.files and k in OPTIONAL_MAPS:
                 continue                              # a state file written by an object that did not report this map
@@ -976,11 +1046,20 @@ class HotPathEnsemble(_HotPath):
     [N] forcing 12.59 / 46.87 / 139.23 ms, with coefficients 12.72 / 46.66 / 139.66 ms (the two kernels take 0.15 / 0.32 /
     0.65 ms, 0.80 - 0.94 of the copy ceiling at 8 (rank + 1 + members) bytes per element), from host-made [members, N]
     rows 12.67 / 47.17 / 141.54 ms plus 222 / 854 / 2523 ms of numpy per step to make them.
+    With meteo= (the dict snow_frost.check_meteo describes: three statics, seven scalars, initial SnowCoverS [3, N] or
+    [members, 3, N] and FrostIndex [N] or [members, N]; "Snow": True for the Snow row as well) the forcing is Precipitation,
+    Tavg, EWRef, ETRef, ESRef -- what a forecast ensemble differs in, so forcing_perturbation("Tavg", ..., multiplicative=False,
+    lower=-inf) and ("Precipitation", ...) act where the spread is -- and step(..., season=(SnowSeasonTerm, SummerSeason)) is
+    required.  lf_snow_frost_members_device is then the first launch of the step, ahead of the land surface: one kernel for all
+    members writes their Rain, SnowMelt and isFrozenSoil rows (which exist once, not per buffer set; frozen soil is per member)
+    and advances SnowCoverS and FrostIndex, which are state -- state_names(), analysis_names(), state files, set_member_state,
+    download -- while SnowCover (and Snow) are [N] land rows for summary / rasters / sample / track_begin.  Without meteo=
+    nothing of this exists: not an allocation, not a launch, not a name.
     Not in this class (HotPathDevice has them): step_profile, state_maps / load_state_maps and mass_balance."""
 
     def __init__(self, values, scalars, land_mask, ldd_to_chan, ldd_kinematic, members, split=True, device=0, structures=None,
-                 compact=True, overlap_channel=True, report=None, pad=0):
-        land_mask = self._begin(scalars, land_mask, split, device, overlap_channel, report)
+                 compact=True, overlap_channel=True, report=None, pad=0, meteo=None):
+        land_mask = self._begin(scalars, land_mask, split, device, overlap_channel, report, meteo, int(members))
         M = self.members = int(members)
         self._gap = 0.0                      # what lies between the members' rows of the channel part (set_gaps)
         N, sc = self.N, self.sc
@@ -990,6 +1069,8 @@ class HotPathEnsemble(_HotPath):
         self._overland(values, ldd_to_chan, land_mask)
         # ---- land surface: the member rows and shared statics of LandSurfaceEnsemble -------------------------------------
         d = {k: self._ordered(a) for k, a in values.items() if k not in chan_names}
+        if self.meteo is not None:
+            d.update({k: self._ordered(a) for k, a in self._meteo_values().items()})
         d.update(sc)
         E = self.land = SL.LandSurfaceEnsemble(d, M, device, pad)
         for k in list(E._member):
@@ -1028,6 +1109,19 @@ class HotPathEnsemble(_HotPath):
         for k in SR._V_IN + SR._N_IN + SR._STATE + SR._OUT + ["SurfaceRunSoil", "scratch"]:
             setattr(f, k, E.dev[k].ptr.value)
         self._finish_args(p, f)
+        # ---- snow and frost: the kernel writes the member rows of Rain, SnowMelt and isFrozenSoil, which therefore differ from
+        # member to member whatever the forcing -- the land surface and the aggregates always get the member forcing stride --
+        # and Precipitation and Tavg are forcing rows like EWRef
+        if self.meteo is not None:
+            statics(SF.STATICS)
+            rows(["SnowCoverS"], E._member, (3, N))
+            rows(["FrostIndex", "SnowCover"] + (["Snow"] if self.meteo["Snow"] else []), E._pixel, N)
+            for k in SF.METEO:
+                E._forcing.append(k)
+                E._put(k, np.zeros(N))
+            for k in ("Rain", "SnowMelt", "isFrozenSoil"):
+                E._shared_forcing[k] = False
+            self.snow_frost = self._meteo_block(lambda k: E.dev[k].ptr.value)
         # ---- channel domain and channel part; the members' channel rows ---------------------------------------------------
         v, structures = self._channel(values, ldd_kinematic, land_mask, structures, compact)
         m, Nk = self.rmod, self.Nk
@@ -1049,9 +1143,9 @@ class HotPathEnsemble(_HotPath):
                     self._put_qin(k, np.broadcast_to(m._down(m._st["dev"][k].download()), (M, Nk)))
                     setattr(a, k, self._qin[k].ptr.value)
         # ---- forcing: two sets of member rows; set 0 is the land surface's own vectors (see prefetch) -------------------
-        self.force = [{k: E.dev[k] for k in FORCING},
-                      {k: DeviceArray(M * self.pstride, np.float64, device).zero() for k in FORCING}]
-        self._shared = [{k: E._shared_forcing[k] for k in FORCING}, {k: True for k in FORCING}]
+        self.force = [{k: E.dev[k] for k in self.forcing_names},
+                      {k: DeviceArray(M * self.pstride, np.float64, device).zero() for k in self.forcing_names}]
+        self._shared = [{k: E._shared_forcing[k] for k in self.forcing_names}, {k: True for k in self.forcing_names}]
         self._cur, self._prefetched, self._prefetched_coefficients, self._keep = 0, None, None, [None, None]
         # forcing_perturbation(): name -> (patterns on the device in sweep order, rank, multiplicative, lower, upper)
         self._perturbations = {}
@@ -1099,15 +1193,16 @@ class HotPathEnsemble(_HotPath):
         up as always and are perturbed where they lie.  Either way the rows differ from then on (_shared)."""
         L, dev, M, N = lib(), self.device, self.members, self.N
         coeff = self._forcing_coefficients(coefficients)
+        self._check_forcing(forcing)
         host = []
-        for k in FORCING:
+        for k in self.forcing_names:
             a = np.asarray(forcing[k])
             if a.shape not in ((N,), (M, N)):
                 raise ValueError("forcing vector %s must be [%d] or [%d, %d]" % (k, N, M, N))
             host.append(np.ascontiguousarray(a) if a.dtype == np.float32 else f64(a))
         check(L.lf_upload_begin(dev, b))
         try:
-            for k, a in zip(FORCING, host):
+            for k, a in zip(self.forcing_names, host):
                 c, rows = coeff.get(k), self.force[b][k].ptr
                 check(L.lf_upload_rows(dev, rows, self.pstride, 1 if c is not None and a.ndim == 1 else M,
                                        a.ctypes.data_as(C.c_void_p), 1 if a.ndim == 1 else M, 1 if a.dtype == np.float32 else 0,
@@ -1132,8 +1227,8 @@ class HotPathEnsemble(_HotPath):
         assimilation.fourier_patterns(); gathered to sweep order and uploaded here, once, with a blocking copy (the copy
         stream reads them, and nothing orders it behind the main stream but the host).  patterns=None removes the
         registration.  Only the [members, rank] table crosses PCIe per step (lf_upload_perturb_rows)."""
-        if name not in FORCING:
-            raise ValueError("%s is no forcing vector (%s)" % (name, ", ".join(FORCING)))
+        if name not in self.forcing_names:
+            raise ValueError("%s is no forcing vector (%s)" % (name, ", ".join(self.forcing_names)))
         if self.members > 128:
             raise ValueError("a forcing perturbation takes at most 128 members (%d)" % self.members)
         new = None
@@ -1173,9 +1268,9 @@ class HotPathEnsemble(_HotPath):
     def _use_set(self, b):
         """point the argument blocks of the stages that read forcing, and the land surface's own table, at set b"""
         E = self.land
-        for k in FORCING:
+        for k in self.forcing_names:
             E.dev[k] = self.force[b][k]
-            for st in (E.canopy, E.soil, self.pixel):
+            for st in (E.canopy, E.soil, self.pixel) + (() if self.meteo is None else (self.snow_frost,)):
                 if hasattr(type(st), k):
                     setattr(st, k, self.force[b][k].ptr.value)
         E._shared_forcing.update(self._shared[b])
@@ -1201,11 +1296,16 @@ class HotPathEnsemble(_HotPath):
         self._upload(1 - self._cur, forcing, coefficients)
         self._prefetched, self._prefetched_coefficients = forcing, coefficients
 
-    def step(self, forcing, time_since_start=None, QInM3=None, coefficients=None):
+    def step(self, forcing, time_since_start=None, QInM3=None, coefficients=None, season=None):
         """forcing: dict of Rain, SnowMelt, EWRef, ETRef, ESRef, each [N] (every member) or [members, N], pixel order,
         float32 or float64 -- or None: the forcing rows of the step before (no PCIe traffic); QInM3 (structures= with inflow
         hydrographs): [N] or [members, N]; coefficients: None or forcing name -> [members, rank] float64 for vectors with a
-        forcing_perturbation(), whose member rows are then perturbed on the device behind their upload"""
+        forcing_perturbation(), whose member rows are then perturbed on the device behind their upload.
+        With meteo=: Precipitation and Tavg take the place of Rain and SnowMelt, season=(SnowSeasonTerm, SummerSeason) of
+        the step is required (snow_frost.season_terms), and lf_snow_frost_members_device is the first launch of the step,
+        ahead of the land surface: it makes every member's Rain, SnowMelt and isFrozenSoil rows and advances SnowCoverS and
+        FrostIndex; step(None, season=...) repeats the meteo of the step before and still advances them."""
+        self._season(season)
         if forcing is None and coefficients is not None:
             raise ValueError("coefficients without forcing: the rows on the device are perturbed already")
         if forcing is not None and self._prefetched is forcing and coefficients is not None \
@@ -1225,6 +1325,10 @@ class HotPathEnsemble(_HotPath):
         b = self._cur
         check(L.lf_compute_acquire(dev, b))
         try:
+            if self.meteo is not None:            # snow.dynamic, frost.dynamic (Precipitation and Tavg: one row for all, or rows)
+                one = self._shared[b]["Precipitation"] and self._shared[b]["Tavg"]
+                check(L.lf_snow_frost_members_device(dev, C.byref(self.snow_frost), M, self.stride, self.pstride,
+                                                     0 if one else self.pstride))
             E.step()                                                                                        # dyn.py:114-123
             self.steps_done += 1
             self.pixel.TimeSinceStart = float(time_since_start if time_since_start else self.steps_done)
@@ -1927,6 +2031,7 @@ class HotPathEnsemble(_HotPath):
 
     def load_state(self, path):
         z = np.load(path)
+        self._check_state_file(z.files)
         for k in self.state_names():
             if k not in z.files and k in OPTIONAL_MAPS:
                 continue
