@@ -346,6 +346,42 @@ int lf_members_transform_device(int device, double *rows_dev, int members, int64
                                 const double *lower_dev, double lower, const double *upper_dev, double upper);
 int lf_members_resample_device(int device, double *rows_dev, int members, int64_t stride, int64_t n,
                                const int32_t *parents_host);
+/* The localised serial analysis (the two-step ensemble filter of Anderson 2003 / Whitaker & Hamill 2002 with Gaspari-Cohn
+ * localisation): the observation-space increments of ALL gauges regressed onto every element in ONE pass, IN PLACE on
+ * `members` (2 .. 64) rows of n doubles, `stride` elements apart, as lf_members_transform_device takes them.  cx_dev, cy_dev:
+ * [n] doubles, the coordinates of the elements.  table_dev: gauges * (2 * members + 5) doubles in device memory, G = gauges
+ * (1 .. 256), M = members, in sections
+ *   A[G][M] anomalies | D[G][M] increments | s[G] = 1 / sum_k A[j][k]^2 | gx[G] | gy[G] gauge coordinates |
+ *   c[G] half-width, > 0 | cut2[G] = (2.0 * c) * (2.0 * c)
+ * which the host makes in observation space (lisflood_amd.assimilation.serial_increments).  With x[k] = rows_dev[k * stride + i],
+ * for every element i the gauges are taken in ascending j, each on the column as the gauges before it left it:
+ *   dx = cx[i] - gx[j];  dy = cy[i] - gy[j];  d2 = dx * dx + dy * dy
+ *   if !(d2 < cut2[j]): the gauge leaves the element alone (every member keeps its bits)
+ *   z = sqrt(d2) / c[j]                                                        (IEEE square root and division)
+ *   z <= 1:  p = -0.25 * z + 0.5;  p = p * z + 0.625;  p = p * z - C53;  p = p * z;  rho = p * z + 1.0
+ *   else:    q = C112 * z - 0.5;  q = q * z + 0.625;  q = q * z + C53;  q = q * z - 5.0;  q = q * z + 4.0;  rho = q - C23 / z
+ *            with the double constants C53 = 5.0 / 3.0, C112 = 1.0 / 12.0, C23 = 2.0 / 3.0
+ *   if !(rho > 0): the gauge leaves the element alone (rho reaches about -3e-16 just below z = 2; a NaN coordinate, whose
+ *            d2 is no less than anything, has left at the first test)
+ *   cov = x[0] * A[j][0];  for k = 1 .. M - 1:  cov = cov + x[k] * A[j][k]     (one multiply, one add, ascending k; never fused)
+ *   g = rho * (cov * s[j])
+ *   for k = 0 .. M - 1:  x[k] = x[k] + g * D[j][k]
+ * and after the last gauge the bound lines of lf_members_transform_device (lower, then upper) and the store.  The covariance
+ * is taken WITHOUT centring x: sum_k x[k] A[j][k] equals sum_k (x[k] - mean) A[j][k] only because the host's anomalies sum
+ * to zero to rounding, which is the caller's to keep.  Bounds apply to every element, touched by a gauge or not; a call
+ * without bounds (both rows NULL, lower = -inf, upper = +inf) stores nothing to an element that no gauge touched, so -0.0
+ * and every NaN payload stay there.  Elements n .. stride - 1 are neither read nor written; the table is only read.  A lane
+ * owns its element's whole column, which stays on chip from the load to the store (in registers up to 16 members; beyond
+ * that in LDS, 256 lanes per workgroup up to 32 members, 128 up to 64); the table is read through the scalar cache, and a gauge with no lane of a wavefront in range costs that
+ * wavefront one distance and one vote.  Asynchronous on the stream the library calls currently go to; no allocation, no
+ * synchronisation, no atomics, no scratch.  16 members + 16 bytes per element at most, about 4 members + 40 fp64 operations
+ * per element and gauge in range (measured: profiles/members_regress.json).
+ * LF_E_INVALID, with the argument named, before a device is touched: members outside 2 .. 64, gauges outside 1 .. 256, n < 0
+ * or beyond the 32-bit range of a launch, stride < n, rows_dev, cx_dev, cy_dev or table_dev NULL with n > 0, lower > upper
+ * where both are scalars.  n == 0: LF_OK, nothing is launched. */
+int lf_members_regress_device(int device, double *rows_dev, int members, int64_t stride, int64_t n, int gauges,
+                              const double *cx_dev, const double *cy_dev, const double *table_dev,
+                              const double *lower_dev, double lower, const double *upper_dev, double upper);
 /* The forecast half of the cycle: what makes the members differ.  Member rows (forcing, or state as model error / jitter)
  * perturbed from `rank` static spatial patterns on the device and a [members][rank] table of coefficients from the host --
  * only the table crosses PCIe.  For every element i < n and member m < members

@@ -1,6 +1,23 @@
 """Host side of an assimilation cycle on a HotPathEnsemble: what is computed from the members at the gauges
 (ens.sample(), [members, gauges] -- a few KB) and handed to ens.transform() / ens.resample(), which rewrite the state on
-the device.  numpy only; members are rows throughout, as the ensemble holds them."""
+the device.  numpy only; members are rows throughout, as the ensemble holds them.
+
+A cycle of the localised serial filter (serial_increments() + ens.regress(): every gauge corrects the pixels near it, all
+gauges in one pass over the state), with model error as the forecast half:
+
+    P = fourier_patterns(land_mask, 8, 30.0, rng)           # once: [8, N] patterns for the model error
+    c = ar1_coefficients(None, (members, 8), 0.02, rng)
+    ens.step(forcing)                                        # forecast
+    hx = ens.sample("ChanQ", gauge_pixels)                   # [members, G]: the members at the gauges, a few KB
+    inc = serial_increments(hx, obs, obs_var, gauge_rc, halfwidth=25.0)          # gauge_rc [G, 2]: (row, column) of the gauges
+    ens.regress(inc, bounds={"W1a": (0.0, None), "ChanQ": (0.0, None)})          # analysis: inc.table goes up, nothing else
+    c = ar1_coefficients(c, 0.9, 0.02, rng)
+    ens.perturb(c, P, ["W1a", "W1b"], multiplicative=True)   # model error, so that the spread does not collapse
+    ens.step(forcing)                                        # the next forecast sees the analysed state
+
+inc.dropped lists the gauges that had no spread at their turn, inc.posterior is the analysed ensemble at the gauges.
+kind="perturbed" with perturbed_obs=obs + sqrt(obs_var) N(0, 1) gives the stochastic filter instead of the square-root
+one; coords=(X, Y) in regress() and the same coordinates in gauge_rc put the distances on any other two-coordinate map."""
 import numpy as np
 
 
@@ -32,6 +49,144 @@ def enkf_weights(hx, obs, obs_var, perturbed_obs=None):
     S = np.linalg.solve(Cm, (Y - hx).T)                   # [G, members]
     centre = np.eye(M) - np.full((M, M), 1.0 / M)
     return np.eye(M) + centre @ (A @ S)
+
+
+_C53, _C112, _C23 = 5.0 / 3.0, 1.0 / 12.0, 2.0 / 3.0
+
+
+def _gc_horner(z):
+    """both branches of Gaspari & Cohn's function in the Horner form of lf_members_regress_device, chosen by z <= 1"""
+    with np.errstate(all="ignore"):
+        p = -0.25 * z + 0.5
+        p = p * z + 0.625
+        p = p * z - _C53
+        p = p * z
+        p = p * z + 1.0
+        q = _C112 * z - 0.5
+        q = q * z + 0.625
+        q = q * z + _C53
+        q = q * z - 5.0
+        q = q * z + 4.0
+        q = q - _C23 / z
+    return np.where(z <= 1.0, p, q)
+
+
+def gaspari_cohn(z):
+    """Gaspari & Cohn's (1999, eq. 4.10) compactly supported fifth-order correlation function of z = distance / half-width:
+    1 at z = 0, 5/24 at z = 1, 0 from z = 2 on -- in the Horner form the device evaluates (include/lisflood_amd.h).  The form
+    dips to about -3e-16 just below z = 2; what is not above 0 there, z >= 2 and a NaN give 0."""
+    z = np.asarray(z, np.float64)
+    rho = _gc_horner(z)
+    return np.where((z < 2.0) & (rho > 0.0), rho, 0.0)
+
+
+def localisation(dx, dy, halfwidth, cut2):
+    """the weight lf_members_regress_device gives a gauge at the offset (dx, dy) -- its two tests included: 0 where
+    !(dx dx + dy dy < cut2) and where the Horner form is not above 0"""
+    dx, dy = np.asarray(dx, np.float64), np.asarray(dy, np.float64)
+    with np.errstate(all="ignore"):
+        d2 = dx * dx + dy * dy
+        inside = d2 < cut2
+        rho = _gc_horner(np.sqrt(d2) / halfwidth)
+    return np.where(inside & (rho > 0.0), rho, 0.0)
+
+
+class SerialIncrements:
+    """What serial_increments() hands to HotPathEnsemble.regress(): the sections of lf_members_regress_device's table for
+    the gauges that were kept, in the order they were processed.
+    anomalies, increments [K, members]; scale, gx, gy, halfwidth, cut2 [K];  kept: the K indices into the caller's gauges,
+    dropped: the others (no spread at their turn);  posterior [members, G]: the members at ALL gauges after the last
+    update (a dropped gauge is still moved by the others);  table: the whole table, one contiguous float64 array."""
+
+    def __init__(self, anomalies, increments, scale, gx, gy, halfwidth, kept, dropped, posterior):
+        self.anomalies, self.increments, self.scale = anomalies, increments, scale
+        self.gx, self.gy, self.halfwidth = gx, gy, halfwidth
+        self.cut2 = (2.0 * halfwidth) * (2.0 * halfwidth)
+        self.kept, self.dropped, self.posterior = kept, dropped, posterior
+        self.members, self.gauges = anomalies.shape[1], anomalies.shape[0]
+        self.table = self.chunk(0, self.gauges)
+
+    def chunk(self, first, last):
+        """the table of the gauges first .. last - 1 alone: (last - first) (2 members + 5) doubles"""
+        k = slice(first, last)
+        return np.concatenate([self.anomalies[k].reshape(-1), self.increments[k].reshape(-1), self.scale[k], self.gx[k],
+                               self.gy[k], self.halfwidth[k], self.cut2[k]])
+
+
+def serial_increments(hx, obs, obs_var, gauge_xy, halfwidth, kind="eakf", perturbed_obs=None):
+    """The observation-space half of the two-step serial ensemble filter (Anderson 2003; Whitaker & Hamill 2002) with
+    Gaspari-Cohn localisation: the gauges are processed one after the other, in ascending order, and for each one the
+    anomalies of its CURRENT prior (as the gauges before it left it) and the increments of the members are noted down --
+    HotPathEnsemble.regress() then regresses all of them onto the state in one pass over it.
+
+    hx [members, G]: the members at the gauges (ens.sample());  obs, obs_var [G]: observations and their error variances
+    (> 0);  gauge_xy [G, 2]: the gauges' coordinates, in the coordinates regress() is given (by default the pixel's row and
+    column);  halfwidth: the localisation half-width c, a scalar or [G], > 0 -- the weight is gaspari_cohn(distance / c),
+    zero from 2 c on.  For gauge j with prior y, mean ym, a = y - ym, ss = sum a^2, var = ss / (M - 1), r = obs_var[j]:
+        kind "eakf":       pv = 1 / (1 / var + 1 / r);  pm = pv (ym / var + obs / r);  d = (pm - ym) + (sqrt(pv / var) - 1) a
+        kind "perturbed":  d = var / (var + r) (perturbed_obs[:, j] - y)          (perturbed_obs [members, G], required)
+    and every OTHER gauge l moves as the state element at its place does:  y_l += rho (sum_k y_l[k] a[k] / ss) d  with rho
+    the localisation weight of the distance between the two gauges -- a later gauge's prior, an earlier one's posterior,
+    so that .posterior is the state's own posterior at the gauges.  The sum is taken without centring y_l, as on the
+    device: a sums to zero to rounding.  A gauge whose ss is 0 at its turn (every member equal) says nothing about
+    the state: it is dropped from the table and listed in .dropped.  -> SerialIncrements."""
+    hx = np.asarray(hx, np.float64)
+    if hx.ndim != 2:
+        raise ValueError("hx must be [members, gauges]")
+    M, G = hx.shape
+    if M < 2:
+        raise ValueError("an ensemble covariance needs at least 2 members")
+    obs, obs_var = np.asarray(obs, np.float64), np.asarray(obs_var, np.float64)
+    if obs.shape != (G,) or obs_var.shape != (G,):
+        raise ValueError("obs and obs_var must be [%d]" % G)
+    if not np.all(obs_var > 0):
+        raise ValueError("obs_var must be above 0")
+    xy = np.asarray(gauge_xy, np.float64)
+    if xy.shape != (G, 2):
+        raise ValueError("gauge_xy must be [%d, 2]" % G)
+    c = np.asarray(halfwidth, np.float64)
+    if c.ndim == 0:
+        c = np.full(G, float(c))
+    if c.shape != (G,) or not np.all(c > 0):
+        raise ValueError("halfwidth must be a scalar or [%d], above 0" % G)
+    if kind not in ("eakf", "perturbed"):
+        raise ValueError("kind must be \"eakf\" or \"perturbed\"")
+    if kind == "perturbed":
+        if perturbed_obs is None or np.shape(perturbed_obs) != (M, G):
+            raise ValueError("kind \"perturbed\" takes perturbed_obs [%d, %d]" % (M, G))
+        Y = np.asarray(perturbed_obs, np.float64)
+    cut2 = (2.0 * c) * (2.0 * c)
+    y = hx.copy()
+    kept, dropped, anomalies, increments, scale = [], [], [], [], []
+    for j in range(G):
+        yj = y[:, j].copy()
+        ym = yj.mean()
+        a = yj - ym
+        ss = float((a * a).sum())
+        if ss == 0.0:
+            dropped.append(j)
+            continue
+        var, r = ss / (M - 1), obs_var[j]
+        if kind == "eakf":
+            pv = 1.0 / (1.0 / var + 1.0 / r)
+            pm = pv * (ym / var + obs[j] / r)
+            d = (pm - ym) + (np.sqrt(pv / var) - 1.0) * a
+        else:
+            d = var / (var + r) * (Y[:, j] - yj)
+        s = 1.0 / ss
+        # every other gauge moves as the state element at its place does: the later ones' priors, the earlier ones' posteriors
+        rho = localisation(xy[:, 0] - xy[j, 0], xy[:, 1] - xy[j, 1], c[j], cut2[j])
+        g = rho * ((a @ y) * s)
+        y += d[:, None] * g[None, :]
+        y[:, j] = yj + d                                      # (the gauge itself: rho = 1 and sum a a / ss = 1)
+        kept.append(j)
+        anomalies.append(a)
+        increments.append(d)
+        scale.append(s)
+    K = np.asarray(kept, np.int64)
+    return SerialIncrements(np.array(anomalies, np.float64).reshape(len(kept), M), np.array(increments, np.float64).reshape(len(kept), M),
+                            np.asarray(scale, np.float64), xy[K, 0].copy(), xy[K, 1].copy(), c[K].copy(), K,
+                            np.asarray(dropped, np.int64), y)
 
 
 def systematic_parents(weights, u):

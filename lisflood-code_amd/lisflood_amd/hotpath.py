@@ -1162,6 +1162,8 @@ class HotPathEnsemble(_HotPath):
         # transform(): the weight table on the device ([array object it holds, device table], made on first use), the taper /
         # bound rows on the device by the array object they were made from, and the keys the call in hand uses
         self._weights, self._analysis_cache, self._analysis_pinned = None, {}, set()
+        # regress(): the resident table of 256 gauges (made on first use) and the default coordinates (made once)
+        self._regress_table, self._regress_coords = None, None
 
     def _lai_vectors(self):
         return self.land.dev
@@ -1919,6 +1921,73 @@ class HotPathEnsemble(_HotPath):
         finally:
             self._analysis_pinned = set()
 
+    _REGRESS_GAUGES = 256  # gauges of one lf_members_regress_device call: what the resident table is sized for
+
+    def regress(self, increments, names=None, coords=None, bounds=None):
+        """The localised serial analysis on the device (the two-step filter of Anderson 2003 with Gaspari-Cohn localisation):
+        the observation-space increments of ALL gauges -- `increments`, what assimilation.serial_increments() made of
+        sample() at the gauges -- regressed onto every element of every state vector in ONE pass over the state, each gauge
+        weighted by gaspari_cohn(distance to the gauge / its half-width) computed on the device from coordinates, in place
+        on the member rows as they lie (lf_members_regress_device, whose header entry states the arithmetic: one call per
+        row set, a [3, N] vector three).  The same analysis through transform() is one pass and one [N] taper map per gauge.
+        Only the table of increments.gauges (2 members + 5) doubles crosses PCIe, through a page-locked slot into one
+        resident buffer made on first use for 256 gauges.  The page-locked slots are the device's ring of eight, shared with
+        every other staged upload, and a slot grows the first time it meets a table larger than itself: the first eight or so
+        calls, or a later call with more gauges than any before, may each allocate page-locked memory once; after that
+        nothing is allocated from cycle to cycle.  More than 256 gauges
+        go in several calls, in order: the filter is serial, so that is the same arithmetic.  2 to 64 members.
+        names, bounds, what stays untouched and the ordering (joins the side stream, enqueues, no host synchronisation):
+        as transform().  Without bounds an element beyond every gauge's reach (twice the half-width) keeps its bits.
+        coords: None or (X, Y), two [N] float64 arrays in pixel order, the coordinates the distances are taken in -- the
+        gauges' in `increments` are in the same.  None: the pixel's (row, column) on the land mask, made once and kept.
+        They go to the device once per array object and row order, like taper and bound rows: pass the SAME arrays every
+        cycle.  A site row takes its pixel's coordinates.  No gauge kept in `increments`: nothing is launched."""
+        M, N = self.members, self.N
+        if not 2 <= M <= 64:
+            raise ValueError("regress() takes 2 to 64 members (%d)" % M)
+        sections = ("anomalies", "increments", "scale", "gx", "gy", "halfwidth", "cut2", "gauges", "members", "chunk")
+        if not all(hasattr(increments, k) for k in sections):
+            raise ValueError("increments must be what assimilation.serial_increments() returns")
+        if increments.members != M:
+            raise ValueError("increments are of %d members, the ensemble has %d" % (increments.members, M))
+        if coords is None:
+            if self._regress_coords is None:
+                rows, cols = np.nonzero(self.land_mask)
+                self._regress_coords = (rows.astype(np.float64), cols.astype(np.float64))
+            coords = self._regress_coords
+        if not (isinstance(coords, (tuple, list)) and len(coords) == 2
+                and all(isinstance(a, np.ndarray) and a.dtype == np.float64 and a.shape == (N,) for a in coords)):
+            raise ValueError("coords must be None or (X, Y), two float64 arrays of shape [%d] in pixel order" % N)
+        names = self._analysis_names(names)
+        bounds = self._analysis_bounds(names, bounds)
+        G = int(increments.gauges)
+        if G == 0:
+            return
+        calls = []
+        self._analysis_pinned = set()
+        try:
+            for name in names:
+                lower, upper = bounds.get(name, (None, None))
+                for base, n, stride, order, v in self._analysis_rows(name):
+                    arg = lambda b, inf: (None, inf) if b is None else (None, b) if isinstance(b, float) \
+                        else (self._pixel_rows(b, order, v).ptr, 0.0)
+                    if n:
+                        calls.append((base, stride, n, self._pixel_rows(coords[0], order).ptr, self._pixel_rows(coords[1], order).ptr)
+                                     + arg(lower, -np.inf) + arg(upper, np.inf))
+            L, dev = lib(), self.device
+            check(L.lf_side_stream_join(dev))
+            if self._regress_table is None:
+                self._regress_table = DeviceArray(self._REGRESS_GAUGES * (2 * M + 5), np.float64, dev)
+            t = self._regress_table
+            for first in range(0, G, self._REGRESS_GAUGES):
+                last = min(first + self._REGRESS_GAUGES, G)
+                # in order on the stream behind the kernels of the chunk before, which read the table it overwrites
+                t.upload(increments.table if (first, last) == (0, G) else increments.chunk(first, last), staged=True, prefix=True)
+                for base, stride, n, cx, cy, lo_dev, lo, hi_dev, hi in calls:
+                    check(L.lf_members_regress_device(dev, base, M, stride, n, last - first, cx, cy, t.ptr, lo_dev, lo, hi_dev, hi))
+        finally:
+            self._analysis_pinned = set()
+
     def perturb(self, coefficients, patterns, names, multiplicative=False, bounds=None):
         """Model error or jitter on the device: for every element i of the state vectors `names`, in place on the member
         rows as they lie,  x[m, i] = x[m, i] + sum_r coefficients[m, r] patterns[r, i]  (multiplicative: x[m, i] * (1 + sum)),
@@ -2052,6 +2121,8 @@ class HotPathEnsemble(_HotPath):
         products = [d for cache in (self._thresholds, self._gauges, self._analysis_cache) for hit in cache.values()
                     for d in hit if isinstance(d, DeviceArray)] + list(self._products.values()) + [self._gpix_dev]
         products += [self._weights[1]] if self._weights else []
+        products += [self._regress_table] if self._regress_table else []
+        self._regress_table = None
         products += [d for t in self._trackers.values() for d in list(t.dev.values()) + [t.thr]]
         products += [p[0] for p in self._perturbations.values()]
         self._perturbations = {}
