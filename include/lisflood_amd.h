@@ -424,6 +424,33 @@ int lf_upload_perturb_rows(int device, double *rows_dev, int members, int64_t st
                            int rank, const double *patterns_dev, int64_t pattern_stride,
                            const double *coeff_host, int multiplicative,
                            const double *lower_dev, double lower, const double *upper_dev, double upper);
+/* Sums ACROSS the elements of member rows -- zonal sums: a footprint, a basin, a member's total storage -- in a fixed order,
+ * so that the fp64 result is reproducible bit for bit (lisflood_amd.zonal.ZonePlan fixes the order on the host; no atomics
+ * anywhere).  ONE call is ONE pass: it sums `runs` runs of consecutive entries, run r = entries run_start_dev[r] ..
+ * run_start_dev[r + 1] - 1 (int32 [runs + 1] in device memory, ascending, at most 256 entries per run, run_start_dev[runs] <=
+ * entries -- the caller's word), for every member m < members:
+ *   entry e reads   x = rows_dev[m * stride + (index_dev ? index_dev[e] : e)]     (index_dev: int32 [entries] on the device)
+ *   its value is    t = divisor == 1.0 ? x : x / divisor                           (an IEEE division)
+ *                   t = weights_dev ? t * weights_dev[e] : t                       (one multiply, rounded on its own)
+ *   the run's values v[0 .. len) are padded to 256 with +0.0 -- a selected +0.0, never a product, and nothing is loaded for it;
+ *   lane l of 64:   s = 0.0;  s = s + v[l];  s = s + v[l + 64];  s = s + v[l + 128];  s = s + v[l + 192]
+ *   for d = 32, 16, 8, 4, 2, 1:   s[l] = s[l] + s[l + d]  for l < d
+ *   out_dev[m * out_stride + r] = s[0]
+ * so a run of length 0 gives +0.0, a -0.0 alone in a run gives +0.0, NaN and inf propagate.  A later pass sums the run sums
+ * of the pass before: its rows_dev is that pass's out_dev, its stride that out_stride, with no index, no weights and
+ * divisor 1.0; the passes end when every zone is one run.  Elements of a row that no entry names are never read (the elements
+ * between the rows in particular); elements of out_dev beyond `runs` in a row are never written.  A wavefront owns a run, holds
+ * its four entries per lane (position and weight) in registers and walks the members, the loads of four members issued before
+ * the first addition; the fold goes through __shfl_down; lane 0 stores.  With few runs the members also go on the grid's
+ * second dimension; which wavefront computes a (member, run) does not enter its arithmetic.  Traffic: 8 bytes per (member,
+ * entry), plus 4 (index) and 8 (weights) per entry once.  Asynchronous on the device's library stream, like
+ * lf_gather_rows_device; no allocation, no synchronisation, no LDS, no scratch.
+ * LF_E_INVALID, with the argument named, before a device is touched: members < 1, entries or runs negative or beyond the 32-bit
+ * range of a launch, runs > 0 without run_start_dev or out_dev, out_stride < runs, rows_dev NULL with entries > 0, a divisor that
+ * is 0 or a NaN.  runs == 0: LF_OK, nothing is launched. */
+int lf_members_zonal_device(int device, const double *rows_dev, int members, int64_t stride, double divisor, int64_t entries,
+                            const int32_t *index_dev, const double *weights_dev, int64_t runs, const int32_t *run_start_dev,
+                            double *out_dev, int64_t out_stride);
 /* Report maps in the form a map writer takes (lf_report.hip): for up to 16 sources in ONE launch, source k < nmaps,
  * row r < rows_host[k] and cell < cells = H * W,  dst_dev[k][r * cells + cell] =
  *     idx_dev[cell] >= 0 : convert(src_dev[k][r * stride_host[k] + idx_dev[cell]] / divisor_host[k])

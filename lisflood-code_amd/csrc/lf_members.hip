@@ -14,6 +14,8 @@
 //                       (k_members_regress_reg: the column in registers, up to 16 members)
 //   k_members_perturb : the forecast step's counterpart -- the member rows written or rewritten from one base row or their
 //                       own values plus / times a sum of `rank` static patterns weighted by a [members][rank] table
+//   k_members_zonal   : the one kernel here that sums ACROSS the elements of a row -- runs of up to 256 entries of every
+//                       member's row, one wavefront per run, in an order the plan fixes (its own section below)
 //
 // The value of (m, i) is rows[m * stride + i] / divisor, an IEEE division (divisor 1: the element itself), the result of
 // element i goes to dst_index ? dst_index[i] : i.  Everything is in member order: the sum is ((x0 + x1) + x2) + ..., the
@@ -564,6 +566,93 @@ void launch_perturb(hipStream_t s, double *rows, const double *base, const doubl
         hipLaunchKernelGGL((k_members_perturb<RANK, true>), grid, block, 0, s, rows, base, patterns, coeff, lower_dev, upper_dev, A);
 }
 
+// ---- sums across the elements of a member row: runs of up to 256 entries, one wavefront per run, in a fixed order --------------
+constexpr int kZonalRun = 256;          // entries of a run: four per lane of a wavefront
+constexpr int kZonalPerLane = kZonalRun / 64;
+constexpr int kZonalWaves = 4;          // runs (wavefronts) per workgroup
+constexpr int kZonalMembers = 4;        // members whose four loads per lane are in flight before the first fold
+constexpr long long kZonalFewBlocks = 1024; // below this many workgroups of runs the members go on the grid as well
+
+struct zonal_args {
+    const double *rows;
+    long long stride;
+    double divisor;
+    const int *index;
+    const double *weights;
+    long long runs;
+    const int *run_start;
+    double *out;
+    long long out_stride;
+    int members, members_per_block;
+};
+
+// One pass of the zonal reduction (lf_members_zonal_device).  A wavefront owns run r = entries run_start[r] .. run_start[r + 1]
+// - 1: lane l holds the row positions and weights of entries l, l + 64, l + 128 and l + 192 of the run in registers and walks
+// the members, kZonalMembers at a time -- their 4 x kZonalMembers loads are issued before the first addition.  A lane past the
+// end of its run loads nothing and contributes a selected +0.0 (never a product); the lane sum is ((0.0 + v0) + v1) + v2) + v3
+// and the fold s[l] = s[l] + s[l + d], d = 32 .. 1, goes through __shfl_down, so every run sum has one order whatever the
+// grid: blockIdx.y only says which members this wavefront walks.  Lane 0 stores.  No atomics, no LDS.
+template <bool DIV, bool WEIGHTED>
+__global__ void __launch_bounds__(64 * kZonalWaves) k_members_zonal(zonal_args A)
+{
+    const int lane = threadIdx.x & 63;
+    const long long r = (long long)blockIdx.x * kZonalWaves + (threadIdx.x >> 6);
+    if (r >= A.runs) return;
+    const int first = A.run_start[r], len = A.run_start[r + 1] - first;
+    bool on[kZonalPerLane];
+    long long at[kZonalPerLane];
+    double w[kZonalPerLane];
+#pragma unroll
+    for (int k = 0; k < kZonalPerLane; ++k) {
+        const int e = lane + 64 * k;
+        on[k] = e < len;
+        at[k] = on[k] ? (A.index ? (long long)A.index[first + e] : (long long)first + e) : 0;
+        w[k] = (WEIGHTED && on[k]) ? A.weights[first + e] : 0.0;
+    }
+    auto value = [&](int k, double raw) {
+        double v = member_value<DIV>(raw, A.divisor);
+        if (WEIGHTED) v = v * w[k];
+        return on[k] ? v : 0.0;
+    };
+    auto fold = [&](int m, const double (&raw)[kZonalPerLane]) {
+        double s = 0.0;
+#pragma unroll
+        for (int k = 0; k < kZonalPerLane; ++k) s = s + value(k, raw[k]);
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) s = s + __shfl_down(s, d);
+        if (lane == 0) A.out[(long long)m * A.out_stride + r] = s;
+    };
+    auto load = [&](int m, double (&raw)[kZonalPerLane]) {
+        const double *p = A.rows + (long long)m * A.stride;
+#pragma unroll
+        for (int k = 0; k < kZonalPerLane; ++k) raw[k] = on[k] ? row_load(p + at[k]) : 0.0;
+    };
+    int m = blockIdx.y * A.members_per_block;
+    const int end = m + A.members_per_block < A.members ? m + A.members_per_block : A.members;
+    for (; m + kZonalMembers <= end; m += kZonalMembers) {
+        double raw[kZonalMembers][kZonalPerLane];
+#pragma unroll
+        for (int u = 0; u < kZonalMembers; ++u) load(m + u, raw[u]);
+#pragma unroll
+        for (int u = 0; u < kZonalMembers; ++u) fold(m + u, raw[u]);
+    }
+    for (; m < end; ++m) {
+        double raw[kZonalPerLane];
+        load(m, raw);
+        fold(m, raw);
+    }
+}
+
+template <bool DIV>
+void launch_zonal(hipStream_t s, const zonal_args &A, dim3 grid)
+{
+    const dim3 block(64 * kZonalWaves);
+    if (A.weights)
+        hipLaunchKernelGGL((k_members_zonal<DIV, true>), grid, block, 0, s, A);
+    else
+        hipLaunchKernelGGL((k_members_zonal<DIV, false>), grid, block, 0, s, A);
+}
+
 // what the two perturb entry points refuse, in the order the header lists it (no device is touched)
 int check_perturb(const double *rows_dev, int members, int64_t stride, int64_t n, int rank, const double *patterns_dev,
                   int64_t pattern_stride, const double *coeff_host, int multiplicative, const double *lower_dev, double lower,
@@ -852,6 +941,43 @@ int lf_members_regress_device(int device, double *rows_dev, int members, int64_t
         launch_regress<256>(c->stream, rows_dev, cx_dev, cy_dev, table_dev, lower_dev, upper_dev, A);
     else
         launch_regress<128>(c->stream, rows_dev, cx_dev, cy_dev, table_dev, lower_dev, upper_dev, A);
+    LF_HIP(hipGetLastError());
+    return LF_OK;
+}
+
+int lf_members_zonal_device(int device, const double *rows_dev, int members, int64_t stride, double divisor, int64_t entries,
+                            const int32_t *index_dev, const double *weights_dev, int64_t runs, const int32_t *run_start_dev,
+                            double *out_dev, int64_t out_stride)
+{
+    if (members < 1) return lf_set_error(LF_E_INVALID, "members must be at least 1 (got %d)", members);
+    if (entries < 0 || entries > 0x7fffffffll)
+        return lf_set_error(LF_E_INVALID, "entries = %lld outside the 32-bit range of a launch", (long long)entries);
+    if (runs < 0 || runs > 0x7fffffffll)
+        return lf_set_error(LF_E_INVALID, "runs = %lld outside the 32-bit range of a launch", (long long)runs);
+    if (runs > 0 && !run_start_dev) return lf_set_error(LF_E_INVALID, "run_start_dev is NULL with runs = %lld", (long long)runs);
+    if (runs > 0 && !out_dev) return lf_set_error(LF_E_INVALID, "out_dev is NULL with runs = %lld", (long long)runs);
+    if (out_stride < runs)
+        return lf_set_error(LF_E_INVALID, "out_stride %lld is less than runs = %lld", (long long)out_stride, (long long)runs);
+    if (entries > 0 && !rows_dev) return lf_set_error(LF_E_INVALID, "rows_dev is NULL with entries = %lld", (long long)entries);
+    if (divisor == 0.0 || divisor != divisor) return lf_set_error(LF_E_INVALID, "divisor must be neither 0 nor a NaN (got %g)", divisor);
+    if (runs == 0) return LF_OK;
+    lf_device_ctx *c;
+    LF_TRY(lf_ctx(device, &c));
+    // Few runs leave most of the device idle while each wavefront walks every member: the members then go on the grid's
+    // second dimension, kZonalMembers per workgroup (LF_ZONAL_GRID=0 / 1 in the environment: never / always; A/B switch).
+    // Which wavefront computes a (member, run) does not enter its arithmetic.
+    const long long blocks = (runs + kZonalWaves - 1) / kZonalWaves;
+    const char *e = std::getenv("LF_ZONAL_GRID");
+    const bool split = e && (e[0] == '0' || e[0] == '1') ? e[0] == '1' : blocks < kZonalFewBlocks;
+    int per_block = members;
+    if (split && members > kZonalMembers && (members + kZonalMembers - 1) / kZonalMembers <= 65535) per_block = kZonalMembers;
+    const zonal_args A = {rows_dev, (long long)stride, divisor, (const int *)index_dev, weights_dev, (long long)runs,
+                          (const int *)run_start_dev, out_dev, (long long)out_stride, members, per_block};
+    const dim3 grid((unsigned)blocks, (unsigned)((members + per_block - 1) / per_block));
+    if (divisor == 1.0)
+        launch_zonal<false>(c->stream, A, grid);
+    else
+        launch_zonal<true>(c->stream, A, grid);
     LF_HIP(hipGetLastError());
     return LF_OK;
 }

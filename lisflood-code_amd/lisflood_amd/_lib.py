@@ -37,6 +37,7 @@ _SIGNATURES = {
     "ipiqqdpqipp": "members_order_statistics_device",
     "ipiqqdiiqpppipqpp": "members_track_device",
     "ipiqqdpqpppipqp": "members_summary_device",
+    "ipiqdqppqppq": "members_zonal_device",
     "ipiqqippppdpd": "members_regress_device",
     "ipiqqp": "members_resample_device",
     "ipiqqpipqpipdpd": "members_perturb_device upload_perturb_rows",

@@ -17,7 +17,15 @@ gauges in one pass over the state), with model error as the forecast half:
 
 inc.dropped lists the gauges that had no spread at their turn, inc.posterior is the analysed ensemble at the gauges.
 kind="perturbed" with perturbed_obs=obs + sqrt(obs_var) N(0, 1) gives the stochastic filter instead of the square-root
-one; coords=(X, Y) in regress() and the same coordinates in gauge_rc put the distances on any other two-coordinate map."""
+one; coords=(X, Y) in regress() and the same coordinates in gauge_rc put the distances on any other two-coordinate map.
+
+Areal observations -- satellite soil-moisture or snow footprints, basin averages -- enter the same way: the members' zone
+means take the place of the members at the gauges, the zones' centroids that of the gauges' places:
+
+    xy, radius = zone_geometry(footprints, land_mask)        # once: [Z, 2] centroids, [Z] equivalent radii in pixels
+    hx = ens.zonal("Theta1aPixel", footprints)               # [members, Z] footprint means, made on the device
+    inc = serial_increments(hx, obs, obs_var, xy, halfwidth=np.maximum(25.0, radius))
+    ens.regress(inc, bounds={"W1a": (0.0, None)})"""
 import numpy as np
 
 
@@ -187,6 +195,29 @@ def serial_increments(hx, obs, obs_var, gauge_xy, halfwidth, kind="eakf", pertur
     return SerialIncrements(np.array(anomalies, np.float64).reshape(len(kept), M), np.array(increments, np.float64).reshape(len(kept), M),
                             np.asarray(scale, np.float64), xy[K, 0].copy(), xy[K, 1].copy(), c[K].copy(), K,
                             np.asarray(dropped, np.int64), y)
+
+
+def zone_geometry(zones, land_mask, weights=None):
+    """Where an areal observation sits, for serial_increments() and regress(): zones as HotPathEnsemble.zonal() takes them
+    (an int label map [N] in pixel order, negative: no zone; or a sequence of Z arrays of compressed land indices) on the
+    land pixels of land_mask [H, W], weights [N] in pixel order as zonal() takes them (None: every pixel 1).
+    -> (centroids float64 [Z, 2]: the weighted mean (row, column) of the zone's pixels -- gauge_xy in regress()'s default
+    coordinates;  radius float64 [Z]: sqrt(pixels / pi), the radius of the disc with the zone's number of pixels, a lower
+    bound for the localisation half-width).  A zone without pixels, or whose weights sum to 0, has a NaN centroid."""
+    mask = np.asarray(land_mask)
+    if mask.ndim != 2 or mask.dtype != np.bool_:
+        raise ValueError("land_mask must be a boolean [H, W] array")
+    from .zonal import zone_pairs
+    rows, cols = np.nonzero(mask)
+    zone, pix, Z = zone_pairs(zones, rows.size)
+    w = np.ones(rows.size) if weights is None else np.asarray(weights, np.float64)
+    if w.shape != (rows.size,):
+        raise ValueError("weights must be [%d] in pixel order" % rows.size)
+    total = np.bincount(zone, w[pix], minlength=Z)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        centroids = np.stack([np.bincount(zone, w[pix] * rows[pix], minlength=Z) / total,
+                              np.bincount(zone, w[pix] * cols[pix], minlength=Z) / total], axis=1)
+    return centroids, np.sqrt(np.bincount(zone, minlength=Z) / np.pi)
 
 
 def systematic_parents(weights, u):

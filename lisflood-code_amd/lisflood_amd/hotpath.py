@@ -26,7 +26,8 @@ from . import routing as RT
 from . import snow_frost as SF
 from . import soilloop as SL
 from . import surface_routing as SR
-from ._lib import DeviceArray, PinnedArray, check, f64, lib, timer_start, timer_stop, u8
+from . import zonal as ZN
+from ._lib import DeviceArray, PinnedArray, check, f64, lib, ptr, timer_start, timer_stop, u8
 from .channel_domain import _structures_on_subdomain, channel_domain, inert_pixels  # noqa: F401 (inert_pixels: read from here)
 from .kinematic_wave_parallel import Graph, kinematicWave
 
@@ -1020,6 +1021,10 @@ class HotPathEnsemble(_HotPath):
     maximum over the members, the members above up to four threshold maps and order statistics (lf_members_summary_device,
     lf_members_order_statistics_device: one pass over the member rows as they lie, only the product maps cross PCIe) -- and
     sample(name, pixels), every member at a few gauges (lf_gather_rows_device), whose rows output.TssWriter.append takes.
+    zonal(name, zones, weights=, mean=) is the areal counterpart of sample() -- a satellite footprint, a basin average above
+    a gauge, a member's total storage for a water balance: [members, zones] sums or means of a member row over label-map or
+    index-list zones (lf_members_zonal_device, one call per pass of a zonal.ZonePlan), in a fixed order so that the fp64
+    bits are those of the numpy restatement; assimilation.zone_geometry gives the centroids serial_increments() takes.
     Maps that are written every step do not wait for the device at all: summary_rasters() and rasters() enqueue the pack
     kernel (lf_pack_rasters_device: [H, W] rasters of the writer's type, the fill outside the mask) and an asynchronous
     copy into page-locked memory on a download stream of its own, and return a PendingRasters to wait() on after the next
@@ -1164,6 +1169,8 @@ class HotPathEnsemble(_HotPath):
         self._weights, self._analysis_cache, self._analysis_pinned = None, {}, set()
         # regress(): the resident table of 256 gauges (made on first use) and the default coordinates (made once)
         self._regress_table, self._regress_coords = None, None
+        # zonal(): (zones object, weights object, row kind) -> the plan and its device tables (made on first use)
+        self._zonal = {}
 
     def _lai_vectors(self):
         return self.land.dev
@@ -1620,17 +1627,21 @@ class HotPathEnsemble(_HotPath):
             groups["channel" if channel else "land"].append((name, src, self.members, stride, divisor, True))
         return self._report_rasters(list(groups.items()), dtype, fill, side=not groups["land"])
 
+    def _position_of_pixel(self, channel):
+        """int64 [N]: compressed land index -> row position of the channel rows (or the land rows), -1 outside their domain"""
+        if channel not in self._row_of_pixel:
+            row = np.full(self.N, -1, np.int64)
+            row[self.gpix if channel else self.pixel_of_position] = np.arange(self.Nk if channel else self.N)
+            self._row_of_pixel[channel] = row
+        return self._row_of_pixel[channel]
+
     def _gauge_table(self, pixels, channel):
         """compressed land indices -> (device index in row positions, device [members, gauges] rows, gauges inside the
         rows' domain); a gauge outside it reads position 0 and is set to 0.0 afterwards"""
         pix = np.asarray(pixels, np.int64).reshape(-1)
         if pix.size and (pix.min() < 0 or pix.max() >= self.N):
             raise ValueError("pixels must be compressed land indices 0 .. %d" % (self.N - 1))
-        if channel not in self._row_of_pixel:
-            row = np.full(self.N, -1, np.int64)
-            row[self.gpix if channel else self.pixel_of_position] = np.arange(self.Nk if channel else self.N)
-            self._row_of_pixel[channel] = row
-        row = self._row_of_pixel[channel][pix]
+        row = self._position_of_pixel(channel)[pix]
         inside = row >= 0
         if not pix.size:
             return None, None, inside
@@ -1653,6 +1664,70 @@ class HotPathEnsemble(_HotPath):
         rows = dst.download().reshape(M, G)
         rows[:, ~inside] = 0.0
         return rows / divisor if divisor != 1.0 else rows
+
+    # ---- sums and means of the member rows over zones, in the fixed order of a zonal.ZonePlan ------------------------------
+    def _zonal_tables(self, zones, weights, channel):
+        """What zonal() keeps per (zones object, weights object, row kind), made once and cached like threshold sets and
+        gauge tables: the ZonePlan and on the device its index, its weights, the run table of every pass and the two partial
+        buffers the passes alternate between.  The entry holds both objects, so their ids stay their own."""
+        key = (id(zones), id(weights), channel)
+        hit = self._zonal.get(key)
+        if hit is not None and hit.zones is zones and hit.weights is weights:
+            return hit
+        stale = [key] if hit is not None else list(self._zonal)[:max(0, len(self._zonal) - self._CACHED + 1)]
+        for k in stale:                                # (an id that went to another object; beyond _CACHED the oldest)
+            for d in self._zonal.pop(k).arrays:
+                d.free()
+        plan = ZN.row_plan(zones, weights, self.N, self.gpix if channel else self.pixel_of_position, self._position_of_pixel(channel))
+        up = lambda a: DeviceArray.from_host(a, self.device) if a is not None and a.size else None
+        t = types.SimpleNamespace(zones=zones, weights=weights, plan=plan, index=up(plan.positions), wdev=up(plan.weights),
+                                  run_start=[up(s) for s in plan.run_start],
+                                  partial=[DeviceArray(self.members * max(1, plan.runs(p)), np.float64, self.device)
+                                           for p in range(min(2, plan.passes))])
+        t.arrays = [d for d in [t.index, t.wdev] + t.run_start + t.partial if d is not None]
+        self._zonal[key] = t
+        return t
+
+    def zonal_plan(self, zones, weights=None, name="LZ"):
+        """the zonal.ZonePlan zonal(name, zones, weights) sums by: which pixels go into which zone, in what order and in
+        which runs (the plan of a channel row differs from that of a land row: other positions, fewer pixels)"""
+        return self._zonal_tables(zones, weights, self._product_rows(name)[4]).plan
+
+    def zonal(self, name, zones, weights=None, mean=True):
+        """[members, Z]: every member's sum -- or, with mean=True, mean -- of one member vector over Z zones, made on the
+        device in a fixed order (lf_members_zonal_device, one call per pass of the plan; include/lisflood_amd.h states the
+        arithmetic, zonal.ZonePlan the order): only members * Z doubles cross PCIe, and the bits are those of the numpy
+        restatement on download(name) whatever the launch shape.
+        name: anything summary() takes -- a channel row, "ChanQAvg" (through the divisor), an [N] member row of the land
+        part (Theta1aPixel, SnowCover, LZ ...), an fp64 tracker row such as "LZ.period_mean".
+        zones: an int label map [N] in pixel order (labels 0 .. Z - 1, negative: no zone) or a sequence of Z arrays of
+        compressed land indices, which may overlap (the nested upstream areas of gauges).  weights: [N] in pixel order, e.g.
+        the pixel area; a value is x / divisor * weight, two roundings.  For a channel row a zone holds only its pixels
+        inside the channel domain, and so does its weight sum.
+        mean=True divides the sums on the host by plan.weight_sum (the same ordered sum over the weights, or the number of
+        pixels): an empty zone has the sum 0.0 and the mean NaN.
+        The plan and its device tables are kept per (zones object, weights object, row kind): pass the SAME arrays every
+        step.  Runs behind the channel loop of the last step (joins the side stream), like sample()."""
+        L, dev, M = lib(), self.device, self.members
+        src, _, stride, divisor, channel = self._product_rows(name)
+        t = self._zonal_tables(zones, weights, channel)
+        plan = t.plan
+        sums = np.zeros((M, plan.zones))
+        if plan.zones == 0:
+            return sums
+        check(L.lf_side_stream_join(dev))
+        rows, entries = src.ptr, plan.entries
+        for p in range(plan.passes):
+            first, runs, out = p == 0, plan.runs(p), t.partial[p % 2]
+            check(L.lf_members_zonal_device(dev, rows, M, stride, divisor if first else 1.0, entries,
+                                            t.index.ptr if first and t.index else None, t.wdev.ptr if first and t.wdev else None,
+                                            runs, t.run_start[p].ptr, out.ptr, runs))
+            rows, stride, entries = out.ptr, runs, runs
+        check(L.lf_memcpy_d2h(dev, ptr(sums), rows, sums.nbytes))
+        if not mean:
+            return sums
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return sums / plan.weight_sum
 
     # ---- products over the steps of a run: accumulators per member, updated on the device by every step -------------------
     _TRACK_MAX = 4         # names tracked at once
@@ -2125,7 +2200,8 @@ class HotPathEnsemble(_HotPath):
         self._regress_table = None
         products += [d for t in self._trackers.values() for d in list(t.dev.values()) + [t.thr]]
         products += [p[0] for p in self._perturbations.values()]
-        self._perturbations = {}
+        products += [d for t in self._zonal.values() for d in t.arrays]
+        self._perturbations, self._zonal = {}, {}
         self._thresholds, self._gauges, self._products, self._gpix_dev, self._outside_held = {}, {}, {}, None, {}
         self._trackers, self._weights, self._analysis_cache = {}, None, {}
         self._free_shared([self._gidx, self._side, self._pidx] + list(self._qin.values()) +
